@@ -12,6 +12,9 @@ backward, Adam, cosine LR) on a synthetic batch of BASELINE.json configs[1]: FNO
 [B=32/GPU, 20, 128, 128, 2], modes (4,12,16), width 64, 4 layers, fp32.  Inputs are resident in HBM when the
 timed region starts.  Rank 0 prints ONE JSON line with the whole-job samples/s, the roofline of the dominant
 kernel (HIP-event timed inside the timed region) and a CPU baseline (the oracle timed on the host cores).
+That line is the compact form of the result record (scalars and short labels); ``--record FILE`` writes the whole record.
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (see ``dump_outputs``): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -52,9 +55,16 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true", help="take roofline.traffic from profiles/traffic_per_launch.json instead of measuring it "
                     "now (default at N=1: two rocprofv3 --pmc request-size passes over tools/kbench.py cell_mix, --kernel-trace only, ~40 s)")
     ap.add_argument("--only-headline", action="store_true", help="the FNO train step only: no rollout, secondary models, PMC passes or CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, updated parameters, parameter gradients; "
+                         "large tensors as a fixed seeded sample) as DIR/<name>.npy, float32, <= 64 MB in all")
+    ap.add_argument("--record", metavar="FILE", default=None,
+                    help="write the full result record (every nested table and note) as JSON to FILE; stdout carries its compact form")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--proxy-worker", type=float, default=None, help=argparse.SUPPRESS)     # child process of the scaling proxy: ms of the B = 32 step
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.only_headline:
         a.no_cpu_baseline = a.no_rollout = a.no_transolver = a.no_galerkin = a.no_dpot = a.no_unet = a.no_bf16 = a.no_pmc = True
         a.no_scaling_proxy = True
@@ -78,6 +88,62 @@ def self_launch(a):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 17          # per tensor; larger tensors are dumped as a seeded sample of this many entries
+
+
+def dump_outputs(out_dir, loss, model, grad):
+    """What the last timed ``Trainer.step`` hands its caller: the loss, and the model it updated -- parameters (reference-format
+    state dict, BatchNorm running statistics included) and the parameter gradients of that step.  float32; complex tensors as
+    (real, imag) pairs; a tensor over DUMP_MAX_ELEMS entries is dumped as the entries at sorted indices drawn without replacement by
+    numpy's default_rng seeded with the CRC-32 of its name (the same for every run and build).  Returns {name: shape}.
+    The training step is bit-reproducible, so two runs of one build match exactly.  Across builds compare with a tolerance, and
+    expect the convs.*.bias gradients to be rounding noise: BatchNorm cancels them, and Adam turns that noise into full-size moves
+    of those biases and of the BatchNorm running means."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(-1)}
+    for prefix, sd in (("param", model.state_dict()), ("grad", model.grads_as_state_dict(grad))):
+        for k, v in sd.items():
+            arrays[f"{prefix}.{k}"] = v
+    total, shapes = 0, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = torch.view_as_real(t.resolve_conj()) if t.is_complex() else t
+        a = t.float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, DUMP_MAX_ELEMS, replace=False)
+            a = a[np.sort(idx)]
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def _line_scalar(v):
+    if isinstance(v, str):
+        return len(v) <= 160
+    if isinstance(v, list):
+        return len(v) <= 16 and all(isinstance(e, (int, float)) and not isinstance(e, bool) for e in v)
+    return v is None or isinstance(v, (bool, int, float))
+
+
+def compact_line(line):
+    """The stdout form of the result record: every top-level scalar, and of every top-level object its scalars, short strings and
+    short numeric lists.  Deeper tables and long notes stay in the full record (--record); ``roofline`` keeps flat copies of its
+    nested figures for this reason."""
+    out = {}
+    for k, v in line.items():
+        if isinstance(v, dict):
+            out[k] = {kk: vv for kk, vv in v.items() if _line_scalar(vv)}
+        elif _line_scalar(v):
+            out[k] = v
+    return out
 
 
 def usable_cores():
@@ -900,6 +966,11 @@ def main():
     ms_per_step = 1e3 * dt / a.steps
     value = B * world * a.steps / dt
 
+    # ---- --dump-outputs: the last timed step's results, before anything below steps the trainer again
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = {"dir": a.dump_outputs, "arrays": len(dump_outputs(a.dump_outputs, loss, model, trainer.grad))}
+
     # ---- N > 1: one more step with the collective instrumented (per-bucket schedule on the side stream, how long Adam waited for the
     #      last bucket, cost of the inline SyncBN reductions) -- outside the timed region
     dp_info = None
@@ -1236,9 +1307,16 @@ def main():
         line.update(extra)
         if not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
+        if dumped:
+            line["dumped_outputs"] = dumped
+        if a.record:
+            os.makedirs(os.path.dirname(os.path.abspath(a.record)), exist_ok=True)
+            with open(a.record, "w") as f:
+                json.dump(line, f)
+                f.write("\n")
         sys.stdout.flush()
         _flush_c_stdio()
-        print(json.dumps(line), flush=True)                 # the ONE JSON line, last thing on stdout
+        print(json.dumps(compact_line(line)), flush=True)   # the ONE JSON line, last thing on stdout
 
 
 if __name__ == "__main__":

@@ -334,8 +334,10 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
     // and the CU's memory path unevenly) and the mean wave lifetime is 0.87-0.92 of the launch.
     //      Mode 2 claims from ONE counter in HBM (device-scope atomic, a line ahead of its use): that also evens out the workgroups
     //      (those on odd XCDs run 3-8 % slower than those on even ones).
+    //      Launches that accumulate statistics (STATS != 0: BatchNorm sums, weight-gradient rows) keep the static deal: their per-wave
+    //      partial sums are over the lines a wave walked, and only a fixed line-to-wave map makes a training step bit-reproducible.
     __shared__ int claim_s;
-    const int DYN = (WG || (CMX_PF2 && !DFT && !BF && STATS != 2) || (CMX_PF2_BF && BF)) ? 0 : ((C2 && a.claim_mode == 2) ? 1 : a.claim_mode);   // C2: both halves walk the workgroup pair's own lines
+    const int DYN = (WG || STATS != 0 || (CMX_PF2 && !DFT && !BF && STATS != 2) || (CMX_PF2_BF && BF)) ? 0 : ((C2 && a.claim_mode == 2) ? 1 : a.claim_mode);   // C2: both halves walk the workgroup pair's own lines
     if (DYN == 1 && tid == 0) claim_s = CMX_WAVES;
     __syncthreads();
 
