@@ -34,7 +34,8 @@ extern "C" {
  *   2  round 4: rpb_cell_mix_bf16, rpb_cell_mix_eval_dft_bf16 and rpb_cell_mix_eval_crop gained `int spectra_bf16` before `stream`;
  *      round 5: rpb_dp_reduce_scatter_enqueue / rpb_dp_allgather_enqueue / rpb_dp_mark / rpb_dp_wait_mark / rpb_dp_set_model /
  *      rpb_adam_step_ranges added (additions only);
- *      round 6: rpb_dp_p2p_*, rpb_cell_mix_eval_dft_f16x2, rpb_cell_mix_eval_crop_f16x2, rpb_proj_fwd_f16x2 added (additions only) */
+ *      round 6: rpb_dp_p2p_*, rpb_cell_mix_eval_dft_f16x2, rpb_cell_mix_eval_crop_f16x2, rpb_proj_fwd_f16x2 added (additions only);
+ *      rpb_amax_exp, rpb_split2h, rpb_conv3x_wprep_f16x2, rpb_conv3x_f16x2 added (additions only) */
 #define RPB_ABI_VERSION 2
 const char* rpb_last_error(void);
 int rpb_abi_version(void);
@@ -340,6 +341,20 @@ int rpb_split3t(const float* x, void* planes_t, long M, int C, int ldx, int rev,
  *     rpb_conv3x_wgrad and transpose the three tap axes of its result (for meshes whose innermost dimension is not % 8). */
 int rpb_conv3x_wgrad_splits(long M, int Co, int Ci);
 int rpb_conv3x_wgrad(const void* Gt, const void* Xt, float* part, long M, int Co, int Ci, int Hc, int Wc, int Dc, void* stream);
+/* ---- the forward of that convolution on the opt-in "f16x2" eval arithmetic (csrc/rpb_conv3h.hip; Transolver / Unet3d .set_arith("f16x2")):
+ *      operands as two fp16 planes (both rounded to nearest even) of the tensor scaled by an exact power of two, three products per fp32
+ *      product (hi*hi + hi*lo + lo*hi; dropped term <= 2^-22 |a b|).  The exponents stay in device memory (no host synchronisation).
+ *      rpb_amax_exp: e[0] = the integer with max|x| * 2^e in [2^14, 2^15) over x[M][ldx] (C columns; C % 4 == 0), 0 for an all-zero
+ *        or non-finite tensor;
+ *      rpb_split2h: planes[2][M][C] (fp16 bit patterns) = rn(x * 2^e), rn(x * 2^e - hi) (C % 8 == 0);
+ *      rpb_conv3x_wprep_f16x2: W[N][27*Ci] as rpb_conv3x_wprep takes it -> 2 * N * 27 * Ci fp16 in MFMA B-operand order, scaled by 2^e
+ *        (e from rpb_amax_exp(W, N, 27 * Ci, 27 * Ci, e));
+ *      rpb_conv3x_f16x2: out[M][ldo] = ldexp(conv(planes, Wz), -(ea + ew)) + bias.  Shapes as rpb_conv3x. */
+int rpb_amax_exp(const float* x, long M, int C, int ldx, int* e, void* stream);
+int rpb_split2h(const float* x, void* planes, long M, int C, int ldx, const int* e, void* stream);
+int rpb_conv3x_wprep_f16x2(const float* W, void* Wz, int N, int Ci, const int* e, void* stream);
+int rpb_conv3x_f16x2(const void* planes, const void* Wz, const float* bias, float* out, long M, int N, int Ci, int ldo, int Hc,
+                     int Wc, int Dc, const int* ea, const int* ew, void* stream);
 /*     input pipeline: one pass from the full-resolution time slabs as they lie in the
  *     reference's Arrow cells -- planar [B][Cp][horizon][Hf][Wf] ((u, v, p): Cp = 3; combustion's `observed`: Cp = 1) and an
  *     optional channels-last cell cl [B][horizon][Hf][Wf][Cl] (combustion's 15 `numerical` channels) -- to the model's channels-last

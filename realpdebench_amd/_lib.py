@@ -161,6 +161,10 @@ SIGNATURES = {
     "rpb_split3": (_I, "pp" + "lii" + "p"),
     "rpb_conv3x_wprep": (_I, "pp" + "ii" + "p"),
     "rpb_conv3x": (_I, "pppp" + "liii" + "iii" + "p"),
+    "rpb_amax_exp": (_I, "p" + "lii" + "p" + "p"),
+    "rpb_split2h": (_I, "pp" + "lii" + "p" + "p"),
+    "rpb_conv3x_wprep_f16x2": (_I, "pp" + "ii" + "p" + "p"),
+    "rpb_conv3x_f16x2": (_I, "pppp" + "liii" + "iii" + "pp" + "p"),
     "rpb_split3t": (_I, "pp" + "lii" + "iiii" + "p"),
     "rpb_gemm3x_wprep": (_I, "pp" + "ii" + "p"),
     "rpb_gemm3x": (_I, "pppppp" + "liiii" + "i" + "ppp" + "lf" + "p"),

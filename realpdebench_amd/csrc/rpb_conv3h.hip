@@ -1,0 +1,434 @@
+// 3x3x3 convolution (padding 1) on the opt-in "f16x2" eval arithmetic: the implicit GEMM of rpb_conv3x.hip with every fp32
+// operand written as TWO fp16 numbers, both rounded to nearest even, after an exact power-of-two rescale per tensor:
+//   x * 2^e = hi + lo   (11 + 11 significand bits and the sign of lo: x to one fp32 unit in the last place)
+// and a product accumulated in fp32 from the three fp16 x fp16 products hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_f16 (the
+// bf16 rate on gfx950); the dropped term lo*lo is <= 2^-22 |a b|.  Three MFMAs instead of the six of the bf16x3 split.
+// fp16 has 5 exponent bits, so each tensor is first scaled by 2^e with max|x| * 2^e in [2^14, 2^15) (rpb_amax_exp, computed and
+// kept on the device: no host synchronisation); the lo plane of every element within 2^-16 of the maximum is then a normal or
+// exactly representable subnormal fp16.  The epilogue undoes both scales: out = ldexp(acc, -(ea + ew)) + bias.
+// Evaluation forward only (Transolver.set_arith / Unet3d.set_arith); training and data gradients stay on rpb_conv3x.
+//
+// Layout and tiling are those of conv3x_kernel: a workgroup owns 128 consecutive tokens, stages the 130 rows of each (kt, kh) and
+// 64-channel chunk in LDS (two planes: 2 x 33 KB per stage buffer instead of 2 x 50 KB), the w boundary is applied to the A operand,
+// weights are pre-arranged in MFMA B-operand order Wz[tap][Ci/16][2 planes][N/32][64 lanes][8] fp16.
+#include "rpb_common.h"
+#include <stdlib.h>
+
+typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4h __attribute__((ext_vector_type(4)));
+template <int V>
+struct ICh {
+    static constexpr int value = V;
+};
+
+#define CH_BM 128
+#define CH_ROWS (CH_BM + 2)
+
+__device__ __forceinline__ f32x16 mfma_f16(u32x4h a, u32x4h b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8h, a), __builtin_bit_cast(f16x8h, b), c, 0, 0, 0);
+}
+
+// x * 2^e -> (hi, lo) fp16 bit patterns, both RNE; non-finite values give a non-finite hi (and lo = NaN): they propagate
+__device__ __forceinline__ void split2h(float x, int e, unsigned& h, unsigned& l) {
+    const float v = ldexpf(x, e);                                       // exact (power of two, no overflow by the choice of e)
+    const _Float16 hi = (_Float16)v;
+    const _Float16 lo = (_Float16)(v - (float)hi);                      // v - hi exact in fp32
+    h = __builtin_bit_cast(unsigned short, hi);
+    l = __builtin_bit_cast(unsigned short, lo);
+}
+
+// ---------------------------------------------------------------------------------- per-tensor exponent
+// bits = max over the tensor of (|x| as an unsigned fp32 pattern): for non-negative floats the integer order is the float order,
+// and NaN / inf patterns sort above every finite value
+__global__ __launch_bounds__(256) void amax_bits_kernel(const float* __restrict__ x, long M, int C, int ldx, unsigned* __restrict__ bits) {
+    const int c4n = C >> 2;
+    const long total = M * c4n;
+    unsigned mx = 0;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long m = idx / c4n;
+        const int c4 = (int)(idx - m * c4n);
+        // loaded as unsigned: a bit cast of each element of an f32x4 compiled to a compare of element 0 only
+        const u32x4h v = *reinterpret_cast<const u32x4h*>(x + m * ldx + c4 * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned u = v[i] & 0x7FFFFFFFu;
+            mx = u > mx ? u : mx;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned t = __shfl_xor(mx, o);
+        mx = t > mx ? t : mx;
+    }
+    __shared__ unsigned wm[4];
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned r = wm[0];
+        for (int w = 1; w < 4; ++w) r = wm[w] > r ? wm[w] : r;
+        atomicMax(bits, r);
+    }
+}
+
+// bits -> e with max|x| * 2^e in [2^14, 2^15); 0 for an all-zero or non-finite tensor.  The binary exponent is read from the bits
+// (normal: biased exponent - 127; subnormal: position of the leading one - 149).
+__global__ void amax_exp_finish_kernel(int* e) {
+    const unsigned b = (unsigned)e[0];
+    int r = 0;
+    if (b != 0 && b < 0x7F800000u) r = 14 - (b >= 0x00800000u ? (int)(b >> 23) - 127 : (31 - __builtin_clz(b)) - 149);
+    e[0] = r;
+}
+
+extern "C" int rpb_amax_exp(const float* x, long M, int C, int ldx, int* e, void* stream) {
+    RPB_REQUIRE(x && e && M > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C, "amax_exp: bad arguments (C=%d ldx=%d)", C, ldx);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(e, 0, sizeof(int), st) != hipSuccess) RPB_FAIL(RPB_ERR_LAUNCH, "amax_exp: memset failed");
+    const long total = M * (C / 4);
+    long grid = (total + 255) / 256;
+    const long cap = (long)rpb_num_cus() * 4;
+    if (grid > cap) grid = cap;
+    hipLaunchKernelGGL(amax_bits_kernel, dim3((unsigned)grid), dim3(256), 0, st, x, M, C, ldx, (unsigned*)e);
+    hipLaunchKernelGGL(amax_exp_finish_kernel, dim3(1), dim3(1), 0, st, e);
+    RPB_CHECK_LAUNCH("amax_exp");
+}
+
+// ---------------------------------------------------------------------------------- activation planes
+// x [M][ldx] fp32 (C channels used) -> P[2][M][C] fp16 of x * 2^e; one thread = 8 channels (32 B in, 2 x 16 B out)
+__global__ __launch_bounds__(256) void split2h_kernel(const float* __restrict__ x, uint16_t* __restrict__ P, long M, int C, int ldx,
+                                                      const int* __restrict__ ep) {
+    const int e = *ep;
+    const int c8n = C >> 3;
+    const long total = M * c8n;
+    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const long m = idx / c8n;
+        const int c8 = (int)(idx - m * c8n);
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(x + m * ldx + c8 * 8);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(x + m * ldx + c8 * 8 + 4);
+        unsigned h[8], lo[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            split2h(v0[i], e, h[i], lo[i]);
+            split2h(v1[i], e, h[4 + i], lo[4 + i]);
+        }
+        uint4 oh, ol;
+        oh.x = h[0] | (h[1] << 16); oh.y = h[2] | (h[3] << 16); oh.z = h[4] | (h[5] << 16); oh.w = h[6] | (h[7] << 16);
+        ol.x = lo[0] | (lo[1] << 16); ol.y = lo[2] | (lo[3] << 16); ol.z = lo[4] | (lo[5] << 16); ol.w = lo[6] | (lo[7] << 16);
+        const long o = m * C + c8 * 8;
+        *reinterpret_cast<uint4*>(P + o) = oh;
+        *reinterpret_cast<uint4*>(P + M * C + o) = ol;
+    }
+}
+
+extern "C" int rpb_split2h(const float* x, void* planes, long M, int C, int ldx, const int* e, void* stream) {
+    RPB_REQUIRE(x && planes && e && M > 0 && C > 0 && C % 8 == 0 && ldx % 4 == 0 && ldx >= C, "split2h: bad arguments (C=%d ldx=%d)", C, ldx);
+    const long total = M * (C / 8);
+    long grid = (total + 255) / 256;
+    const long cap = (long)rpb_num_cus() * 16;
+    if (grid > cap) grid = cap;
+    hipLaunchKernelGGL(split2h_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)planes, M, C, ldx, e);
+    RPB_CHECK_LAUNCH("split2h");
+}
+
+// ---------------------------------------------------------------------------------- weights in B-operand order
+// W [N][27 * Ci] fp32 -> Wz[tap][Ci/16][2 planes][N/32][64 lanes][8] fp16 of W * 2^e, lane = (co & 31) + 32 * k-half,
+// element j <-> ci = 16 cc + 8 half + j (the order of conv3x_wprep with two planes)
+__global__ __launch_bounds__(256) void conv3x_wprep_f16x2_kernel(const float* __restrict__ W, uint16_t* __restrict__ Wz, int N, int Ci,
+                                                                 const int* __restrict__ ep) {
+    const int NT = N >> 5, NCC = Ci >> 4;
+    const long total = 27L * NCC * NT * 64;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int e = *ep;
+    const int lane = (int)(idx & 63);
+    long r = idx >> 6;
+    const int nt = (int)(r % NT);
+    r /= NT;
+    const int cc = (int)(r % NCC);
+    const int tap = (int)(r / NCC);
+    const int co = nt * 32 + (lane & 31), half = lane >> 5;
+    const float* src = W + (long)co * 27 * Ci + (long)tap * Ci + cc * 16 + half * 8;
+    unsigned h[8], lo[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) split2h(src[j], e, h[j], lo[j]);
+    uint4 o[2];
+    o[0].x = h[0] | (h[1] << 16); o[0].y = h[2] | (h[3] << 16); o[0].z = h[4] | (h[5] << 16); o[0].w = h[6] | (h[7] << 16);
+    o[1].x = lo[0] | (lo[1] << 16); o[1].y = lo[2] | (lo[3] << 16); o[1].z = lo[4] | (lo[5] << 16); o[1].w = lo[6] | (lo[7] << 16);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const long dst = (((((long)tap * NCC + cc) * 2 + p) * NT + nt) * 64 + lane) * 8;
+        *reinterpret_cast<uint4*>(Wz + dst) = o[p];
+    }
+}
+
+extern "C" int rpb_conv3x_wprep_f16x2(const float* W, void* Wz, int N, int Ci, const int* e, void* stream) {
+    RPB_REQUIRE(W && Wz && e && N > 0 && N % 32 == 0 && Ci > 0 && Ci % 16 == 0, "conv3x_wprep_f16x2: N=%d Ci=%d unsupported", N, Ci);
+    const long total = 27L * (Ci / 16) * (N / 32) * 64;
+    hipLaunchKernelGGL(conv3x_wprep_f16x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W,
+                       (uint16_t*)Wz, N, Ci, e);
+    RPB_CHECK_LAUNCH("conv3x_wprep_f16x2");
+}
+
+// ---------------------------------------------------------------------------------- the convolution
+struct Conv3hArgs {
+    const uint16_t* P;     // [2][M][Ci] fp16 planes of the scaled input tokens
+    const uint16_t* Wz;    // B-operand order, see above
+    const float* bias;     // [N] or null
+    float* out;            // [M][ldo]
+    const int* ea;         // exponent of the activations
+    const int* ew;         // exponent of the weights
+    long M;
+    int N, Ci, ldo, T, H, W;
+};
+
+// WN: waves over co (64 each), KS = 4 / WN split the 16-channel chunks of a stage.  One workgroup per CU, one wave per SIMD, as
+// conv3x_kernel: the two-plane stage pair (66.6 KB of LDS) would fit two workgroups per CU, but at the 256 registers per wave that
+// allows the N >= 128 instances spill 35 / 46 VGPRs to scratch (-Rpass-analysis=kernel-resource-usage: 128 accumulators + 36 staging
+// + 48 operand registers); with the whole register file they hold 168-239 VGPRs + 128 AGPRs and no spill.
+template <int WN>
+__global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
+    constexpr int KS = 4 / WN;
+    extern __shared__ u32x4h lds4h[];
+    // two stage buffers of [2 planes][4 chunks][2 halves][CH_ROWS] x 16 B, then [9][CH_ROWS] row validity per (kt, kh)
+    unsigned char* rv = reinterpret_cast<unsigned char*>(lds4h + 2 * 16 * CH_ROWS);
+    const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nw = wave % WN, kp = wave / WN;
+    // XCD-aware tile order (as conv3x_kernel)
+    const unsigned chunk = gridDim.x >> 3;
+    const long tile = (long)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    const long m0 = tile * CH_BM;
+    if (m0 >= a.M) return;
+    const int n0 = blockIdx.y * (64 * WN) + nw * 64;
+    const int NT = a.N >> 5, NCC = a.Ci >> 4;
+    const unsigned uT = a.T, uH = a.H, uW = a.W;
+
+    for (int idx = tid; idx < 9 * CH_ROWS; idx += 256) {
+        const int g = idx / CH_ROWS, j = idx - g * CH_ROWS;
+        const int kt = g / 3, kh = g - kt * 3;
+        const long q = m0 - 1 + j + ((long)(kt - 1) * a.H + (kh - 1)) * a.W;
+        bool ok = q >= 0 && q < a.M;
+        if (ok) {
+            const unsigned uq = (unsigned)q, r = uq / uW;
+            const int hq = (int)(r % uH), tq = (int)((r / uH) % uT);
+            const int tt = tq - kt + 1, hh = hq - kh + 1;
+            ok = tt >= 0 && tt < a.T && hh >= 0 && hh < a.H;
+        }
+        rv[idx] = ok ? 1 : 0;
+    }
+    bool wlo[4], whi[4];                                                // my output tokens at the w boundaries
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm) {
+        const unsigned w = (unsigned)(m0 + tm * 32 + col) % uW;
+        wlo[tm] = (w == 0);
+        whi[tm] = (w == uW - 1);
+    }
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm) acc[tm][0] = acc[tm][1] = zero16();
+    const u32x4h z4 = {0u, 0u, 0u, 0u};
+    const long MC = a.M * a.Ci;
+
+    // software pipeline of conv3x_kernel: next stage's A loads spread over the current stage's tap steps, next tap step's B operands
+    // requested before the current one's MFMAs, A operands of the next row tile read from LDS before the current tile's MFMAs
+    constexpr int SPS = 4 / KS;                                        // my 16-channel chunks per stage
+    const int nc64 = a.Ci >> 6;
+    const uint16_t* wbase = a.Wz + ((long)(n0 >> 5) * 64 + lane) * 8;
+    const long wplane = (long)NT * 512;                                // fp16 elements between the planes of one (tap, chunk)
+    const long wchunk = 2 * wplane, wtap = (long)NCC * wchunk;
+    auto bload = [&](const uint16_t* src, u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) b[tn][p] = *reinterpret_cast<const u32x4h*>(src + p * wplane + tn * 512);
+    };
+    u32x4h bc[2][2], bn[2][2];
+    const u32x4h* As = lds4h;
+    u32x4h ac[2], an[2];
+    auto lda = [&](int s, int kw, int tm, u32x4h (&av)[2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) av[p] = As[((p * 4 + s) * 2 + half) * CH_ROWS + tm * 32 + col + kw];
+    };
+    auto mfma6 = [&](int tm, int kw, u32x4h (&av)[2], const u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+        if ((kw == 0 && wlo[tm]) || (kw == 2 && whi[tm])) av[0] = av[1] = z4;
+        // small terms first; the two co tiles alternate so consecutive MFMAs are independent
+        acc[tm][0] = mfma_f16(av[1], b[0][0], acc[tm][0]);
+        acc[tm][1] = mfma_f16(av[1], b[1][0], acc[tm][1]);
+        acc[tm][0] = mfma_f16(av[0], b[0][1], acc[tm][0]);
+        acc[tm][1] = mfma_f16(av[0], b[1][1], acc[tm][1]);
+        acc[tm][0] = mfma_f16(av[0], b[0][0], acc[tm][0]);
+        acc[tm][1] = mfma_f16(av[0], b[1][0], acc[tm][1]);
+    };
+    auto tap_step = [&](int s, int kw, bool more, const u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+        lda(s, kw, 1, an);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma6(0, kw, ac, b);
+        __builtin_amdgcn_sched_barrier(0);
+        lda(s, kw, 2, ac);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma6(1, kw, an, b);
+        __builtin_amdgcn_sched_barrier(0);
+        lda(s, kw, 3, an);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma6(2, kw, ac, b);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) lda(kw == 2 ? s + KS : s, kw == 2 ? 0 : kw + 1, 0, ac);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma6(3, kw, an, b);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto bsel = [&](auto pc) -> u32x4h(&)[2][2] {
+        if constexpr (decltype(pc)::value) return bn;
+        else return bc;
+    };
+    // A staging registers: 9 x 16 B per thread (130 rows x 16 pieces of 16 B over 256 threads), named individually
+    constexpr int NLD = (CH_ROWS * 16 + 255) / 256;
+    static_assert(NLD == 9, "staging macros below are written for 9 loads per thread");
+#define CH_FOR9(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define CH_DECL(J) u32x4h sv##J = z4; bool ok##J = false;
+    CH_FOR9(CH_DECL)
+#define CH_LOAD(J)                                                                                            \
+    if constexpr (J >= j0 && J < j1) {                                                                        \
+        const int idx = tid + J * 256;                                                                        \
+        const int row = idx >> 4, rem = idx & 15;                                                             \
+        const int p = rem >> 3, sh = rem & 7; /* sh = 2 * chunk + half: 8 x 16 B = one 128 B line */          \
+        ok##J = idx < CH_ROWS * 16 && rv[g * CH_ROWS + (row < CH_ROWS ? row : 0)];                            \
+        const long off = ok##J ? (long)p * MC + (rowbase + row) * a.Ci + c * 64 + sh * 8 : 0;                 \
+        sv##J = *reinterpret_cast<const u32x4h*>(a.P + off);                                                  \
+    }
+#define CH_STORE(J)                                                                                           \
+    {                                                                                                         \
+        const int idx = tid + J * 256;                                                                        \
+        const int row = idx >> 4, rem = idx & 15;                                                             \
+        if (idx < CH_ROWS * 16) dst[rem * CH_ROWS + row] = ok##J ? sv##J : z4;                                \
+    }
+    auto stage_load = [&](int g, int c, auto j0c, auto j1c) __attribute__((always_inline)) {
+        constexpr int j0 = decltype(j0c)::value, j1 = decltype(j1c)::value;
+        const int kt = g / 3, kh = g - kt * 3;
+        const long rowbase = m0 - 1 + ((long)(kt - 1) * a.H + (kh - 1)) * a.W;
+        CH_FOR9(CH_LOAD)
+    };
+    auto stage_store = [&](u32x4h* dst) __attribute__((always_inline)) { CH_FOR9(CH_STORE) };
+    bload(wbase + (long)kp * wchunk, bc);                               // (g 0, c 0, s = kp, kw 0)
+    stage_load(0, 0, ICh<0>{}, ICh<NLD>{});
+    stage_store(lds4h);
+    __syncthreads();
+    int buf = 0;
+    constexpr int NST = 3 * SPS;                                        // tap steps per stage
+    for (int g = 0; g < 9; ++g) {
+        for (int c = 0; c < nc64; ++c) {
+            int gn = g, cn = c + 1;                                     // next stage
+            if (cn == nc64) {
+                cn = 0;
+                ++gn;
+            }
+            const bool more = gn < 9;
+            As = lds4h + buf * 16 * CH_ROWS;
+            lda(kp, 0, 0, ac);
+#define CH_SI_BLOCK(SI)                                                                                        \
+    if constexpr (SI < SPS) {                                                                                  \
+        const int s = kp + SI * KS;                                                                            \
+        const uint16_t* w0 = wbase + (long)(g * 3) * wtap + (long)(c * 4 + s) * wchunk;                        \
+        bload(w0 + wtap, bsel(ICh<(SI * 3 + 1) & 1>{}));                                                       \
+        if (more) stage_load(gn, cn, ICh<(SI * 3 + 0) * NLD / NST>{}, ICh<(SI * 3 + 1) * NLD / NST>{});        \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
+        tap_step(s, 0, true, bsel(ICh<(SI * 3 + 0) & 1>{}));                                                   \
+        bload(w0 + 2 * wtap, bsel(ICh<(SI * 3 + 2) & 1>{}));                                                   \
+        if (more) stage_load(gn, cn, ICh<(SI * 3 + 1) * NLD / NST>{}, ICh<(SI * 3 + 2) * NLD / NST>{});        \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
+        tap_step(s, 1, true, bsel(ICh<(SI * 3 + 1) & 1>{}));                                                   \
+        if (SI + 1 < SPS) bload(w0 + (long)KS * wchunk, bsel(ICh<(SI * 3 + 3) & 1>{}));                        \
+        else if (more) bload(wbase + (long)(gn * 3) * wtap + (long)(cn * 4 + kp) * wchunk, bsel(ICh<(SI * 3 + 3) & 1>{})); \
+        if (more) stage_load(gn, cn, ICh<(SI * 3 + 2) * NLD / NST>{}, ICh<(SI * 3 + 3) * NLD / NST>{});        \
+        __builtin_amdgcn_sched_barrier(0);                                                                     \
+        tap_step(s, 2, SI + 1 < SPS, bsel(ICh<(SI * 3 + 2) & 1>{}));                                           \
+    }
+            CH_SI_BLOCK(0) CH_SI_BLOCK(1) CH_SI_BLOCK(2) CH_SI_BLOCK(3)
+            if constexpr (NST & 1) {                                    // odd step count (N = 64): the next stage's first B set is in bn
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) bc[tn][p] = bn[tn][p];
+            }
+            if (more) stage_store(lds4h + (buf ^ 1) * 16 * CH_ROWS);
+            __syncthreads();                                            // everyone is done with buf and has filled buf ^ 1
+            buf ^= 1;
+        }
+    }
+#undef CH_SI_BLOCK
+#undef CH_STORE
+#undef CH_LOAD
+#undef CH_DECL
+#undef CH_FOR9
+    // ---- K-split partial sums through LDS in one round (as conv3x_kernel)
+    float* red = reinterpret_cast<float*>(lds4h);                       // [WN][4 tiles][KS - 1 sources][2 col tiles][16 regs][64 lanes]
+    if (KS > 1) {
+        __syncthreads();
+#pragma unroll
+        for (int tm = 0; tm < 4; ++tm) {
+            const int owner = tm % KS;
+            if (kp != owner) {
+                const int rank = kp < owner ? kp : kp - 1;
+                float* slot = red + ((nw * 4 + tm) * (KS - 1) + rank) * 2048;
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) slot[(tn * 16 + r) * 64 + lane] = acc[tm][tn][r];
+            }
+        }
+        __syncthreads();
+    }
+    const int esum = -(*a.ea + *a.ew);
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm) {
+        if (KS > 1 && kp != tm % KS) continue;
+        if (KS > 1) {
+#pragma unroll
+            for (int k2 = 0; k2 < KS - 1; ++k2) {
+                const float* slot = red + ((nw * 4 + tm) * (KS - 1) + k2) * 2048;
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[tm][tn][r] += slot[(tn * 16 + r) * 64 + lane];
+            }
+        }
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            const int n = n0 + tn * 32 + col;
+            const float bv = a.bias ? a.bias[n] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long m = m0 + tm * 32 + mfma_row(lane, r);
+                if (m < a.M) a.out[m * a.ldo + n] = ldexpf(acc[tm][tn][r], esum) + bv;
+            }
+        }
+    }
+}
+
+// bytes of dynamic LDS: the two stage buffers + validity table, or the K-split reduction if larger (N = 64: 4 tiles x 3 sources x 8 KB)
+static size_t conv3h_lds(int WN) {
+    const size_t stage = (size_t)2 * 16 * CH_ROWS * 16 + 9 * CH_ROWS + 16;
+    const size_t red = (size_t)WN * 4 * (4 / WN - 1) * 2048 * 4;
+    return stage > red ? stage : red;
+}
+
+template <int WN>
+static void conv3h_launch(const Conv3hArgs& a, unsigned gx, unsigned gy, hipStream_t st) {
+    const size_t lds = conv3h_lds(WN);
+    (void)hipFuncSetAttribute((const void*)conv3x_f16x2_kernel<WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(conv3x_f16x2_kernel<WN>, dim3(gx, gy), dim3(256), lds, st, a);
+}
+
+extern "C" int rpb_conv3x_f16x2(const void* planes, const void* Wz, const float* bias, float* out, long M, int N, int Ci, int ldo,
+                                int Hc, int Wc, int Dc, const int* ea, const int* ew, void* stream) {
+    RPB_REQUIRE(planes && Wz && out && ea && ew && M > 0 && M < (1L << 31), "conv3x_f16x2: bad arguments");
+    RPB_REQUIRE(Ci % 64 == 0 && (N == 64 || N == 128 || N % 256 == 0) && ldo >= N,
+                "conv3x_f16x2: N=%d Ci=%d unsupported (Ci %% 64, N = 64, 128 or a multiple of 256)", N, Ci);
+    RPB_REQUIRE(Hc > 0 && Wc > 0 && Dc > 0 && M % ((long)Hc * Wc * Dc) == 0, "conv3x_f16x2: bad mesh");
+    Conv3hArgs a{(const uint16_t*)planes, (const uint16_t*)Wz, bias, out, ea, ew, M, N, Ci, ldo, Hc, Wc, Dc};
+    const unsigned gx = (unsigned)(((M + CH_BM - 1) / CH_BM + 7) / 8 * 8);
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 64) conv3h_launch<1>(a, gx, 1, st);
+    else if (N == 128) conv3h_launch<2>(a, gx, 1, st);
+    else conv3h_launch<4>(a, gx, N / 256, st);
+    RPB_CHECK_LAUNCH("conv3x_f16x2");
+}

@@ -95,6 +95,8 @@ class Transolver(_ModelBase):
                                      for i in range(n_layers)])
         self.placeholder = nn.Parameter((1.0 / n_hidden) * torch.rand(n_hidden))
         self._wcat = {}
+        self._wh = {}                   # block -> (key, f16x2 weight planes of _conv_cat) for the f16x2 eval forward
+        self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
         self._mask_override = None      # tests: list of (attn_mask [B,h,G,G], out_mask [M,C]) per block, already scaled
 
     # fused, re-laid-out weight of the two convolutions: rows 0..C-1 = in_project_fx, C..2C-1 = in_project_x;
@@ -110,6 +112,24 @@ class Transolver(_ModelBase):
             b = torch.cat([a.in_project_fx.bias.detach(), a.in_project_x.bias.detach()]).contiguous()
             self._wcat[i] = (key, w, b)
         return self._wcat[i][1], self._wcat[i][2]
+
+    def _conv_cat_f16x2(self, i):
+        """_conv_cat's weight as ops.conv3_f16x2_weights planes, cached under the same key."""
+        wcat, _ = self._conv_cat(i)
+        key = self._wcat[i][0]
+        if self._wh.get(i, (None,))[0] != key:
+            self._wh[i] = (key, ops.conv3_f16x2_weights(wcat, 2 * self.n_hidden, self.n_hidden))
+        return self._wh[i][1]
+
+    def set_arith(self, arith):
+        """Arithmetic of the evaluation / rollout forward's 3x3x3 convolutions: ``"f32"`` (default, the parity path: operands as three
+        bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power
+        of two, three products, dropped term <= 2^-22; csrc/rpb_conv3h.hip).  Only the forward that records no backward changes:
+        training forwards, data gradients and weight gradients stay on the default arithmetic."""
+        if arith not in ("f32", "f16x2"):
+            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
+        self.arith = arith
+        return self
 
     # ------------------------------------------------------------------ forward (optionally saving for backward)
     @torch.no_grad()
@@ -153,7 +173,10 @@ class Transolver(_ModelBase):
                 st.update(fx0=fx, a1=a, xf=xf, w=w, tokS=tokS, norm=norm, tok2=tok2, ox=ox)
             ops.layernorm_fwd(fx, blk.ln_1.weight.data, blk.ln_1.bias.data, a, M, C)
             wcat, bcat = self._conv_cat(i)
-            ops.conv3(a, wcat, xf, M, 2 * C, C, (self.H, self.W, self.D), bias=bcat)
+            if not keep and self.arith == "f16x2" and ops.conv3_split_ok(2 * C, C):
+                ops.conv3(a, wcat, xf, M, 2 * C, C, (self.H, self.W, self.D), bias=bcat, arith="f16x2", wh=self._conv_cat_f16x2(i))
+            else:
+                ops.conv3(a, wcat, xf, M, 2 * C, C, (self.H, self.W, self.D), bias=bcat)
             ops.slice_fwd(xf, at.in_project_slice.weight.data, at.in_project_slice.bias.data,
                           at.temperature.data.reshape(-1).contiguous(), w, tok_part, norm_part, B, ntok, heads, G, 2 * C)
             # per-sample finish of the block partials (deterministic fp64 sums), all samples in one launch each

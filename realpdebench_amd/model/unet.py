@@ -211,6 +211,7 @@ class Unet3d(_ModelBase):
         resnet("final_conv.0", dim * 2, dim, temb=False)
         conv("final_conv.1", self.out_dim, dim, 1, 1, 1)
         self._wcache = {}
+        self.arith = "f32"              # arithmetic of the eval / rollout forward's 3x3x3 convolutions, see set_arith
 
     # ------------------------------------------------------------------ parameter tree with the reference's names
     def _register(self, name, value, buffer=False):
@@ -292,6 +293,27 @@ class Unet3d(_ModelBase):
         self._wcache[key] = (w._version, v)
         return v
 
+    def _w_f16x2(self, name, Co, Ci):
+        """The "conv3" re-layout of ``name`` as ops.conv3_f16x2_weights planes + exponent, cached by ``_version`` like ``_w``."""
+        w = self.p(name)
+        key = ("conv3_f16x2", name)
+        hit = self._wcache.get(key)
+        if hit is not None and hit[0] == w._version and hit[1][0].device == w.device:
+            return hit[1]
+        v = ops.conv3_f16x2_weights(self._w("conv3", name), Co, Ci)
+        self._wcache[key] = (w._version, v)
+        return v
+
+    def set_arith(self, arith):
+        """Arithmetic of the evaluation / rollout forward's 3x3x3 convolutions: ``"f32"`` (default, the parity path: operands as three
+        bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power
+        of two, three products, dropped term <= 2^-22; csrc/rpb_conv3h.hip).  Only the forward that records no backward changes:
+        training forwards, data gradients and weight gradients stay on the default arithmetic."""
+        if arith not in ("f32", "f16x2"):
+            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
+        self.arith = arith
+        return self
+
     # ------------------------------------------------------------------ primitives (forward + taped backward)
     def _linear(self, tp, x, wname, bname, M, N, K, residual=None):
         """y = x W^T + b (+ residual) for nn.Linear / 1x1 convolutions."""
@@ -327,7 +349,11 @@ class Unet3d(_ModelBase):
         """nn.Conv3d(Ci, Co, 3, padding=1) on the (T,H,W) mesh."""
         M = B * mesh[0] * mesh[1] * mesh[2]
         y = _new(M, Co, like=x)
-        ops.conv3(x, self._w("conv3", name + ".weight"), y, M, Co, Ci, mesh, bias=self.p(name + ".bias").detach())
+        if not tp.record and self.arith == "f16x2" and ops.conv3_split_ok(Co, Ci):
+            ops.conv3(x, self._w("conv3", name + ".weight"), y, M, Co, Ci, mesh, bias=self.p(name + ".bias").detach(), arith="f16x2",
+                      wh=self._w_f16x2(name + ".weight", Co, Ci))
+        else:
+            ops.conv3(x, self._w("conv3", name + ".weight"), y, M, Co, Ci, mesh, bias=self.p(name + ".bias").detach())
 
         def bwd():
             gy = tp.grad(y)

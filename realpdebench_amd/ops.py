@@ -722,6 +722,31 @@ def conv3x(planes, Wz, out, M, N, Ci, mesh, bias=None, ldo=None):
               label=f"conv3x[N{N},Ci{Ci}]", nbytes=6 * M * Ci * 9 + 4 * M * N, flops=2 * M * N * 27 * Ci)
 
 
+def amax_exp(x, e, M, C, ldx=None):
+    """e[0] (int32 on the device) = the exponent with max|x| * 2^e in [2^14, 2^15) over x[M][ldx] (C columns); 0 when all-zero or
+    non-finite.  Stays on the device: no host synchronisation."""
+    _lib.call("rpb_amax_exp", _p(x), M, C, C if ldx is None else ldx, _p(e, torch.int32), _stream(), label="amax_exp", nbytes=4 * M * C)
+
+
+def split2h(x, planes, M, C, e, ldx=None):
+    """planes[2][M][C] (fp16 bit patterns in an int16 tensor) = hi / lo of x[M][ldx] * 2^e[0], both rounded to nearest even."""
+    _lib.call("rpb_split2h", _p(x), _p(planes, torch.int16), M, C, C if ldx is None else ldx, _p(e, torch.int32), _stream(),
+              label="split2h", nbytes=8 * M * C)
+
+
+def conv3x_wprep_f16x2(W, Wz, N, Ci, e):
+    _lib.call("rpb_conv3x_wprep_f16x2", _p(W), _p(Wz, torch.int16), N, Ci, _p(e, torch.int32), _stream(), label="conv3x_wprep_f16x2",
+              nbytes=8 * N * 27 * Ci)
+
+
+def conv3x_f16x2(planes, Wz, out, M, N, Ci, mesh, ea, ew, bias=None, ldo=None):
+    """out[M][ldo] = Conv3d(Ci, N, 3, padding=1)(tokens) + bias on the fp16 MFMA from two-plane operands scaled by 2^ea / 2^ew."""
+    hc, wc, dc = mesh
+    _lib.call("rpb_conv3x_f16x2", _p(planes, torch.int16), _p(Wz, torch.int16), _p(bias), _p(out), M, N, Ci, N if ldo is None else ldo,
+              hc, wc, dc, _p(ea, torch.int32), _p(ew, torch.int32), _stream(),
+              label=f"conv3x_f16x2[N{N},Ci{Ci}]", nbytes=4 * M * Ci * 9 + 4 * M * N, flops=2 * M * N * 27 * Ci)
+
+
 def split3t(x, planes_t, M, C, ldx=None, rev_mesh=None):
     """planes_t[3][M/8][C][8] (bf16 bit patterns): hi / mid / lo terms of x[M][ldx] in runs of 8 tokens per channel;
     ``rev_mesh=(d0, d1, d2)``: in the token order of the reversed mesh (d2, d1, d0)."""
@@ -784,13 +809,36 @@ def conv3_split_ok(N, Ci):
     return CONV3_SPLIT and Ci % 64 == 0 and (N in (64, 128) or N % 256 == 0)
 
 
-def conv3(x, W, out, M, N, Ci, mesh, bias=None, ldx=None):
+def conv3_f16x2_weights(W, N, Ci):
+    """(Wz, ew): W[N][27*Ci] as two scaled fp16 planes in MFMA operand order and their exponent (int32 [1] on the device) -- what
+    ``conv3(..., arith="f16x2", wh=...)`` takes; callers that run the same weights repeatedly cache it."""
+    ew = torch.empty(1, dtype=torch.int32, device=W.device)
+    wz = torch.empty(2 * N * 27 * Ci, dtype=torch.int16, device=W.device)
+    amax_exp(W, ew, N, 27 * Ci)
+    conv3x_wprep_f16x2(W, wz, N, Ci, ew)
+    return wz, ew
+
+
+def conv3(x, W, out, M, N, Ci, mesh, bias=None, ldx=None, arith="f32", wh=None):
     """out[M][N] = Conv3d(Ci, N, 3, padding=1)(x tokens [M][ldx]) + bias with W[N][27*Ci] (tap-major rows) -- forward, or the
     data gradient when W holds the flipped / transposed taps.  Shapes the split-bf16 kernel covers (Ci % 64 == 0, N = 64, 128
     or 256 k) run on the bf16 MFMA from hi + mid + lo operands (csrc/rpb_conv3x.hip: fp32-grade accuracy, ~2x the fp32 MFMA
-    rate); everything else, or RPB_CONV3_EXACT=1, takes the exact-fp32 implicit GEMM (rpb_gemm_nt conv mode 1)."""
+    rate); everything else, or RPB_CONV3_EXACT=1, takes the exact-fp32 implicit GEMM (rpb_gemm_nt conv mode 1).
+    ``arith="f16x2"`` (evaluation forwards only): the same shapes run on the fp16 MFMA from two-plane operands, three products per
+    fp32 product (csrc/rpb_conv3h.hip; dropped term <= 2^-22 |a b|); ``wh`` = ``conv3_f16x2_weights(W, N, Ci)`` prepared earlier.
+    Shapes outside the split kernels, or RPB_CONV3_EXACT=1, take the exact-fp32 path whatever ``arith`` says."""
+    if arith not in ("f32", "f16x2"):
+        raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
     if not conv3_split_ok(N, Ci):
         return gemm_nt(x, W, out, M, N, 27 * Ci, bias=bias, conv=mesh, lda=ldx)
+    if arith == "f16x2":
+        ea = torch.empty(1, dtype=torch.int32, device=out.device)
+        planes = torch.empty(2 * M * Ci, dtype=torch.int16, device=out.device)
+        amax_exp(x, ea, M, Ci, ldx)
+        split2h(x, planes, M, Ci, ea, ldx)
+        wz, ew = wh if wh is not None else conv3_f16x2_weights(W, N, Ci)
+        conv3x_f16x2(planes, wz, out, M, N, Ci, mesh, ea, ew, bias=bias)
+        return
     planes = torch.empty(3 * M * Ci, dtype=torch.int16, device=out.device)
     wz = torch.empty(3 * N * 27 * Ci, dtype=torch.int16, device=out.device)
     split3(x, planes, M, Ci, ldx)

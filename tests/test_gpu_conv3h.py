@@ -1,0 +1,257 @@
+"""The opt-in f16x2 arithmetic of the 3x3x3 convolutions (csrc/rpb_conv3h.hip; Transolver.set_arith / Unet3d.set_arith): operands as
+two fp16 planes of the tensor scaled by a per-tensor power of two, three products per fp32 product (dropped term <= 2^-22 |a b|).
+Kernels against fp64 PyTorch, the models' eval forwards against the default path and the CPU oracles, training untouched."""
+import copy
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import rel_l2
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from realpdebench_amd import ops as o
+    return o
+
+
+def _exp(ops, x, M, C):
+    e = torch.full((1,), 12345, dtype=torch.int32, device="cuda")
+    ops.amax_exp(x, e, M, C)
+    return e
+
+
+def test_split2h_reconstructs_and_exponent_range(ops):
+    torch.manual_seed(0)
+    M, C = 1000, 64
+    for scale in (1e-30, 1e-6, 1.0, 3e5, 1e30):
+        x = (torch.randn(M, C, device="cuda") * torch.logspace(-3, 3, C, device="cuda") * scale).contiguous()
+        e = _exp(ops, x, M, C)
+        ei = int(e.item())
+        mx = float(x.abs().max().double()) * 2.0 ** ei
+        assert 2.0 ** 14 <= mx < 2.0 ** 15, (scale, ei, mx)
+        planes = torch.empty(2 * M * C, dtype=torch.int16, device="cuda")
+        ops.split2h(x, planes, M, C, e)
+        p = planes.view(2, M, C).view(torch.float16).double().cpu()
+        xs = x.double().cpu() * 2.0 ** ei
+        big = xs.abs() >= 2.0 ** -16 * xs.abs().max()
+        err = ((p[0] + p[1] - xs).abs() / xs.abs().clamp_min(1e-300))[big].max()
+        assert float(err) <= 2.0 ** -23, (scale, float(err))
+    z = torch.zeros(64, 64, device="cuda")
+    assert int(_exp(ops, z, 64, 64).item()) == 0
+    # fp32 subnormal maximum, and every power-of-two / just-below boundary of the exponent choice
+    for v in (2.0 ** -140, 3.0 * 2.0 ** -130, 2.0 ** -87, 2.0 ** -88 * (2 - 2 ** -23), 1.0, 2.0 ** 100):
+        z[3, 5] = -v
+        assert 2.0 ** 14 <= v * 2.0 ** int(_exp(ops, z, 64, 64).item()) < 2.0 ** 15, v
+    # strided rows (ldx > C): only the C used columns count
+    xw = torch.randn(50, 128, device="cuda")
+    xw[:, 64:] = 1e6
+    e = torch.empty(1, dtype=torch.int32, device="cuda")
+    ops.amax_exp(xw, e, 50, 64, ldx=128)
+    assert 2.0 ** 14 <= float(xw[:, :64].abs().max()) * 2.0 ** int(e.item()) < 2.0 ** 15
+
+
+def _conv_ref(x, w, bias, B, mesh, Ci, Co):
+    T, H, W = mesh
+    M = B * T * H * W
+    xr = x.view(B, T, H, W, Ci).permute(0, 4, 1, 2, 3).double().cpu()
+    wr = w.view(Co, 3, 3, 3, Ci).permute(0, 4, 1, 2, 3).double().cpu()
+    return F.conv3d(xr, wr, bias.double().cpu(), padding=1).permute(0, 2, 3, 4, 1).reshape(M, Co)
+
+
+def _conv_case(ops, B, mesh, Ci, Co, xs=1.0, ws=None, seed=0):
+    T, H, W = mesh
+    M = B * T * H * W
+    torch.manual_seed(seed + Ci + Co)
+    x = torch.randn(M, Ci, device="cuda") * xs
+    w = torch.randn(Co, 27 * Ci, device="cuda") * (ws if ws is not None else 1.0 / (27 * Ci) ** 0.5)
+    bias = torch.randn(Co, device="cuda") * (xs * (ws if ws is not None else 1.0))
+    return M, x, w, bias
+
+
+@pytest.mark.parametrize("B,mesh,Ci,Co", [(2, (3, 5, 7), 64, 64), (1, (4, 6, 40), 128, 128), (1, (2, 9, 33), 64, 256),
+                                          (1, (5, 4, 13), 192, 512), (3, (2, 2, 2), 64, 64), (1, (3, 6, 20), 256, 512)])
+def test_conv3x_f16x2_forward_vs_fp64(ops, B, mesh, Ci, Co):
+    M, x, w, bias = _conv_case(ops, B, mesh, Ci, Co)
+    assert ops.conv3_split_ok(Co, Ci)
+    y = torch.full((M, Co), float("nan"), device="cuda")
+    ops.conv3(x, w, y, M, Co, Ci, mesh, bias=bias, arith="f16x2")
+    ref = _conv_ref(x, w, bias, B, mesh, Ci, Co)
+    assert rel_l2(y.cpu(), ref) < 2e-6
+    # the same through prepared weights, and different bits from the default kernel (the switch is live)
+    y2 = torch.full((M, Co), float("nan"), device="cuda")
+    ops.conv3(x, w, y2, M, Co, Ci, mesh, bias=bias, arith="f16x2", wh=ops.conv3_f16x2_weights(w, Co, Ci))
+    assert torch.equal(y, y2)
+    y0 = torch.full((M, Co), float("nan"), device="cuda")
+    ops.conv3(x, w, y0, M, Co, Ci, mesh, bias=bias)
+    assert not torch.equal(y, y0)
+
+
+@pytest.mark.parametrize("xs,ws", [(2.0 ** -10, None), (2.0 ** 10, None), (1.0, 1e-3), (2.0 ** -10, 1e-3)])
+def test_conv3x_f16x2_range(ops, xs, ws):
+    """Activations scaled by 2^-10 / 2^+10 and weights around 1e-3 meet the same bound: the per-tensor exponents do their job."""
+    B, mesh, Ci, Co = 1, (4, 6, 40), 128, 128
+    M, x, w, bias = _conv_case(ops, B, mesh, Ci, Co, xs=xs, ws=ws, seed=7)
+    y = torch.empty(M, Co, device="cuda")
+    ops.conv3(x, w, y, M, Co, Ci, mesh, bias=bias, arith="f16x2")
+    assert rel_l2(y.cpu(), _conv_ref(x, w, bias, B, mesh, Ci, Co)) < 2e-6
+
+
+def test_conv3x_f16x2_non_finite_propagates(ops):
+    B, mesh, Ci, Co = 1, (3, 5, 16), 64, 64
+    M, x, w, bias = _conv_case(ops, B, mesh, Ci, Co, seed=3)
+    x[17, 5] = float("inf")
+    y = torch.zeros(M, Co, device="cuda")
+    ops.conv3(x, w, y, M, Co, Ci, mesh, bias=bias, arith="f16x2")
+    torch.cuda.synchronize()
+    assert not bool(torch.isfinite(y[17]).all())
+
+
+def _transolver(n_hidden=64, heads=2, seed=4, H=10, W=6, D=5, drop=0.0):
+    from realpdebench_amd.model.transolver import Transolver
+    torch.manual_seed(seed)
+    m = Transolver(space_dim=3, n_layers=2, n_hidden=n_hidden, n_head=heads, fun_dim=0, out_dim=3, slice_num=16, mlp_ratio=2,
+                   H=H, W=W, D=D, dropout=drop)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if n.endswith("bias") or "ln_" in n:
+                p.add_(0.1 * torch.randn_like(p))
+    return m
+
+
+def _unet(seed=3, T=2, H=64, C=3):
+    from realpdebench_amd.model.unet import Unet3d
+    torch.manual_seed(seed)
+    m = Unet3d(dim=H, out_channels=C, dim_mults=[1, 2, 4], channels=C, in_time=T, out_time=T)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if n.endswith("bias") or n.endswith("gamma") or "norm" in n:
+                p.add_(0.1 * torch.randn_like(p))
+    return m
+
+
+def test_transolver_eval_forward_f16x2():
+    from oracle import transolver_oracle as TO
+    H, W, D = 10, 6, 5
+    m = _transolver(H=H, W=W, D=D).eval()
+    fresh = copy.deepcopy(m).cuda().eval()
+    x = torch.randn(2, D, W, H, 3)
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    ref = TO.transolver_forward(sd, x, 2, 2, H, W, D)
+    m = m.cuda()
+    assert m.arith == "f32"
+    with torch.no_grad():
+        y0 = m(x.cuda())
+        assert m.set_arith("f16x2") is m
+        y1 = m(x.cuda())
+        m.set_arith("f32")
+        y2 = m(x.cuda())
+        yf = fresh(x.cuda())
+    assert not torch.equal(y0, y1)
+    assert rel_l2(y1.cpu(), y0.cpu()) < 5e-6
+    assert rel_l2(y1.cpu(), ref) < 1e-5
+    assert torch.equal(y2, yf) and torch.equal(y0, yf)
+
+
+def test_unet_eval_forward_f16x2():
+    from oracle import unet_oracle as UO
+    m = _unet().cuda().eval()
+    x = torch.randn(2, 2, 64, 16, 3)
+    with torch.no_grad():
+        y0 = m(x.cuda())
+        y1 = m.set_arith("f16x2")(x.cuda())
+        y1b = m(x.cuda())                                 # second call: cached weight planes
+    ref = UO.unet_forward({k: v.detach().cpu() for k, v in m.state_dict().items()}, x)
+    assert not torch.equal(y0, y1)
+    assert torch.equal(y1, y1b)
+    assert rel_l2(y1.cpu(), y0.cpu()) < 5e-6
+    assert rel_l2(y1.cpu(), ref) < 2e-5
+    # an in-place weight update invalidates the cached planes
+    with torch.no_grad():
+        m.p("downs.0.0.block1.proj.weight").mul_(0.5)
+        y2 = m(x.cuda())
+        m.set_arith("f32")
+        y3 = m(x.cuda())
+    assert rel_l2(y2.cpu(), y3.cpu()) < 5e-6
+
+
+@pytest.mark.parametrize("which", ["transolver", "unet"])
+def test_training_is_unaffected(which):
+    """Under set_arith("f16x2") a train_loss + backward gives the default's loss and every gradient bit for bit."""
+    torch.manual_seed(11)
+    if which == "transolver":
+        base = _transolver(seed=6)
+        x, y = torch.randn(2, 5, 6, 10, 3), torch.randn(2, 5, 6, 10, 3)
+    else:
+        base = _unet(seed=5)
+        x, y = torch.randn(2, 2, 64, 16, 3), torch.randn(2, 2, 64, 16, 3)
+    res = []
+    for arith in ("f32", "f16x2"):
+        m = copy.deepcopy(base).cuda().train()
+        m.set_arith(arith)
+        loss = m.train_loss(x.cuda(), y.cuda()).mean()
+        loss.backward()
+        res.append((loss.detach().cpu(), {n: p.grad.detach().cpu() for n, p in m.named_parameters() if p.grad is not None}))
+    (l0, g0), (l1, g1) = res
+    assert torch.equal(l0, l1)
+    assert set(g0) == set(g1) and len(g0) > 10
+    for n in g0:
+        assert torch.equal(g0[n], g1[n]), n
+
+
+@pytest.mark.parametrize("which", ["transolver", "unet"])
+def test_rollout_f16x2(which):
+    from realpdebench_amd.rollout import autoregressive_rollout
+    torch.manual_seed(13)
+    if which == "transolver":
+        m = _transolver(seed=8).cuda()
+        x = torch.randn(2, 5, 6, 10, 3, device="cuda")
+    else:
+        m = _unet(seed=8).cuda()
+        x = torch.randn(2, 2, 64, 16, 3, device="cuda")
+    r0 = autoregressive_rollout(m.set_arith("f32"), x, 3)
+    r1 = autoregressive_rollout(m.set_arith("f16x2"), x, 3)
+    assert not torch.equal(r0, r1)
+    assert rel_l2(r1.cpu(), r0.cpu()) < 2e-5
+
+
+def test_eval_entrypoint_takes_eval_arith_transolver(tmp_path):
+    """`python -m realpdebench_amd.eval` with `eval_arith: f16x2` on a small synthetic Transolver YAML: the metrics agree with the
+    default arithmetic's to 1e-4 relative."""
+    import glob
+    import os
+    import yaml
+    from realpdebench_amd import eval as ev
+    from realpdebench_amd import train as tr
+    cfg = dict(exp_name="t", gpu=0, seed=0, results_path=str(tmp_path), dataset_name="synthetic", dataset_root="",
+               num_workers=0, normalizer="none", shape_in=[4, 6, 10, 3], shape_out=[4, 6, 10, 3], n_train=8, n_val=4,
+               model_name="transolver", checkpoint_path="", space_dim=3, n_layers=1, n_hidden=64, n_head=2, H=10, W=6, D=4,
+               fun_dim=0, out_dim=3, ref=4, dropout=0.0, act="gelu", mlp_ratio=2, slice_num=16, is_use_tb=None,
+               scheduler="cosine", step_size=10, num_update=100, train_batch_size=4, test_batch_size=4, lr=1e-3,
+               clip_grad_norm=0.0, N_autoregressive=1)
+    path = tmp_path / "trainsolver.yaml"
+    path.write_text(yaml.safe_dump(cfg))
+    exp = tr.main(["--config", str(path), "--max_updates", "3"])
+    ck = sorted(glob.glob(os.path.join(exp, "model_*.pth")))[-1]
+    base = ev.main(["--config", str(path), "--checkpoint_path", ck])
+    path2 = tmp_path / "trainsolver_f16x2.yaml"
+    path2.write_text(yaml.safe_dump(dict(cfg, eval_arith="f16x2")))
+    fast = ev.main(["--config", str(path2), "--checkpoint_path", ck])
+    assert set(base) == set(fast)
+    n = 0
+    for k in base:
+        if not isinstance(base[k], (int, float)):
+            assert base[k] == fast[k]
+            continue
+        a, b = float(base[k]), float(fast[k])
+        if a == a and b == b:
+            assert abs(a - b) <= 1e-4 * max(abs(a), 1e-12), (k, a, b)
+            n += 1
+    assert n >= 5
+    path3 = tmp_path / "bad.yaml"
+    path3.write_text(yaml.safe_dump(dict(cfg, eval_arith="fp8")))
+    with pytest.raises(ValueError):
+        ev.main(["--config", str(path3), "--checkpoint_path", ck])
