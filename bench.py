@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X FNO3d path (contract: see the task statement / DESIGN.md).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
 
 N>1: either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (WORLD_SIZE set: this
 process is one rank) or started plainly as ``python bench.py --gpus N``: it then re-executes itself under
@@ -10,8 +10,11 @@ torch.distributed.run with N ranks on 127.0.0.1, one per GPU over RCCL, and the 
 One "step" = one full training iteration of the reference's hot loop (train.py:321-334: forward, MSE mean,
 backward, Adam, cosine LR) on a synthetic batch of BASELINE.json configs[1]: FNO3d cylinder-shaped
 [B=32/GPU, 20, 128, 128, 2], modes (4,12,16), width 64, 4 layers, fp32.  Inputs are resident in HBM when the
-timed region starts.  Rank 0 prints ONE JSON line with the whole-job samples/s, the roofline of the dominant
-kernel (HIP-event timed inside the timed region) and a CPU baseline (the oracle timed on the host cores).
+timed region starts.  Rank 0 prints ONE JSON line with the whole-job samples/s and the roofline of the dominant
+kernel (HIP-event timed inside the timed region).  A plain run does nothing else: it sets up, warms up, times the K steps,
+writes --dump-outputs and prints the line.  ``--full`` adds what takes runs of its own: the parity checks against the
+reference fixtures, the rollout, the live PMC traffic and chip ceilings, the scaling proxy, the secondary models and
+configurations, and a CPU baseline (the oracle timed on the host cores); the ``--no-*`` options leave parts of it out.
 That line is the compact form of the result record (scalars and short labels); ``--record FILE`` writes the whole record.
 ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (see ``dump_outputs``): the inputs are
 seeded, so two builds run with the same arguments can be compared output for output.
@@ -32,7 +35,7 @@ MFMA_F32_PEAK_TF = 157.3     # fp32-input MFMA = fp32 vector peak
 MFMA_BF16_PEAK_TF = 2500.0   # dense bf16 MFMA (MI355X_MICROARCH.md)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -54,7 +57,12 @@ def parse():
     ap.add_argument("--no-bf16", action="store_true", help="skip the bf16-storage FNO rollout (BASELINE.json configs[4])")
     ap.add_argument("--no-pmc", action="store_true", help="take roofline.traffic from profiles/traffic_per_launch.json instead of measuring it "
                     "now (default at N=1: two rocprofv3 --pmc request-size passes over tools/kbench.py cell_mix, --kernel-trace only, ~40 s)")
-    ap.add_argument("--only-headline", action="store_true", help="the FNO train step only: no rollout, secondary models, PMC passes or CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: loss / gradient checks against the reference fixtures, rollouts, live PMC traffic, "
+                         "copy / MFMA ceilings, N > 1 collective timing, scaling proxy, secondary models and CPU baseline (the --no-* "
+                         "options and --only-headline select within it); without it a run only sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--only-headline", action="store_true", help="with --full: the FNO train step only: no rollout, secondary models, PMC passes or CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (loss, updated parameters, parameter gradients; "
                          "large tensors as a fixed seeded sample) as DIR/<name>.npy, float32, <= 64 MB in all")
@@ -62,10 +70,10 @@ def parse():
                     help="write the full result record (every nested table and note) as JSON to FILE; stdout carries its compact form")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--proxy-worker", type=float, default=None, help=argparse.SUPPRESS)     # child process of the scaling proxy: ms of the B = 32 step
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be >= 1")
-    if a.only_headline:
+    if a.only_headline or not a.full:
         a.no_cpu_baseline = a.no_rollout = a.no_transolver = a.no_galerkin = a.no_dpot = a.no_unet = a.no_bf16 = a.no_pmc = True
         a.no_scaling_proxy = True
         a.no_fno_native = True
@@ -935,10 +943,10 @@ def main():
             print(f"family {k:40s} {100 * v['total_ms'] / tot:5.1f}%  {v['total_ms'] / max(a.warmup, 1):7.2f} ms/step  "
                   f"{v['bytes'] / v['total_ms'] / 1e6:8.1f} GB/s", file=sys.stderr)
 
-    # ---- parity guard on the timed workload itself: the first-step loss of this exact batch / these exact weights must be
+    # ---- parity guard on the timed workload itself (--full): the first-step loss of this exact batch / these exact weights must be
     #      the one the IMPORTED reference computed for them (tests/golden/make_golden_headline.py)
     loss_check = None
-    if world == 1 and B == 32 and rank == 0:
+    if a.full and world == 1 and B == 32 and rank == 0:
         import numpy as np
         gz = np.load(os.path.join(ROOT, "tests", "golden", "fno3d_headline.npz"))
         ref = float(gz["b32/loss"])
@@ -972,7 +980,7 @@ def main():
         dumped = {"dir": a.dump_outputs, "arrays": len(dump_outputs(a.dump_outputs, loss, model, trainer.grad))}
 
     # ---- N > 1: one more step with the collective instrumented (per-bucket schedule on the side stream, how long Adam waited for the
-    #      last bucket, cost of the inline SyncBN reductions) -- outside the timed region
+    #      last bucket, cost of the inline SyncBN reductions) -- outside the timed region, with --full (a plain run describes the setup only)
     dp_info = None
     if (world > 1 or force_dp) and model.dp is not None:
         comm = getattr(model.dp, "comm", None)
@@ -984,7 +992,7 @@ def main():
                                           if getattr(model.dp, "p2p_opt", False) else
                                           ("reduce-scatter + Adam on owned ranges + all-gather" if getattr(model.dp, "shard_opt", False)
                                            else "all-reduce buckets + full-arena Adam"))}
-        if comm is not None:
+        if comm is not None and a.full:
             comm.set_timing(True)
             trainer.step(x, y)
             torch.cuda.synchronize()
@@ -997,9 +1005,9 @@ def main():
                 dp_info["timing_error"] = repr(e)
             comm.set_timing(False)
 
-    # ---- the chip's streaming ceiling for the kernels' read / write mixes, measured now (rank 0)
+    # ---- the chip's streaming ceiling for the kernels' read / write mixes, measured now (rank 0, --full)
     ceiling = mfma_peak = None
-    if rank == 0 and B * world >= 1:
+    if a.full and rank == 0:
         try:
             free_b = torch.cuda.mem_get_info()[0]
             if free_b > 20e9:
@@ -1076,7 +1084,7 @@ def main():
     #      kernels, against what the IMPORTED reference produced for the same seeded weights and batch -- the Frobenius norm and 256 sampled
     #      entries of EVERY parameter gradient (tests/golden/fno3d_headline.npz, b2/*; tests/test_gpu_headline.py holds the same check)
     grad_check = None
-    if world == 1 and rank == 0 and not a.only_headline:
+    if a.full and world == 1 and rank == 0 and not a.only_headline:
         try:
             import numpy as np
             sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))

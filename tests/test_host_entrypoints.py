@@ -156,6 +156,23 @@ def test_bench_pmc_csv_to_family_traffic(tmp_path):
     assert fam == pytest.approx((3 * f_bytes + (8 * 32 + 4 * 64) + 3 * (20 * 128 + 6 * 64)) / 7)
 
 
+def test_bench_plain_run_leaves_every_extra_to_full():
+    """A plain ``bench.py`` run measures the headline only; ``--full`` turns every other part back on, and the ``--no-*`` options and
+    ``--only-headline`` still select within it."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    parts = ("no_cpu_baseline", "no_rollout", "no_transolver", "no_galerkin", "no_dpot", "no_unet", "no_bf16", "no_pmc",
+             "no_scaling_proxy", "no_fno_native")
+    plain = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and all(getattr(plain, p) for p in parts)
+    full = bench.parse(["--full"])
+    assert full.full and not any(getattr(full, p) for p in parts)
+    some = bench.parse(["--full", "--no-unet", "--no-cpu-baseline"])
+    assert some.no_unet and some.no_cpu_baseline and not some.no_rollout and not some.no_transolver
+    assert all(getattr(bench.parse(["--full", "--only-headline"]), p) for p in parts)
+
+
 def test_shipped_yamls_carry_the_references_values():
     """Every YAML under realpdebench_amd/configs/<scenario>/ for the four north-star models has the reference's key set and values
     (tests/golden/reference_configs.json: yaml.safe_load of realpdebench/configs/**, written by make_golden_configs.py), except the

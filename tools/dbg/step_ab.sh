@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/dbg/step_ab.sh "base nopk2 ..." : FNO step + rollout of each library variant, alternating twice; prints ms_per_step and the rollout ms per forward
-FNO="--no-pmc --no-bf16 --no-transolver --no-galerkin --no-unet --no-dpot --no-cpu-baseline --no-fno-native --no-scaling-proxy"
+FNO="--full --no-pmc --no-bf16 --no-transolver --no-galerkin --no-unet --no-dpot --no-cpu-baseline --no-fno-native --no-scaling-proxy"
 for rep in 1 2; do
 for v in $1; do
   if [ $v = base ]; then unset RPB_LIB_PATH; else export RPB_LIB_PATH=$PWD/tools/dbg/librpb_$v.so; fi

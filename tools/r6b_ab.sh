@@ -10,7 +10,7 @@ build() {
   for f in $files; do touch realpdebench_amd/csrc/$f; done
   RPB_HIPCC_FLAGS="$*" python realpdebench_amd/build.py > /dev/null 2>&1 || echo "BUILD FAILED: $*"
 }
-step() { python bench.py --only-headline --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('   step %.3f ms  loss_check %s' % (d['ms_per_step'], d.get('loss_check', {}).get('rel_err')))"; }
+step() { python bench.py --full --only-headline --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('   step %.3f ms  loss_check %s' % (d['ms_per_step'], d.get('loss_check', {}).get('rel_err')))"; }
 wg() { python tools/kbench.py cell_mix 2>/dev/null | grep -E "conv wgrad" | sed "s/^/   /"; }
 for rep in 1 2; do
   echo "== WG gelu: erf + two exponentials (CMX_WG_GELU_AS=0), rep $rep"; build "rpb_cmx.hip" -DCMX_WG_GELU_AS=0; wg; step

@@ -7,7 +7,7 @@ build() {
   for f in $FILES; do touch realpdebench_amd/csrc/$f; done
   RPB_HIPCC_FLAGS="$*" python realpdebench_amd/build.py > /dev/null 2>&1 || echo "BUILD FAILED: $*"
 }
-step() { python bench.py --only-headline --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('   step %.3f ms  loss_check %s first_step_loss %.10f' % (d['ms_per_step'], d.get('loss_check', {}).get('rel_err'), d.get('first_step_loss', 0)))"; }
+step() { python bench.py --full --only-headline --steps 10 --warmup 3 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('   step %.3f ms  loss_check %s first_step_loss %.10f' % (d['ms_per_step'], d.get('loss_check', {}).get('rel_err'), d.get('first_step_loss', 0)))"; }
 probe() {
   python tools/kbench.py cell_mix axis bwd_row proj mode 2>/dev/null | grep -E "conv wgrad|lazy|layer 0|step's|head_fwd_bwd|K268|K48|mode_contract" | sed "s/^/   /"
   step
