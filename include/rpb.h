@@ -35,8 +35,10 @@ extern "C" {
  *      round 5: rpb_dp_reduce_scatter_enqueue / rpb_dp_allgather_enqueue / rpb_dp_mark / rpb_dp_wait_mark / rpb_dp_set_model /
  *      rpb_adam_step_ranges added (additions only);
  *      round 6: rpb_dp_p2p_*, rpb_cell_mix_eval_dft_f16x2, rpb_cell_mix_eval_crop_f16x2, rpb_proj_fwd_f16x2 added (additions only);
- *      rpb_amax_exp, rpb_split2h, rpb_conv3x_wprep_f16x2, rpb_conv3x_f16x2 added (additions only) */
-#define RPB_ABI_VERSION 2
+ *      rpb_amax_exp, rpb_split2h, rpb_conv3x_wprep_f16x2, rpb_conv3x_f16x2 added (additions only)
+ *   3  rpb_proj_wgrad, rpb_proj_wgrad_slots, rpb_proj_wgrad_row, rpb_proj_wgrad_roles removed; rpb_proj_dgrad reads gh from `gu` only
+ *      and lost its b1, w2, gout and act arguments */
+#define RPB_ABI_VERSION 3
 const char* rpb_last_error(void);
 int rpb_abi_version(void);
 /* bf16 activation STORAGE (BASELINE.json configs[4]; the opt-in rollout path): how many bf16 planes of the fp32 constants (conv / fc1 weights,
@@ -438,27 +440,16 @@ int rpb_bn_bwd_row_c128(const float* s, const float* gy, float* gs, const float*
                         const float* beta, const float* sums, double count, int gelu, const float* GWt, float* Y1, float* part,
                         int G, int Wp, int K2, void* stream);
 
-/* ---- backward of the projection head without the gu round trips (fno.py:121-125 autograd; C = 64, DO <= 4, W >= 16):
- *      gh = (fc2^T gout) * act'(fc1 a + b1) is recomputed on the bf16 matrix pipe by each consumer instead of being written once
- *      ([ncrop][128] fp32) and read twice.  `s` is the PADDED pre-BatchNorm tensor of the last Fourier layer, a = xf(s) on the
- *      cropped cells (xf_* = that layer's mean, invstd, gamma, beta, gelu flag); act 0 = exact GELU, 1 = SiLU.
- *      rpb_proj_dgrad: g [ncell][64] = gradient w.r.t. the layer output in the padded layout (zeros in the margin) and
- *        (gu != NULL: gh is READ from gu [ncrop][128] as written by rpb_proj_bwd instead of recomputed -- the faster choice, see
- *        csrc/rpb_pjx.hip -- and gout may be NULL)
- *        stats_part [rpb_proj_dgrad_slots][2][64] = partial (sum g, sum g * shat), shat = (s - mean) * invstd.
- *      rpb_proj_wgrad: part [rpb_proj_wgrad_slots][rpb_proj_wgrad_row(DO)], row `slot` = partial sums for the HB = 128 / roles hidden
- *        units [HB * (slot % roles), + HB): [HB*64] d fc1.weight | [DO*HB] d fc2.weight | [HB] d fc1.bias | [DO] d fc2.bias. */
+/* ---- fc1 data gradient of the projection head on the bf16 matrix pipe (fno.py:121-125 autograd; C = 64, DO <= 4, W >= 16):
+ *      `s` is the PADDED pre-BatchNorm tensor of the last Fourier layer (xf_* = that layer's mean, invstd, gamma, beta, gelu flag), gu
+ *      [ncrop][128] = gh as written by rpb_proj_bwd.
+ *      rpb_proj_dgrad: g [ncell][64] = fc1^T gh, the gradient w.r.t. the layer output in the padded layout (zeros in the margin), and
+ *        stats_part [rpb_proj_dgrad_slots][2][64] = partial (sum g, sum g * shat), shat = (s - mean) * invstd. */
 int rpb_proj_bwd_fused_supported(int C, int DO, int W, int Wp);
 long rpb_proj_dgrad_slots(int B, int Tp, int Hp);
-int rpb_proj_dgrad(const float* s, const float* w1, const float* b1, const float* w2, const float* gout, const float* gu,
-                   float* g, float* stats_part, int B, int DO, int T, int H, int W, int Tp, int Hp, int Wp, const float* xf_mean,
-                   const float* xf_invstd, const float* xf_gamma, const float* xf_beta, int xf_gelu, int act, void* stream);
-long rpb_proj_wgrad_slots(int B, int T, int H);
-int rpb_proj_wgrad_row(int DO);
-int rpb_proj_wgrad_roles(void);
-int rpb_proj_wgrad(const float* s, const float* w1, const float* b1, const float* w2, const float* gout, float* part, int B,
-                   int DO, int T, int H, int W, int Tp, int Hp, int Wp, const float* xf_mean, const float* xf_invstd,
-                   const float* xf_gamma, const float* xf_beta, int xf_gelu, int act, void* stream);
+int rpb_proj_dgrad(const float* s, const float* w1, const float* gu, float* g, float* stats_part, int B, int DO, int T, int H, int W,
+                   int Tp, int Hp, int Wp, const float* xf_mean, const float* xf_invstd, const float* xf_gamma, const float* xf_beta,
+                   int xf_gelu, void* stream);
 
 /* ---- the whole backward of the projection head in ONE pass (round 3; fno.py:121-125 autograd + the BatchNorm-backward sums of the last
  *      Fourier layer, fno.py:117; C = 64, DO <= 4, exact-GELU head after a BatchNorm without GELU):  csrc/rpb_pjf.hip.

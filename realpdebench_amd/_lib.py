@@ -7,7 +7,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 2          # RPB_ABI_VERSION of include/rpb.h
+ABI_VERSION = 3          # RPB_ABI_VERSION of include/rpb.h
 LIB_PATH = os.environ.get("RPB_LIB_PATH") or os.path.join(_HERE, "csrc", "librpb_hip.so")     # RPB_LIB_PATH: an instrumented build (tools/dbg)
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -34,11 +34,7 @@ SIGNATURES = {
     "rpb_bn_bwd_row_feat": (_I, "ppppppppp" + "d" + "i" + "ppp" + "iiiii" + "p"),
     "rpb_proj_bwd_fused_supported": (_I, "iiii"),
     "rpb_proj_dgrad_slots": (_L, "iii"),
-    "rpb_proj_dgrad": (_I, "pppppppp" + "ii" + "iiiiii" + "ppppi" + "i" + "p"),
-    "rpb_proj_wgrad_slots": (_L, "iii"),
-    "rpb_proj_wgrad_row": (_I, "i"),
-    "rpb_proj_wgrad_roles": (_I, ""),
-    "rpb_proj_wgrad": (_I, "pppppp" + "ii" + "iiiiii" + "ppppi" + "i" + "p"),
+    "rpb_proj_dgrad": (_I, "ppppp" + "ii" + "iiiiii" + "ppppi" + "p"),
     "rpb_stream_probe": (_I, "pppp" + "l" + "ii" + "p"),
     "rpb_mfma_probe": (_I, "pp" + "ii" + "p" + "p"),
     "rpb_head_bwd_supported": (_I, "iiiiii"),

@@ -83,7 +83,7 @@ __device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
 //     combustion forward; the same change gained 11 % in rpb_cmx.hip's fused launch, profiles/r06b_ab5_waves_dft_sb.txt): 8 stays
 #ifndef AXG_WAVES_XF
 #define AXG_WAVES_XF 8      /* 12 (three waves per SIMD at 165 registers): the micro-benchmark gains 3-6 % (1.19-1.23 -> 1.16 ms), the train step loses
-                               0.1 ms (34.24 / 34.26 -> 34.34 / 34.40 ms, A/B twice, tools/r6b_ab7.sh): 8 stays */
+                               0.1 ms (34.24 / 34.26 -> 34.34 / 34.40 ms, A/B twice): 8 stays */
 #endif
 #ifndef AXG_WAVES_BFIN
 #define AXG_WAVES_BFIN 8

@@ -244,8 +244,7 @@ __global__ __launch_bounds__(512) void bwd_row_kernel(BwdRowArgs a) {
 }
 
 extern "C" long rpb_bn_bwd_row_slots(int G) {
-    static const int per_cu = getenv("RPB_BWD_ROW_WG_PER_CU") ? atoi(getenv("RPB_BWD_ROW_WG_PER_CU")) : 1;
-    long slots = (long)rpb_num_cus() * 8 * (per_cu > 0 ? per_cu : 1);
+    const long slots = (long)rpb_num_cus() * 8;
     const long need = ((long)G + 7) / 8 * 8;
     return slots < need ? slots : need;
 }
@@ -260,15 +259,15 @@ extern "C" int rpb_bn_bwd_row(const float* s, const float* gy, const float* x, f
     RPB_REQUIRE(C == 32 || C == 64, "bn_bwd_row: C=%d not supported by the fused kernel (use the unfused kernels)", C);
     // x == NULL: no weight gradient in this launch (rpb_cell_mix_wgrad of the same layer forms it): the C x C block of the partial
     // rows is left unwritten, only [C] sum gs follows it
-    RPB_REQUIRE(x || (rpb_bwr_supported(C, Wp, K2, 0) && !xf_mean), "bn_bwd_row: x == NULL needs the C = 64 bf16-pipe kernel and no input transform");
+    RPB_REQUIRE(x || (rpb_bwr_supported(C, Wp, K2) && !xf_mean), "bn_bwd_row: x == NULL needs the C = 64 bf16-pipe kernel and no input transform");
     RPB_REQUIRE(G > 0 && Wp > 0 && K2 > 0 && K2 <= 32 && count > 0, "bn_bwd_row: bad sizes G=%d Wp=%d K2=%d", G, Wp, K2);
     RPB_REQUIRE((long)Wp * C * 4 < (1L << 31), "bn_bwd_row: row too long");
     if (xf_mean) RPB_REQUIRE(xf_invstd && xf_gamma && xf_beta, "bn_bwd_row: bad input-transform arguments");
-    if (rpb_bwr_supported(C, Wp, K2, 0)) {               // C = 64: bf16 matrix pipe, B-layout loads (csrc/rpb_bwr.hip)
+    if (rpb_bwr_supported(C, Wp, K2)) {               // C = 64: bf16 matrix pipe, B-layout loads (csrc/rpb_bwr.hip)
         BwrArgs b;
         b.s = s; b.gy = gy; b.x = x; b.gs = gs; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta; b.sums = sums;
         b.inv_count = (float)(1.0 / count); b.gelu = gelu; b.xf = XForm{xf_mean, xf_invstd, xf_gamma, xf_beta, xf_gelu};
-        b.GW = GWt; b.Y1 = Y1; b.part = part; b.G = G; b.Wp = Wp; b.K2 = K2; b.FW = 0; b.CS = 64; b.coff = 0;
+        b.GW = GWt; b.Y1 = Y1; b.part = part; b.G = G; b.Wp = Wp; b.K2 = K2; b.CS = 64; b.coff = 0;
         return rpb_bwr_launch(b, rpb_bn_bwd_row_slots(G), (hipStream_t)stream);
     }
     BwdRowArgs a;
@@ -301,7 +300,7 @@ extern "C" int rpb_bn_bwd_row_c128(const float* s, const float* gy, float* gs, c
         b.s = s; b.gy = gy; b.x = nullptr; b.gs = gs;
         b.mean = mean + 64 * h; b.invstd = invstd + 64 * h; b.gamma = gamma + 64 * h; b.beta = beta + 64 * h; b.sums = sums + 64 * h;
         b.inv_count = (float)(1.0 / count); b.gelu = gelu; b.xf = XForm{nullptr, nullptr, nullptr, nullptr, 0};
-        b.GW = GWt; b.Y1 = Y1; b.part = part + h * rows * (64 * 64 + 64); b.G = G; b.Wp = Wp; b.K2 = K2; b.FW = 0; b.CS = 128; b.coff = 64 * h;
+        b.GW = GWt; b.Y1 = Y1; b.part = part + h * rows * (64 * 64 + 64); b.G = G; b.Wp = Wp; b.K2 = K2; b.CS = 128; b.coff = 64 * h;
         const int rc = rpb_bwr_launch(b, rows, (hipStream_t)stream);
         if (rc != RPB_OK) return rc;
     }
@@ -319,14 +318,7 @@ extern "C" int rpb_bn_bwd_row_feat(const float* s, const float* gy, const float*
     RPB_REQUIRE(s && gy && phi && mean && invstd && gamma && beta && sums && GWt && Y1 && part, "bn_bwd_row_feat: null pointer");
     RPB_REQUIRE(C == 64 && (FW == 8 || FW == 32), "bn_bwd_row_feat: C=%d FW=%d unsupported", C, FW);
     RPB_REQUIRE(G > 0 && Wp > 0 && K2 > 0 && K2 <= 32 && count > 0, "bn_bwd_row_feat: bad sizes G=%d Wp=%d K2=%d", G, Wp, K2);
-    // (measured at B = 32: the feature-field variant of the bf16-pipe kernel 2.72 ms, this fp32 kernel 2.47 ms -- scalar field loads; off unless asked for)
-    if (getenv("RPB_BWR_FEAT") && atoi(getenv("RPB_BWR_FEAT")) == 1 && rpb_bwr_supported(C, Wp, K2, FW)) {
-        BwrArgs b;
-        b.s = s; b.gy = gy; b.x = phi; b.gs = gs; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta; b.sums = sums;
-        b.inv_count = (float)(1.0 / count); b.gelu = gelu; b.xf = XForm{nullptr, nullptr, nullptr, nullptr, 0};
-        b.GW = GWt; b.Y1 = Y1; b.part = part; b.G = G; b.Wp = Wp; b.K2 = K2; b.FW = FW; b.CS = 64; b.coff = 0;
-        return rpb_bwr_launch(b, rpb_bn_bwd_row_slots(G), (hipStream_t)stream);
-    }
+    // (a feature-field variant of the bf16-pipe kernel measured slower at B = 32: 2.72 ms against 2.47 ms for this one -- scalar field loads)
     BwdRowArgs a;
     a.s = s; a.gy = gy; a.x = phi; a.gs = gs; a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta;
     a.sums = sums; a.inv_count = (float)(1.0 / count); a.gelu = gelu;

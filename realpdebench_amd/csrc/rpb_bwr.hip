@@ -64,12 +64,12 @@ __device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
     _Pragma("unroll") for (int c_ = 0; c_ < 4; ++c_) ACC(c_) = mfma16(AM(c_), BH(c_), ACC(c_)); \
     _Pragma("unroll") for (int c_ = 0; c_ < 4; ++c_) ACC(c_) = mfma16(AH(c_), BH(c_), ACC(c_));
 
-// GELU: gy is multiplied by gelu'(z) here (the producer did not store gz);  XGELU / XBN: the layer input is act(BN(x));  FEAT: x is the
-// feature tensor (layer 0): the weight-gradient columns are its FW <= 16 fields;  NOX: no weight gradient here (a.x == null: the
+// GELU: gy is multiplied by gelu'(z) here (the producer did not store gz);  XGELU / XBN: the layer input is act(BN(x));
+// NOX: no weight gradient here (a.x == null: the
 // backward cell_mix of the same layer forms it, csrc/rpb_cmx.hip WG) -- the layer input is not read at all: 12.4 instead of 16.2 GB
 // CS: floats per cell row (64; 128 = one 64-channel half of a width-128 layer per launch, NOX only: BwrArgs::CS / coff)
 // MT: 16-mode row tiles of Y1 (2: K2 <= 32; 3: K2 <= 48, the Galerkin regressor's modes (4, 16, 20) -> K2 = 40)
-template <bool GELU, bool XBN, bool XGELU, bool FEAT, bool NOX = false, int CS = 64, int MT = 2>
+template <bool GELU, bool XBN, bool XGELU, bool NOX = false, int CS = 64, int MT = 2>
 __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
     static_assert(CS == 64 || NOX, "width 128: the launch without the weight gradient");
     extern __shared__ u32x4 lds4[];                     // GW^T planes [q][plane 3][mt MT][lane]: A operand of Y1 = GW^T gs  (rows = mode 16 mt + n16)
@@ -110,13 +110,13 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
         xbe = *reinterpret_cast<const f32x4v*>(a.xf.beta + c0);
     }
     const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4v accW[4][(FEAT || NOX) ? 1 : 4];               // d conv weight: tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n16 <-> in channel 4 n16 + ui (FEAT: field n16)
+    f32x4v accW[4][NOX ? 1 : 4];                         // d conv weight: tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n16 <-> in channel 4 n16 + ui
     f32x4v accY[MT][4];                                   // Y1 of the current row: row 16 mt + 4 mg + r = mode, column n16 of tile u <-> channel 4 n16 + u
     f32x4v bsum = z4;
 #pragma unroll
     for (int uo = 0; uo < 4; ++uo)
 #pragma unroll
-        for (int ui = 0; ui < ((FEAT || NOX) ? 1 : 4); ++ui) accW[uo][ui] = z4;
+        for (int ui = 0; ui < (NOX ? 1 : 4); ++ui) accW[uo][ui] = z4;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -127,12 +127,10 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
     constexpr int CB = CS * 4;                           // width 128: rows of 512 B, this launch's 256 B half at byte 4 coff
     const int coff = CS == 64 ? 0 : a.coff;
     const unsigned row_bytes = (unsigned)Wp * (unsigned)CB - 4u * (unsigned)coff;
-    const int FW = a.FW;
 
     // one step = 32 cells of a row: cell (kg, e) = 32 q + 4 e + kg.  Loads of step k + 1 are issued before step k is computed.
     u32x4 sA[8], yA[8], xA[8], sB[8], yB[8], xB[8];
-    float fA[8], fB[8];                                  // FEAT: field n16 of the lane's 8 cells
-    auto issue = [&](long g, int q, u32x4 (&sv)[8], u32x4 (&yv)[8], u32x4 (&xv)[8], float (&fv)[8]) {
+    auto issue = [&](long g, int q, u32x4 (&sv)[8], u32x4 (&yv)[8], u32x4 (&xv)[8]) {
         const bool ok = g < a.G;
         const long off = (ok ? g : 0) * (long)Wp * CS + coff;
         const unsigned nb = ok ? row_bytes : 0u;         // past the wave's last row: an empty descriptor, the loads return 0 without traffic
@@ -143,19 +141,13 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
             sv[e] = ld16(rs, vo);
             yv[e] = ld16(ry, vo);
         }
-        if (NOX) {
-        } else if (FEAT) {
-            const rsrc_t rx = make_rsrc(a.x + (ok ? g : 0) * (long)Wp * FW, ok ? (unsigned)(Wp * FW) * 4u : 0u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                fv[e] = buf_load_f32(rx, n16 < FW ? ((32 * q + 4 * e + kg) * FW + n16) * 4 : 0x7ffffff0, 0);
-        } else {
+        if (!NOX) {
             const rsrc_t rx = make_rsrc(a.x + off, nb);
 #pragma unroll
             for (int e = 0; e < 8; ++e) xv[e] = ld16(rx, (32 * q + 4 * e + kg) * 256 + n16 * 16);
         }
     };
-    auto compute = [&](long g, int q, const u32x4 (&sv)[8], const u32x4 (&yv)[8], const u32x4 (&xv)[8], const float (&fv)[8]) {
+    auto compute = [&](long g, int q, const u32x4 (&sv)[8], const u32x4 (&yv)[8], const u32x4 (&xv)[8]) {
         const rsrc_t ro = make_rsrc(a.gs ? a.gs + g * (long)Wp * CS + coff : a.s, a.gs ? row_bytes : 0u);   // gs == NULL: stores dropped
         f32x4v gsv[8];
 #pragma unroll
@@ -200,26 +192,7 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
 #undef BW_B3
         }
         // ---- dWc[out][in] += gs^T x
-        if (NOX) {
-        } else if (FEAT) {
-            bf16x8 Xh, Xm, Xl;
-            split8(fv, Xh, Xm, Xl);
-#define BW_ACC(c) accW[c][0]
-#define BW_A1(c) Gh[c]
-#define BW_A2(c) Gm[c]
-#define BW_A3(c) Gl[c]
-#define BW_B1(c) Xh
-#define BW_B2(c) Xm
-#define BW_B3(c) Xl
-            BW_MAC6(BW_ACC, BW_A1, BW_A2, BW_A3, BW_B1, BW_B2, BW_B3)
-#undef BW_ACC
-#undef BW_A1
-#undef BW_A2
-#undef BW_A3
-#undef BW_B1
-#undef BW_B2
-#undef BW_B3
-        } else {
+        if (!NOX) {
             bf16x8 Xh[4], Xm[4], Xl[4];
             f32x4v xt[8];
 #pragma unroll
@@ -275,7 +248,7 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
 
     long g = slot;
     int q = 0;
-    if (g < a.G) issue(g, 0, sA, yA, xA, fA);
+    if (g < a.G) issue(g, 0, sA, yA, xA);
     while (g < a.G) {
         // next step of this wave: the same row's next 32 cells, or the first cells of its next row
         long gn = g;
@@ -285,8 +258,8 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
             gn = g + nslots;
         }
         asm volatile("" ::: "memory");
-        issue(gn, qn, sB, yB, xB, fB);
-        compute(g, q, sA, yA, xA, fA);
+        issue(gn, qn, sB, yB, xB);
+        compute(g, q, sA, yA, xA);
         g = gn;
         q = qn;
         if (g >= a.G) break;
@@ -297,26 +270,21 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
             gn = g + nslots;
         }
         asm volatile("" ::: "memory");
-        issue(gn, qn, sA, yA, xA, fA);
-        compute(g, q, sB, yB, xB, fB);
+        issue(gn, qn, sA, yA, xA);
+        compute(g, q, sB, yB, xB);
         g = gn;
         q = qn;
     }
 
-    // ---- the wave's partial row: [64 out][64 in] (FEAT: columns 0 .. FW-1), then [64] sum gs
+    // ---- the wave's partial row: [64 out][64 in], then [64] sum gs
     float* part = a.part + slot * (long)(64 * 64 + 64);
 #pragma unroll
     for (int uo = 0; uo < 4; ++uo)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int o = 4 * (4 * kg + r) + uo;
-            if (NOX) {
-            } else if (FEAT) {
-                if (n16 < FW) part[o * 64 + n16] = accW[uo][0][r];
-            } else {
-                *reinterpret_cast<f32x4v*>(part + o * 64 + 4 * n16) =
-                    f32x4v{accW[uo][0][r], accW[uo][FEAT ? 0 : 1][r], accW[uo][FEAT ? 0 : 2][r], accW[uo][FEAT ? 0 : 3][r]};
-            }
+            if (!NOX)
+                *reinterpret_cast<f32x4v*>(part + o * 64 + 4 * n16) = f32x4v{accW[uo][0][r], accW[uo][1][r], accW[uo][2][r], accW[uo][3][r]};
         }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -334,10 +302,10 @@ static bool bwr_off() {
 
 // K2 in 33 .. 48: three 16-mode row tiles, the width-128 half launches only (rpb_bwr_supported_c128)
 bool rpb_bwr_supported_c128(int Wp, int K2) {
-    return rpb_bwr_supported(64, Wp, K2 <= 32 ? K2 : 32, 0) && K2 >= 1 && K2 <= 48 && (size_t)((Wp + 31) / 32) * 9 * 1024 <= 150 * 1024;
+    return rpb_bwr_supported(64, Wp, K2 <= 32 ? K2 : 32) && K2 >= 1 && K2 <= 48 && (size_t)((Wp + 31) / 32) * 9 * 1024 <= 150 * 1024;
 }
-bool rpb_bwr_supported(int C, int Wp, int K2, int FW) {
-    return !bwr_off() && C == 64 && K2 >= 1 && K2 <= 32 && Wp >= 1 && (long)Wp * 256 < (1L << 30) && FW >= 0 && FW <= 16 &&
+bool rpb_bwr_supported(int C, int Wp, int K2) {
+    return !bwr_off() && C == 64 && K2 >= 1 && K2 <= 32 && Wp >= 1 && (long)Wp * 256 < (1L << 30) &&
            (size_t)((Wp + 31) / 32) * 6 * 1024 <= 150 * 1024;
 }
 
@@ -359,37 +327,36 @@ int rpb_bwr_launch(const BwrArgs& a, long part_rows, hipStream_t st) {
     const int mt = a.K2 > 32 ? 3 : 2;
     RPB_REQUIRE(mt == 2 || (a.CS == 128 && a.K2 <= 48), "bn_bwd_row (bf16 pipe): K2 = %d", a.K2);
     const size_t lds = (size_t)((a.Wp + 31) / 32) * 3 * mt * 64 * 16;
-    const bool gelu = a.gelu != 0, xbn = a.xf.mean != nullptr, xgelu = xbn && a.xf.gelu != 0, feat = a.FW > 0, nox = a.x == nullptr;
+    const bool gelu = a.gelu != 0, xbn = a.xf.mean != nullptr, xgelu = xbn && a.xf.gelu != 0, nox = a.x == nullptr;
     if (nox && a.CS == 128 && mt == 3) {
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, false, true, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, false, true, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, false, true, 128, 3>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
-        else hipLaunchKernelGGL((bwr_kernel<false, false, false, false, true, 128, 3>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, true, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, true, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, true, 128, 3>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        else hipLaunchKernelGGL((bwr_kernel<false, false, false, true, 128, 3>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
         RPB_CHECK_LAUNCH("bn_bwd_row (bf16 pipe, width 128, one 64-channel half, K2 <= 48)");
     }
     if (nox && a.CS == 128) {
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, false, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, false, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, false, true, 128>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
-        else hipLaunchKernelGGL((bwr_kernel<false, false, false, false, true, 128>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, true, 128>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        else hipLaunchKernelGGL((bwr_kernel<false, false, false, true, 128>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
         RPB_CHECK_LAUNCH("bn_bwd_row (bf16 pipe, width 128, one 64-channel half)");
     }
     if (nox) {
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, false, true>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
-        else hipLaunchKernelGGL((bwr_kernel<false, false, false, false, true>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (gelu) hipLaunchKernelGGL((bwr_kernel<true, false, false, true>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
+        else hipLaunchKernelGGL((bwr_kernel<false, false, false, true>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);
         RPB_CHECK_LAUNCH("bn_bwd_row (bf16 pipe, no weight gradient)");
     }
-#define RPB_BWR(G_, B_, X_, F_)                                                                                                \
-    if (gelu == G_ && xbn == B_ && xgelu == X_ && feat == F_) {                                                                \
-        (void)hipFuncSetAttribute((const void*)bwr_kernel<G_, B_, X_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((bwr_kernel<G_, B_, X_, F_>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);                          \
+#define RPB_BWR(G_, B_, X_)                                                                                                    \
+    if (gelu == G_ && xbn == B_ && xgelu == X_) {                                                                              \
+        (void)hipFuncSetAttribute((const void*)bwr_kernel<G_, B_, X_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
+        hipLaunchKernelGGL((bwr_kernel<G_, B_, X_>), dim3(grid), dim3(BW_WAVES * 64), lds, st, a);                              \
     }
-    RPB_BWR(false, false, false, false) RPB_BWR(true, false, false, false)
-    RPB_BWR(false, true, false, false) RPB_BWR(true, true, false, false)
-    RPB_BWR(false, true, true, false) RPB_BWR(true, true, true, false)
-    RPB_BWR(false, false, false, true) RPB_BWR(true, false, false, true)
+    RPB_BWR(false, false, false) RPB_BWR(true, false, false)
+    RPB_BWR(false, true, false) RPB_BWR(true, true, false)
+    RPB_BWR(false, true, true) RPB_BWR(true, true, true)
 #undef RPB_BWR
     RPB_CHECK_LAUNCH("bn_bwd_row (bf16 pipe)");
 }

@@ -40,9 +40,6 @@ struct CellMixArgs {
 #ifndef CM_MAX_THREADS
 #define CM_MAX_THREADS 768      // 12 waves per CU = 3 per SIMD -> <=168 VGPRs
 #endif
-#ifndef CM_PREF1
-#define CM_PREF1 0
-#endif
 #ifndef CM_UNROLL
 #define CM_UNROLL 8
 #endif
@@ -84,7 +81,6 @@ __global__ __launch_bounds__((KC >= 128 || STATS == 2) ? 512 : CM_MAX_THREADS) v
     constexpr int CO = NT * 32;
     constexpr int XS = KC + 1;
     constexpr int NX = KC / 8;                       // float4 loads per lane per tile
-    constexpr bool PREF1 = CM_PREF1 && NT <= 2;      // prefetch the second z2 row of a straddling tile too
     typedef typename VecT<NT>::T vecb;
     extern __shared__ float lds[];
     const int K2 = a.K2, Wp = a.Wp;
@@ -193,7 +189,7 @@ __global__ __launch_bounds__((KC >= 128 || STATS == 2) ? 512 : CM_MAX_THREADS) v
             }
         }
         // ---- 2. z2 rows of this tile -> registers (land while the conv MFMAs run)
-        float zr0[SPEC ? K2S : 1][NT], zr1[(SPEC && PREF1) ? K2S : 1][NT];
+        float zr0[SPEC ? K2S : 1][NT];
         int g0 = 0, g1 = 0, myg = 0, myw = 0;
         bool valid = false;
         if (SPEC) {
@@ -222,13 +218,6 @@ __global__ __launch_bounds__((KC >= 128 || STATS == 2) ? 512 : CM_MAX_THREADS) v
                 for (int s = 0; s < K2S; ++s)
 #pragma unroll
                     for (int t = 0; t < NT; ++t) zr0[s][t] = (2 * s + half < K2) ? zp[lo + 2 * s * CO + t * 32] : 0.f;
-            }
-            if (PREF1 && g1 > g0) {
-                const float* zq = zp + (long)K2 * CO;
-#pragma unroll
-                for (int s = 0; s < K2S; ++s)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) zr1[s][t] = (2 * s + half < K2) ? zq[lo + 2 * s * CO + t * 32] : 0.f;
             }
         }
         // ---- 2b. STATS == 2: this tile's pre-BN values (same positions as the outputs) for the BN-backward sums
@@ -278,24 +267,16 @@ __global__ __launch_bounds__((KC >= 128 || STATS == 2) ? 512 : CM_MAX_THREADS) v
                 const float* gp = GWl + half * Wp + myw;
                 const float* zq = a.z2 + (long)gg * K2 * CO;
                 const int lo = half * CO + col;
-                const bool pre = PREF1 && (gg == g0 + 1);
                 float zb[SPEC ? K2S : 1][NT];
-                if (!pre) {
 #pragma unroll
-                    for (int s = 0; s < K2S; ++s)
+                for (int s = 0; s < K2S; ++s)
 #pragma unroll
-                        for (int t = 0; t < NT; ++t) zb[s][t] = (2 * s + half < K2) ? zq[lo + 2 * s * CO + t * 32] : 0.f;
-                }
+                    for (int t = 0; t < NT; ++t) zb[s][t] = (2 * s + half < K2) ? zq[lo + 2 * s * CO + t * 32] : 0.f;
 #pragma unroll
                 for (int s = 0; s < K2S; ++s) {
                     const float av = mine ? gp[2 * s * Wp] : 0.f;
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        float b;
-                        if (PREF1) b = pre ? zr1[s][t] : zb[s][t];
-                        else b = zb[s][t];
-                        acc[t] = mfma32(av, b, acc[t]);
-                    }
+                    for (int t = 0; t < NT; ++t) acc[t] = mfma32(av, zb[s][t], acc[t]);
                 }
             }
         }
@@ -646,14 +627,14 @@ extern "C" int rpb_cell_mix_eval_dft_supported(long ncell, int K2, int Wp, int K
 }
 
 // Backward cell_mix of a Fourier layer with the layer's Conv3d weight gradient riding along (wave pairs of csrc/rpb_cmx.hip, WG; C = 64;
-// the one-wave-per-SIMD organisation of round 4 lost every A/B since and is archived as tools/archive/rpb_cmw.hip):
+// the one-wave-per-SIMD organisation of round 4 lost every A/B since and was removed):
 //   out  = gs Wc + FW^T z2, stored as gz = out * act'(BN(s_prev)) when gelu == 2        (as rpb_cell_mix with bnb_*)
 //   stats_part[slot][2][64] = partial (sum gz, sum gz * shat) of the layer below
 //   wg_part[slot][64][64]   = partial dWc[co][ci] = sum_cells gs[cell][co] * act(BN(s_prev))[cell][ci]
 // with slot < rpb_cell_mix_wgrad_slots(ncell, Wp).  Wc is convs.l.weight [co][ci]; FW the adjoint stage matrix [K2][Wp].
 extern "C" long rpb_cell_mix_wgrad_slots(long ncell, int Wp) { return Wp > 0 ? rpb_cmx_wg_slots(ncell, Wp) : -1; }
 extern "C" int rpb_cell_mix_wgrad_supported(long ncell, int K2, int Wp) {
-    return rpb_cmx_supported(ncell, 64, 64, K2, Wp, true, false) && rpb_bwr_supported(64, Wp, K2, 0) ? 1 : 0;
+    return rpb_cmx_supported(ncell, 64, 64, K2, Wp, true, false) && rpb_bwr_supported(64, Wp, K2) ? 1 : 0;
 }
 extern "C" int rpb_cell_mix_wgrad(const float* gs, const float* Wc, const float* z2, const float* FW, float* out, float* stats_part,
                                   float* wg_part, long ncell, int K2, int Wp, const float* s_prev, const float* mean, const float* invstd,

@@ -46,7 +46,7 @@ int rpb_cmx_launch(const CmxArgs& a, int stats, hipStream_t st);
 // The STATS == 2 launch with the 1x1-conv weight gradient of the same layer riding along (x = gs of the layer, bnb_s = the pre-BN tensor
 // whose activation is the layer input): dWc[co][ci] = sum_cells x[cell][co] * act(BN(bnb_s))[cell][ci] -- wave pairs inside the
 // two-waves-per-SIMD kernel (rpb_cmx.hip, template parameter WG).  (The one-wave-per-SIMD organisation of round 4, measured slower in
-// every A/B of rounds 4 and 5, is archived under tools/archive/rpb_cmw.hip and no longer compiled.)
+// every A/B of rounds 4 and 5, was removed.)
 long rpb_cmx_wg_slots(long ncell, int Wp);         // partial rows of stats_part ([2][64]) and wg_part ([64][64])
 int rpb_cmx_wg_launch(const CmxArgs& a, hipStream_t st);
 

@@ -44,15 +44,9 @@ __device__ __forceinline__ u32x4 ld16a(rsrc_t r, int voff) {
 __device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, RPB_STREAM_AUX);
 }
-// per-tensor policies of the SMALL streams (round 6 sweep, tools/eval_policy_sweep.sh): the z2 rows this launch reads were written by the
-// inverse H stage right before it, the Y1 rows the fused W stage writes are read by the next H stage right after it (0.9 GB each at the
-// headline shape; the 256 MB MALL can hold the tail of the producer / the head of the consumer)
-#ifndef CMX_Z_AUX
-#define CMX_Z_AUX RPB_STREAM_AUX
-#endif
-#ifndef CMX_Y_AUX
-#define CMX_Y_AUX RPB_STREAM_AUX
-#endif
+// the SMALL streams -- the z2 rows this launch reads (written by the inverse H stage right before it) and the Y1 rows the fused W stage writes
+// (read by the next H stage right after it), 0.9 GB each at the headline shape -- keep the policy of the large ones: a round-6 sweep of
+// per-tensor policies found no better one (the 256 MB MALL could hold the tail of the producer / the head of the consumer)
 template <int AUX>
 __device__ __forceinline__ void st16a(f32x4v v, rsrc_t r, int voff) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, AUX);
@@ -88,9 +82,6 @@ __device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
 // the dropped lo*lo term is <= 2^-22 |a b| -- the grade of "3xTF32", NOT the 2^-24 grade of the default path.  Half the matrix-pipe time
 // and 2.5 instead of 5.5 vector instructions per split value.  The planes travel in the bf16x8 containers of the default path (bit
 // patterns only): plane slot 0 = hi, slot 1 = lo.  fp16's range is handled by exact power-of-two scalings, see CmxArgs::spec_exp.
-#ifndef RPB_H2_FMAMIX
-#define RPB_H2_FMAMIX 1
-#endif
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2w __attribute__((ext_vector_type(2)));
@@ -101,7 +92,6 @@ __device__ __forceinline__ void split8h(const float (&v)[8], bf16x8& h, bf16x8& 
         const f32x2w ab = {v[2 * q], v[2 * q + 1]};
         const f16x2v hh = __builtin_convertvector(ab, f16x2v);                       // v_cvt_pk_f16_f32 (RNE)
         uh[q] = __builtin_bit_cast(unsigned, hh);
-#if RPB_H2_FMAMIX
         // residual a - float(hi) as ONE v_fma_mix_f32 per value (f16 half * -1 + f32; exact): 4 instead of 5 instructions per value pair
         // (left alone the compiler converts both halves and subtracts packed: 2 x v_cvt_f32_f16 + v_pk_add_f32)
         float r0, r1;
@@ -110,9 +100,6 @@ __device__ __forceinline__ void split8h(const float (&v)[8], bf16x8& h, bf16x8& 
         asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hu), "v"(a0));
         asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hu), "v"(a1));
         const f32x2w r = {r0, r1};
-#else
-        const f32x2w r = ab - __builtin_convertvector(hh, f32x2w);                   // exact in fp32
-#endif
         const f16x2v ll = __builtin_convertvector(r, f16x2v);
         ul[q] = __builtin_bit_cast(unsigned, ll);
     }
@@ -158,7 +145,7 @@ __device__ __forceinline__ f32x4v mfma16h(bf16x8 a, bf16x8 b, f32x4v c) {
 //       (x = gs of the layer, bnb_s = the pre-BN tensor whose activation is the layer input; autograd of fno.py:115).  The product
 //       contracts over CELLS, so it wants both factors as "8 cells of one channel per lane": act(z) has that form in the epilogue
 //       (accumulator layout), gs does not (it is this kernel's A operand, lane = cell).  A wave that did both would need 64 more
-//       accumulator registers than the 256 of a two-waves-per-SIMD kernel (the one-wave-per-SIMD version, tools/archive/rpb_cmw.hip, was
+//       accumulator registers than the 256 of a two-waves-per-SIMD kernel (the one-wave-per-SIMD version of round 4, removed, was
 //       bound by its own instruction stream: 3.4 ms against 2.4 ms for this launch without the product).  So the workgroup is
 //       FOUR PAIRS of waves: "mix" wave p (waves 0-3) is the STATS == 2 kernel and additionally leaves act(z) of its tile -- one erf
 //       serves act and act' -- in an 8 KB LDS mailbox; "wgrad" wave p + 4 fetches the same tile's gs in accumulator layout (L2 hits:
@@ -186,29 +173,9 @@ __device__ __forceinline__ f32x4v mfma16h(bf16x8 a, bf16x8 b, f32x4v c) {
 //       halves (the second read mostly out of L2 / MALL: the pair walks the same lines).  The register image of the x tile stays 32
 //       registers: K-steps 2, 3 of THIS tile are requested into the slots of K-steps 0, 1 as soon as those are split, the next tile's
 //       K-steps 0, 1 into the slots of 2, 3 (half a tile of prefetch distance instead of a whole one).
-// CMX_WG_PRIO: s_setprio 1 for one role of the weight-gradient wave pairs (1: the wgrad wave, the second-dispatched half of the
-// workgroup; 2: the mix wave; 0: none).  Measured (profiles/r05_kbench_valu_variants.txt) -- see DESIGN.md section 4.0000
-#ifndef CMX_WG_PRIO
-#define CMX_WG_PRIO 0
-#endif
-// CMX_WG_GELU_AS: act / act' of the weight-gradient pairs' mix wave from one exponential + one reciprocal (gelu_both_as2x2, rpb_common.h)
-// instead of the erf polynomial + two exponentials
-#ifndef CMX_WG_ONE_EPILOGUE
-#define CMX_WG_ONE_EPILOGUE 0    /* experiment: the wave pairs' mix wave always runs the masked epilogue (a smaller loop body for a few selects per tile) */
-#endif
-#ifndef CMX_ONE_EPILOGUE
-#define CMX_ONE_EPILOGUE 1
-#endif
-#ifndef CMX_SPLIT_LAST
-#define CMX_SPLIT_LAST 1
-#endif
-#ifndef CMX_SPLIT_LAST_EVAL
-#define CMX_SPLIT_LAST_EVAL 0    /* experiment: the same for the fp32-storage eval launches now that they hold one epilogue copy */
-#endif
-#define CMX_SPLITL(STATS_, BF_) (CMX_SPLIT_LAST && ((STATS_) == 1 || (CMX_SPLIT_LAST_EVAL && (STATS_) == 0 && !(BF_))))
-#ifndef CMX_WG_GELU_AS
-#define CMX_WG_GELU_AS 1
-#endif
+// The weight-gradient pairs' mix wave forms act / act' from one exponential + one reciprocal (gelu_both_as2x2, rpb_common.h) instead of
+// the erf polynomial + two exponentials.  (Static wave priorities for either role of the pairs were measured and left off:
+// profiles/r05_kbench_valu_variants.txt)
 // H2:   eval only (STATS == 0 with the output transform), fp32 storage -- the f16x2 arithmetic above for the channel mixing (not with FEAT:
 //       the raw feature fields keep the range-safe bf16 planes, their mixing is one K-step), the last inverse stage and the fused W stage.
 //       Scalings (exact: powers of two): conv weights and bias x 2^H2W, GW x 2^(spec_exp + H2W), z2 x 2^-spec_exp, and 2^-H2W rides in the
@@ -344,9 +311,6 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
     if constexpr (WG) {
         if (wave >= CMX_WG_PAIRS) {
             // ================= "wgrad" wave of pair p = wave - 4: walks the same tiles as mix wave p
-#if CMX_WG_PRIO == 1
-            __builtin_amdgcn_s_setprio(1);               // static priority for the second-dispatched half of the workgroup (A/B: see CMX_WG_PRIO)
-#endif
             const int pair = wave - CMX_WG_PAIRS;
             const int G = __builtin_amdgcn_readfirstlane((int)((unsigned)a.ncell / (unsigned)Wp));
             const int TQ = (Wp + 31) >> 5;
@@ -435,9 +399,6 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
             return;
         }
     }
-#if CMX_WG_PRIO == 2
-    if (WG) __builtin_amdgcn_s_setprio(1);
-#endif
     int wg_tiles = 0;                                // WG, mix wave: tiles handed to the pair's wgrad wave so far
     u32x4* MBw = MBs + (WG ? wave : 0) * 8 * 64 + lane;
     int* wg_fl = flags + 2 * (WG ? wave : 0);
@@ -525,7 +486,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
         }
         const rsrc_t rz = make_rsrc(a.z2 + g * K2 * CC + 64 * hsel, (unsigned)K2 * (unsigned)CB - 256u * (unsigned)hsel);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) zr[e] = ld16a<CMX_Z_AUX>(rz, (8 * kg + e) * CB + m * 16);
+        for (int e = 0; e < 8; ++e) zr[e] = ld16a<RPB_STREAM_AUX>(rz, (8 * kg + e) * CB + m * 16);
     };
 
     u32x4* Zw = Zs + wave * ZST * 64 + lane;
@@ -535,7 +496,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
     // WG: pin the (wave-uniform) line indices to SGPRs -- with the second wave role in the kernel the compiler keeps them in VGPRs and
     // wraps every buffer access in a waterfall loop
     auto U = [&](long v) -> long { return WG ? (long)__builtin_amdgcn_readfirstlane((int)v) : v; };
-    // CMX_SPLIT_LAST: the tile body exists twice -- for a line's last tile (the only one that can be a half tile or carry masked cells, and the
+    // SPLITL: the tile body exists twice -- for a line's last tile (the only one that can be a half tile or carry masked cells, and the
     // one that requests the next line's z2 row) and for all the others, where `last` / `half_tile` are compile-time false: without the
     // specialisation every group of four MFMAs ends in a branch on `half_tile` (36 basic blocks per tile that the scheduler cannot cross).
     // Measured per variant (B = 32, two boxes' worth of A/B in profiles/r06b_ab2_split_last.txt): the training forward with the lazy
@@ -544,7 +505,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
     // instruction cache).  So: the STATS == 1 instances only.
     auto do_tile = [&](auto last_tag, u32x4 (&xa)[2][4], long gi, int q, long ngi, int nq) {
         constexpr bool LASTC = decltype(last_tag)::value;
-        constexpr bool SPLITL = CMX_SPLITL(STATS, BF);              // measured per variant (profiles/r06b_ab2_split_last.txt), see CMX_SPLIT_LAST
+        constexpr bool SPLITL = STATS == 1;                        // measured per variant (profiles/r06b_ab2_split_last.txt), see above
         {
             const long g = U(line_of(gi));
             const rsrc_t ro = make_rsrc(a.out + g * line_floats + 64 * hsel, line_bytes - 256u * (unsigned)hsel);
@@ -738,7 +699,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                     for (int r = 0; r < 4; ++r) {
                         const bool valid = !MASKED || (32 * q + 16 * j + 4 * kg + r < Wp);
                         f32x4v o, avr;
-                        // channel pairs (packed fp32 math); the erf polynomials of the two pairs run in lock-step (gelu2x2 / gelu_both2x2)
+                        // channel pairs (packed fp32 math); the erf polynomials of the two pairs run in lock-step (gelu2x2 / gelu_both_as2x2)
                         f32x2 vv[2], shv[2], gpv[2], acv[2];
 #pragma unroll
                         for (int tt = 0; tt < 2; ++tt) {
@@ -755,11 +716,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                         if (STATS == 0 && oxf && bgelu) gelu2x2(vv[0], vv[1]);
                         if (STATS == 2 && bgelu) {
                             if (WG) {           // act(z) for the weight gradient: the same erf serves act and act'
-#if CMX_WG_GELU_AS
                                 gelu_both_as2x2(acv[0], acv[1], acv[0], acv[1], gpv[0], gpv[1]);
-#else
-                                gelu_both2x2(acv[0], acv[1], acv[0], acv[1], gpv[0], gpv[1]);
-#endif
                             } else {
                                 gpv[0] = gelu_grad2(acv[0]);
                                 gpv[1] = gelu_grad2(acv[1]);
@@ -815,7 +772,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                     if (lane == 0) __hip_atomic_store(wg_fl, wg_tiles, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             };
-            if ((STATS == 0 && CMX_ONE_EPILOGUE) || (WG && CMX_WG_ONE_EPILOGUE)) epilogue(std::true_type{});   // STATS == 0: no sums to mask, one copy of the code instead of two identical ones
+            if (STATS == 0) epilogue(std::true_type{});   // STATS == 0: no sums to mask, one copy of the code instead of two identical ones
             else if (last) epilogue(std::true_type{});
             else epilogue(std::false_type{});
             if (DFT) {
@@ -893,7 +850,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            st16a<CMX_Y_AUX>(f32x4v{Yacc[i][0][r], Yacc[i][1][r], Yacc[i][2][r], Yacc[i][3][r]}, ry, (16 * i + 4 * kg + r) * 256 + m * 16);
+                            st16a<RPB_STREAM_AUX>(f32x4v{Yacc[i][0][r], Yacc[i][1][r], Yacc[i][2][r], Yacc[i][3][r]}, ry, (16 * i + 4 * kg + r) * 256 + m * 16);
                     }
                 }
             }
@@ -901,7 +858,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
     };
 #define CMX_DO_TILE(XA, G_, Q_, NG_, NQ_)                                                                      \
     do {                                                                                                       \
-        if (CMX_SPLITL(STATS, BF) && (Q_) + 1 == TQ) do_tile(std::true_type{}, XA, G_, Q_, NG_, NQ_);              \
+        if (STATS == 1 && (Q_) + 1 == TQ) do_tile(std::true_type{}, XA, G_, Q_, NG_, NQ_);              \
         else do_tile(std::false_type{}, XA, G_, Q_, NG_, NQ_);                                                 \
     } while (0)
     int pend = 0;                   // claim mode 2: the wave's outstanding claim (lane 0)

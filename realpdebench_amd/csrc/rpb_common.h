@@ -215,18 +215,12 @@ __device__ __forceinline__ void gelu_both2(f32x2 x, f32x2& g, f32x2& gp) {
 // and cannot issue back to back; left alone the compiler evaluates one nine-term chain after the other (shortest live ranges), so a wave
 // spends the polynomial waiting on itself.  Written as two interleaved chains every instruction has an independent neighbour.
 // Element-wise the operations -- and therefore the results -- are those of fast_erf2 / gelu2 / gelu_both2.
-#ifndef RPB_ERF_ILP_FENCE
-#define RPB_ERF_ILP_FENCE 1     /* keep the interleaving: the scheduler may not move instructions across the step boundaries */
-#endif
+// A scheduling barrier behind every step keeps the interleaving: the scheduler may not move instructions across the step boundaries.
 __device__ __forceinline__ void fast_erf2x2(f32x2 xa, f32x2 xb, f32x2& ra, f32x2& rb) {
     const f32x2 ta = __builtin_elementwise_min(__builtin_elementwise_abs(xa), pk2(4.0f));
     const f32x2 tb = __builtin_elementwise_min(__builtin_elementwise_abs(xb), pk2(4.0f));
     f32x2 pa = pk2(1.160457393e-05f), pb = pk2(1.160457393e-05f);
-#if RPB_ERF_ILP_FENCE
 #define RPB_ERF_STEP(c) pa = pk_fma(pa, ta, pk2(c)); pb = pk_fma(pb, tb, pk2(c)); __builtin_amdgcn_sched_barrier(0);
-#else
-#define RPB_ERF_STEP(c) pa = pk_fma(pa, ta, pk2(c)); pb = pk_fma(pb, tb, pk2(c));
-#endif
     RPB_ERF_STEP(-1.529619341e-04f)
     RPB_ERF_STEP(8.482242992e-04f)
     RPB_ERF_STEP(-2.274763673e-03f)
@@ -254,20 +248,12 @@ __device__ __forceinline__ float fma_abs_b(float h, float m) {      // the pair'
 }
 // gelu(x) = x/2 + (x/2) erf(x / sqrt 2) = h + |h| (1 - e), h = x / 2 (h has the sign of the erf argument): the sign transfer of erf is the
 // |.| source modifier of the last FMA -- two packed instructions per pair fewer than (0.5 x) (1 + copysign(1 - e, x))
-#ifndef RPB_GELU_ABS_FMA
-#define RPB_GELU_ABS_FMA 1
-#endif
 __device__ __forceinline__ void gelu2x2(f32x2& xa, f32x2& xb) {
-#if RPB_GELU_ABS_FMA
     const f32x2 sa_ = xa * pk2(0.70710678118654752440f), sb_ = xb * pk2(0.70710678118654752440f);
     const f32x2 ta = __builtin_elementwise_min(__builtin_elementwise_abs(sa_), pk2(4.0f));
     const f32x2 tb = __builtin_elementwise_min(__builtin_elementwise_abs(sb_), pk2(4.0f));
     f32x2 pa = pk2(1.160457393e-05f), pb = pk2(1.160457393e-05f);
-#if RPB_ERF_ILP_FENCE
 #define RPB_ERF_STEP(c) pa = pk_fma(pa, ta, pk2(c)); pb = pk_fma(pb, tb, pk2(c)); __builtin_amdgcn_sched_barrier(0);
-#else
-#define RPB_ERF_STEP(c) pa = pk_fma(pa, ta, pk2(c)); pb = pk_fma(pb, tb, pk2(c));
-#endif
     RPB_ERF_STEP(-1.529619341e-04f)
     RPB_ERF_STEP(8.482242992e-04f)
     RPB_ERF_STEP(-2.274763673e-03f)
@@ -284,60 +270,36 @@ __device__ __forceinline__ void gelu2x2(f32x2& xa, f32x2& xb) {
     const f32x2 ha = pk2(0.5f) * xa, hb = pk2(0.5f) * xb;
     xa = f32x2{fma_abs_b(ha[0], ma[0]), fma_abs(ha[1], ma[1])};
     xb = f32x2{fma_abs_b(hb[0], mb[0]), fma_abs(hb[1], mb[1])};
-#else
-    f32x2 ea, eb;
-    fast_erf2x2(xa * pk2(0.70710678118654752440f), xb * pk2(0.70710678118654752440f), ea, eb);
-    xa = (pk2(0.5f) * xa) * (pk2(1.0f) + ea);
-    xb = (pk2(0.5f) * xb) * (pk2(1.0f) + eb);
-#endif
-}
-__device__ __forceinline__ void gelu_both2x2(f32x2 xa, f32x2 xb, f32x2& ga, f32x2& gb, f32x2& gpa, f32x2& gpb) {
-    f32x2 ea, eb;
-    fast_erf2x2(xa * pk2(0.70710678118654752440f), xb * pk2(0.70710678118654752440f), ea, eb);
-    const f32x2 ha = pk2(0.5f) * (pk2(1.0f) + ea), hb = pk2(0.5f) * (pk2(1.0f) + eb);
-    const f32x2 qa = (pk2(-0.72134752044448170368f) * xa) * xa, qb = (pk2(-0.72134752044448170368f) * xb) * xb;
-    const f32x2 pa = f32x2{__builtin_amdgcn_exp2f(qa[0]), __builtin_amdgcn_exp2f(qa[1])};
-    const f32x2 pb = f32x2{__builtin_amdgcn_exp2f(qb[0]), __builtin_amdgcn_exp2f(qb[1])};
-    ga = (pk2(0.5f) * xa) * (pk2(1.0f) + ea);
-    gb = (pk2(0.5f) * xb) * (pk2(1.0f) + eb);
-    gpa = ha + xa * (pk2(0.39894228040143267794f) * pa);
-    gpb = hb + xb * (pk2(0.39894228040143267794f) * pb);
 }
 
 // The same pair of results from ONE exponential and one reciprocal (Abramowitz-Stegun 26.2.17: Phi(-|u|) = phi(u) t P4(t), t = 1 / (1 + p |u|),
 // |error| < 7.5e-8 -- the grade of fast_erf; the density phi(u) is what gelu' needs anyway): 9.5 packed / scalar instructions + 2
-// transcendentals per value against 12 + 2 above.  Two pairs in lock-step, as gelu2x2.  (First used by the head, csrc/rpb_pjg.hip.)
+// transcendentals per value against 12 + 2 for the erf form.  Two pairs in lock-step, as gelu2x2.  (First used by the head, csrc/rpb_pjg.hip.)
 __device__ __forceinline__ void gelu_both_as2x2(f32x2 ua, f32x2 ub, f32x2& va, f32x2& vb, f32x2& da, f32x2& db) {
     const f32x2 aa = __builtin_elementwise_abs(ua), ab = __builtin_elementwise_abs(ub);
     const f32x2 dna = pk_fma(aa, pk2(0.23164189f), pk2(1.0f)), dnb = pk_fma(ab, pk2(0.23164189f), pk2(1.0f));
     const f32x2 qa = (ua * pk2(-0.72134752044448170368f)) * ua, qb = (ub * pk2(-0.72134752044448170368f)) * ub;
     const f32x2 ta = {__builtin_amdgcn_rcpf(dna[0]), __builtin_amdgcn_rcpf(dna[1])}, tb = {__builtin_amdgcn_rcpf(dnb[0]), __builtin_amdgcn_rcpf(dnb[1])};
     const f32x2 ea = {__builtin_amdgcn_exp2f(qa[0]), __builtin_amdgcn_exp2f(qa[1])}, eb = {__builtin_amdgcn_exp2f(qb[0]), __builtin_amdgcn_exp2f(qb[1])};
-#if RPB_ERF_ILP_FENCE
-#define RPB_AS_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define RPB_AS_FENCE()
-#endif
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     f32x2 pa = pk_fma(pk2(0.5307027145f), ta, pk2(-0.7265760135f)), pb = pk_fma(pk2(0.5307027145f), tb, pk2(-0.7265760135f));
     const f32x2 hua = pk2(0.5f) * ua, hub = pk2(0.5f) * ub;
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     pa = pk_fma(pa, ta, pk2(0.7107068705f)), pb = pk_fma(pb, tb, pk2(0.7107068705f));
     const f32x2 xa_ = aa * ea, xb_ = ab * eb;
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     pa = pk_fma(pa, ta, pk2(-0.142248368f)), pb = pk_fma(pb, tb, pk2(-0.142248368f));
     const f32x2 tea = ta * ea, teb = tb * eb;
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     pa = pk_fma(pa, ta, pk2(0.127414796f)), pb = pk_fma(pb, tb, pk2(0.127414796f));
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     const f32x2 ha = pk_fma(-pa, tea, pk2(0.5f)), hb = pk_fma(-pb, teb, pk2(0.5f));           // 1/2 - Phi(-|u|)
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     va = pk_fma(aa, ha, hua), vb = pk_fma(ab, hb, hub);
     const f32x2 wa = pk_fma(xa_, pk2(0.39894228040143267794f), ha), wb = pk_fma(xb_, pk2(0.39894228040143267794f), hb);
-    RPB_AS_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
     da = pk2(0.5f) + f32x2{__builtin_copysignf(wa[0], ua[0]), __builtin_copysignf(wa[1], ua[1])};
     db = pk2(0.5f) + f32x2{__builtin_copysignf(wb[0], ub[0]), __builtin_copysignf(wb[1], ub[1])};
-#undef RPB_AS_FENCE
 }
 
 // four channels at once (two packed pairs)

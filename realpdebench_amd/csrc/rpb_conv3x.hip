@@ -932,7 +932,7 @@ extern "C" int rpb_conv3x_wgrad(const void* Gt, const void* Xt, float* part, lon
     const int sp = conv3x_wgrad_nsplit(M, Co, Ci);
     const int RL = 2 * Dc + WX_KT, RS = RL / 2 + 4;
     const size_t lds_ring = ((size_t)WX_GS + 3 * 64 * RS) * 4 + 2 * 12 * 4;
-    if (Dc % 32 == 0 && lds_ring <= 160 * 1024 && !getenv("RPB_WGRAD_NORING")) {      // X rows in an LDS ring: each loaded once
+    if (Dc % 32 == 0 && lds_ring <= 160 * 1024) {      // X rows in an LDS ring: each loaded once
         WgrArgs r{(const uint16_t*)Gt, (const uint16_t*)Xt, part, M, Co, Ci, Hc, Wc, Dc, RL, RS};
         (void)hipFuncSetAttribute((const void*)conv3x_wgrad_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ring);
         hipLaunchKernelGGL(conv3x_wgrad_ring_kernel, dim3(sp, (Co / 64) * (Ci / 64) * 3), dim3(256), lds_ring, (hipStream_t)stream, r);

@@ -192,8 +192,7 @@ extern "C" int rpb_lift_feat(const float* x, const float* gt, const float* gh, c
     RPB_REQUIRE(x && gt && gh && gw && out && (FW == 8 || FW == 32) && Cin + 4 <= FW, "lift_feat: FW=%d must be 8 or 32 and hold Cin + 4 = %d fields", FW, Cin + 4);
     const long total = (long)B * Tp * Hp * Wp * (FW / 4);
     RPB_REQUIRE(total < (1L << 31), "lift_feat: too many cells");
-    static const bool generic = getenv("RPB_LIFT_FEAT_GENERIC") && atoi(getenv("RPB_LIFT_FEAT_GENERIC")) == 1;
-    if (Cin == 2 && FW == 8 && !generic) {
+    if (Cin == 2 && FW == 8) {
         const int nrows = B * Tp * Hp;
         long g2 = ((long)nrows + 3) / 4;
         const long cap2 = (long)rpb_num_cus() * 8;

@@ -228,8 +228,7 @@ __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
 }
 
 bool rpb_gemm3x2_supported(long M, int N, int K, bool has_mask, bool has_drop) {
-    static const int mode = getenv("RPB_GEMM3X_V2") ? atoi(getenv("RPB_GEMM3X_V2")) : 1;     // 0: off
-    if (mode == 0 || has_mask || K % 64 != 0 || M <= 0) return false;
+    if (has_mask || K % 64 != 0 || M <= 0) return false;
     return N % 256 == 0 || (N % 128 == 0 && !has_drop);                  // 128-column workgroups are built without dropout
 }
 

@@ -173,8 +173,7 @@ __global__ __launch_bounds__(LMX_WAVES * 64) void lift_mx_kernel(LiftMxArgs a) {
 }
 
 bool rpb_lift_mx_supported(int Cin, int C) {
-    static const bool off = getenv("RPB_LIFT_MX") && atoi(getenv("RPB_LIFT_MX")) == 0;
-    return !off && Cin == LMX_CIN && C == 64;
+    return Cin == LMX_CIN && C == 64;
 }
 
 int rpb_lift_mx_launch(const float* x, const float* gt, const float* gh, const float* gw, const float* w0, const float* b0, void* out_bf16,

@@ -334,20 +334,17 @@ __device__ __forceinline__ f32x4 m_mac6(const Planes& a, const Planes& b, f32x4 
     return c;
 }
 }  // namespace
-// MB_NT: non-temporal loads of the mode's weight tile (A/B: profiles/r05_kbench_valu_variants.txt)
-#ifndef MB_NT
-#define MB_NT 0
-#endif
 #define MB_XP 68        // row pitch (floats) of the coefficient tiles [ri][b 32][c 64]
 #define MB_WP 133       // row pitch (floats) of the weight tile [i 64][o 64][2]: odd, so that neither the row-strided gather of the forward
                         // (8 rows per lane group: 8 * 133 = 8 mod 32) nor the column-strided one of the data gradient piles onto a few banks
-// PERSIST (B <= 32, the default there): a workgroup walks modes m = blockIdx.x, + gridDim.x, ... and requests the NEXT mode's weight tile (8 x 16 B
-// per thread) and coefficient rows (4, wgrad 8) into registers before it computes the current one from LDS.  One workgroup per mode left
+// PERSIST (fwd / dgrad at B <= 32): a workgroup walks modes m = blockIdx.x, + gridDim.x, ... and requests the NEXT mode's weight tile (8 x 16 B
+// per thread) and coefficient rows (4) into registers before it computes the current one from LDS.  One workgroup per mode left
 // every global load's latency exposed -- the launch ran at 1-2 TB/s of a 100 MB weight read (0.095 ms cold, 0.046 warm, against 0.02 at the
 // copy rate) with three workgroups of 51 KB per CU and nothing in flight while they computed.
 template <int MODE, bool PERSIST = false>
 __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ GY,
                                                          float* __restrict__ OUT, int B, int M, int accumulate) {
+    static_assert(!(PERSIST && MODE == 2), "wgrad: one workgroup per mode");
     constexpr int C = 64;
     __shared__ __attribute__((aligned(16))) float Xs[2 * 32 * MB_XP];                      // fwd / wgrad: X, dgrad: gY
     __shared__ __attribute__((aligned(16))) float Ws[MODE == 2 ? 2 * 32 * MB_XP : 64 * MB_WP];   // fwd / dgrad: the mode's weight tile; wgrad: gY
@@ -358,23 +355,19 @@ __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict_
     const long plane = (long)M * C;
     const float* src = MODE == 1 ? GY : X;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 wq[PERSIST && MODE != 2 ? 8 : 1], xq[PERSIST ? 4 : 1], gq[PERSIST && MODE == 2 ? 4 : 1];      // PERSIST: the next mode's tiles in flight
+    f32x4 wq[PERSIST ? 8 : 1], xq[PERSIST ? 4 : 1];              // PERSIST: the next mode's tiles in flight
     auto fetch = [&](int mm) {                                   // PERSIST: issue the loads of mode mm (B <= 32: one batch pass)
         if (MODE != 2) {
             const float* Wm = Wt + (long)mm * C * C * 2;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) wq[PERSIST && MODE != 2 ? j : 0] = *reinterpret_cast<const f32x4*>(Wm + (long)(tid + 256 * j) * 4);
+            for (int j = 0; j < 8; ++j) wq[PERSIST ? j : 0] = *reinterpret_cast<const f32x4*>(Wm + (long)(tid + 256 * j) * 4);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int idx = tid + 256 * j, c4 = idx % (C / 4), r = idx / (C / 4), bl = r >> 1, ri = r & 1;
-            f32x4 v = z4, g = z4;
-            if (bl < B) {
-                v = *reinterpret_cast<const f32x4*>(src + (long)(bl * 2 + ri) * plane + (long)mm * C + 4 * c4);
-                if (MODE == 2) g = *reinterpret_cast<const f32x4*>(GY + (long)(bl * 2 + ri) * plane + (long)mm * C + 4 * c4);
-            }
+            f32x4 v = z4;
+            if (bl < B) v = *reinterpret_cast<const f32x4*>(src + (long)(bl * 2 + ri) * plane + (long)mm * C + 4 * c4);
             xq[PERSIST ? j : 0] = v;
-            if (MODE == 2) gq[PERSIST && MODE == 2 ? j : 0] = g;
         }
     };
     auto park = [&]() {                                          // PERSIST: registers -> LDS (waits for the loads)
@@ -382,7 +375,7 @@ __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict_
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int idx = tid + 256 * j, i = (2 * idx) / C, o = 2 * idx - i * C;
-                const f32x4 w = wq[PERSIST && MODE != 2 ? j : 0];
+                const f32x4 w = wq[PERSIST ? j : 0];
                 float* d = Ws + i * MB_WP + 2 * o;
                 d[0] = w[0], d[1] = w[1], d[2] = w[2], d[3] = w[3];
             }
@@ -391,7 +384,6 @@ __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict_
         for (int j = 0; j < 4; ++j) {
             const int idx = tid + 256 * j, c4 = idx % (C / 4), r = idx / (C / 4), bl = r >> 1, ri = r & 1;
             *reinterpret_cast<f32x4*>(Xs + (ri * 32 + bl) * MB_XP + 4 * c4) = xq[PERSIST ? j : 0];
-            if (MODE == 2) *reinterpret_cast<f32x4*>(Ws + (ri * 32 + bl) * MB_XP + 4 * c4) = gq[PERSIST && MODE == 2 ? j : 0];
         }
     };
     if (PERSIST) fetch(m);
@@ -399,11 +391,7 @@ __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict_
     if (!PERSIST && MODE != 2) {
         const float* Wm = Wt + (long)m * C * C * 2;
         for (int idx = tid; idx < C * C / 2; idx += 256) {       // two complex numbers per 16 B load: row i, columns o, o + 1
-#if MB_NT
-            const f32x4 w = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(Wm + (long)idx * 4));      // streamed once per launch by ONE workgroup
-#else
             const f32x4 w = *reinterpret_cast<const f32x4*>(Wm + (long)idx * 4);
-#endif
             const int i = (2 * idx) / C, o = 2 * idx - i * C;
             float* d = Ws + i * MB_WP + 2 * o;
             d[0] = w[0], d[1] = w[1], d[2] = w[2], d[3] = w[3];
@@ -517,53 +505,31 @@ __global__ __launch_bounds__(256) void mode_bf16_kernel(const float* __restrict_
   }
 }
 
-// resident workgroups per CU of the persistent instances (registers: 184 / 180 for fwd / dgrad -> two waves per SIMD; 288 for wgrad -> one)
-static int mode_persist_wgs(int mode) {
-    static const int f = getenv("RPB_MODE_PERSIST_WGS") ? atoi(getenv("RPB_MODE_PERSIST_WGS")) : 0;
-    return f > 0 ? f : (mode == 2 ? 1 : 2);
-}
+// resident workgroups per CU of the persistent instances (registers: 184 / 180 for fwd / dgrad -> two waves per SIMD)
+#define MB_PERSIST_WGS 2
 // Measured (B = 32, profiles/r06b_mode_persist.txt, tools/mode_cold_probe.py): the persistent instances run 0.054 -> 0.048 ms (fwd) and
 // 0.050 -> 0.044 ms (dgrad) with warm weights and 0.055 -> 0.047 / 0.055 -> 0.049 with COLD ones (six 100 MB weight buffers cycled through the
 // 256 MB Infinity Cache).  (A first reading of "0.124 ms persistent against 0.095 one-shot inside the step" came from HIP events around 50 us
 // launches: that is the host's launch gap, not device time -- rocprofv3's kernel trace of the step gives 57 us one-shot, 45 us persistent.)
-// So: forward and dgrad persistent (RPB_MODE_PERSIST_FWD=0 / RPB_MODE_PERSIST=0: one workgroup per mode), wgrad never (288 registers: one
-// workgroup per CU, 0.044 -> 0.046).
-static bool mode_persist_fwd() {
-    static const bool on = !(getenv("RPB_MODE_PERSIST_FWD") && atoi(getenv("RPB_MODE_PERSIST_FWD")) == 0);
-    return on;
-}
-static bool mode_persist_wgrad() {
-    static const bool on = getenv("RPB_MODE_PERSIST_WGRAD") && atoi(getenv("RPB_MODE_PERSIST_WGRAD")) == 1;
-    return on;
-}
-static bool mode_persist_on() {
-    static const bool on = !(getenv("RPB_MODE_PERSIST") && atoi(getenv("RPB_MODE_PERSIST")) == 0);
-    return on;
-}
-// ---- C = 128 (configs/fsi/fno.yaml, the Galerkin regressor) on the same pipe: the composite per-mode GEMM is [B x 256] x [256 x 256];
-// the weight tile (128 KB) does not fit next to the coefficients, so the workgroup walks the 64-wide output halves (fwd: o halves with
-// all 128 rows i of the weights; dgrad: i halves with all 128 columns o), re-staging the weight half in LDS (66 KB) each time.  wgrad
-// keeps sixteen 32 x 32 (re, im) tiles in registers, four per wave.  The VALU kernels above ran these at 18-25 TF/s (10.5 of the
+// So: forward and dgrad persistent, wgrad one workgroup per mode (a persistent wgrad instance, 288 registers: one workgroup per CU, measured
+// 0.044 -> 0.046, was removed).  B > 32 takes one workgroup per mode as well.
+// ---- C = 128 (configs/fsi/fno.yaml, the Galerkin regressor) on the same pipe: the composite per-mode GEMM is [B x 256] x [256 x 256].
+// wgrad keeps sixteen 32 x 32 (re, im) tiles in registers, four per wave.  The VALU kernels above ran these at 18-25 TF/s (10.5 of the
 // fsi step's 65 ms, tools/fsi_probe.py).
 #define MM_LD128 129
-template <int MODE>
-__global__ __launch_bounds__(256) void mode_mfma128_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ GY,
-                                                            float* __restrict__ OUT, int B, int M, int accumulate) {
+__global__ __launch_bounds__(256) void mode_mfma128_kernel(const float* __restrict__ X, const float* __restrict__ GY, float* __restrict__ OUT,
+                                                            int B, int M, int accumulate) {
     constexpr int C = 128;
     extern __shared__ float lds[];
-    float* Xs = lds;                               // [ri][b 32][c 128 (+1)]   fwd: X, dgrad: gY, wgrad: X
-    float* Ws = lds + 2 * 32 * MM_LD128;           // fwd: [ri][i 128][o-half 64 (+1)];  dgrad: [ri][i-half 64][o 128 (+1)];  wgrad: [ri][b 32][o 128 (+1)] = gY
+    float* Xs = lds;                               // [ri][b 32][c 128 (+1)] = X
+    float* Ws = lds + 2 * 32 * MM_LD128;           // [ri][b 32][o 128 (+1)] = gY
     const int m = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int col = lane & 31, half = lane >> 5;
     const long plane = (long)M * C;
-    const float* src = MODE == 1 ? GY : X;
-    const float* Wm = Wt + (long)m * C * C * 2;
-    f32x16 accA[4], accB[4];                       // wgrad: tile q = 4 * wave + j -> (i0, o0) = (32 (q >> 2), 32 (q & 3))
-    if (MODE == 2) {
+    f32x16 accA[4], accB[4];                       // tile q = 4 * wave + j -> (i0, o0) = (32 (q >> 2), 32 (q & 3))
 #pragma unroll
-        for (int j = 0; j < 4; ++j) accA[j] = accB[j] = zero16();
-    }
+    for (int j = 0; j < 4; ++j) accA[j] = accB[j] = zero16();
     for (int b0 = 0; b0 < B; b0 += 32) {
         if (b0) __syncthreads();
         for (int idx = tid; idx < 2 * 32 * (C / 4); idx += 256) {
@@ -571,97 +537,48 @@ __global__ __launch_bounds__(256) void mode_mfma128_kernel(const float* __restri
             const int bl = r >> 1, ri = r & 1, b = b0 + bl;
             f32x4 v = {0.f, 0.f, 0.f, 0.f}, g = {0.f, 0.f, 0.f, 0.f};
             if (b < B) {
-                v = *reinterpret_cast<const f32x4*>(src + (long)(b * 2 + ri) * plane + (long)m * C + 4 * c4);
-                if (MODE == 2) g = *reinterpret_cast<const f32x4*>(GY + (long)(b * 2 + ri) * plane + (long)m * C + 4 * c4);
+                v = *reinterpret_cast<const f32x4*>(X + (long)(b * 2 + ri) * plane + (long)m * C + 4 * c4);
+                g = *reinterpret_cast<const f32x4*>(GY + (long)(b * 2 + ri) * plane + (long)m * C + 4 * c4);
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 Xs[(ri * 32 + bl) * MM_LD128 + 4 * c4 + t] = v[t];
-                if (MODE == 2) Ws[(ri * 32 + bl) * MM_LD128 + 4 * c4 + t] = g[t];
+                Ws[(ri * 32 + bl) * MM_LD128 + 4 * c4 + t] = g[t];
             }
         }
-        if (MODE == 2) {
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = 4 * wave + j, i0 = 32 * (q >> 2), o0 = 32 * (q & 3);
-#pragma unroll 4
-                for (int s = 0; s < 16; ++s) {
-                    const int bl = 2 * s + half;
-                    const float xr = Xs[(0 * 32 + bl) * MM_LD128 + i0 + col], xi = Xs[(1 * 32 + bl) * MM_LD128 + i0 + col];
-                    const float gr = Ws[(0 * 32 + bl) * MM_LD128 + o0 + col], gi = Ws[(1 * 32 + bl) * MM_LD128 + o0 + col];
-                    accA[j] = mfma32(xr, gr, accA[j]);
-                    accA[j] = mfma32(xi, gi, accA[j]);
-                    accB[j] = mfma32(xr, gi, accB[j]);
-                    accB[j] = mfma32(-xi, gr, accB[j]);
-                }
-            }
-            continue;
-        }
-        for (int hf = 0; hf < 2; ++hf) {           // output half: columns (fwd: o, dgrad: i) 64 hf .. 64 hf + 63
-            __syncthreads();                       // Xs staged (first half) / the previous half's weight reads are done
-            if (MODE == 0) {                       // Ws[ri][i][o - 64 hf], 65 floats per row
-                for (int idx = tid; idx < C * 32; idx += 256) {          // 128 rows x 32 pairs of complex numbers
-                    const int i = idx >> 5, p2 = idx & 31, o = 64 * hf + 2 * p2;
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(Wm + ((long)i * C + o) * 2);
-                    Ws[(0 * C + i) * MM_LD + 2 * p2] = w[0];
-                    Ws[(1 * C + i) * MM_LD + 2 * p2] = w[1];
-                    Ws[(0 * C + i) * MM_LD + 2 * p2 + 1] = w[2];
-                    Ws[(1 * C + i) * MM_LD + 2 * p2 + 1] = w[3];
-                }
-            } else {                               // Ws[ri][i - 64 hf][o], 129 floats per row
-                for (int idx = tid; idx < 64 * 64; idx += 256) {         // 64 rows x 64 pairs of complex numbers
-                    const int il = idx >> 6, p2 = idx & 63, o = 2 * p2;
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(Wm + ((long)(64 * hf + il) * C + o) * 2);
-                    Ws[(0 * 64 + il) * MM_LD128 + o] = w[0];
-                    Ws[(1 * 64 + il) * MM_LD128 + o] = w[1];
-                    Ws[(0 * 64 + il) * MM_LD128 + o + 1] = w[2];
-                    Ws[(1 * 64 + il) * MM_LD128 + o + 1] = w[3];
-                }
-            }
-            __syncthreads();
-            const int ro = wave >> 1, n0 = (wave & 1) * 32;              // the wave's 32 columns of plane ro of this half
-            f32x16 acc = zero16();
-#pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const int wp = ri ^ ro;
-                const bool neg = MODE == 0 ? (ri == 1 && ro == 0) : (ri == 0 && ro == 1);
-                const float* xa = Xs + (ri * 32 + col) * MM_LD128 + half;
-                // fwd: B[k][n] = W[i = k][o = n0 + col] (row pitch 65);  dgrad: B[k][n] = W[i = n0 + col][o = k] (row pitch 129)
-                const float* wb = MODE == 0 ? Ws + (wp * C + half) * MM_LD + n0 + col : Ws + (wp * 64 + n0 + col) * MM_LD128 + half;
-                constexpr int kstep = MODE == 0 ? 2 * MM_LD : 2;
-#pragma unroll 8
-                for (int s = 0; s < C / 2; ++s) {
-                    const float a = xa[2 * s];
-                    acc = mfma32(neg ? -a : a, wb[s * kstep], acc);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int b = b0 + mfma_row(lane, r);
-                if (b < B) OUT[(long)(b * 2 + ro) * plane + (long)m * C + 64 * hf + n0 + col] = acc[r];
-            }
-        }
-    }
-    if (MODE == 2) {
-        float* Gm = OUT + (long)m * C * C * 2;
+        __syncthreads();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int q = 4 * wave + j, i0 = 32 * (q >> 2), o0 = 32 * (q & 3);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                f32x2* dst = reinterpret_cast<f32x2*>(Gm + ((long)(i0 + mfma_row(lane, r)) * C + o0 + col) * 2);
-                f32x2 v = {accA[j][r], accB[j][r]};
-                if (accumulate) v += *dst;
-                *dst = v;
+#pragma unroll 4
+            for (int s = 0; s < 16; ++s) {
+                const int bl = 2 * s + half;
+                const float xr = Xs[(0 * 32 + bl) * MM_LD128 + i0 + col], xi = Xs[(1 * 32 + bl) * MM_LD128 + i0 + col];
+                const float gr = Ws[(0 * 32 + bl) * MM_LD128 + o0 + col], gi = Ws[(1 * 32 + bl) * MM_LD128 + o0 + col];
+                accA[j] = mfma32(xr, gr, accA[j]);
+                accA[j] = mfma32(xi, gi, accA[j]);
+                accB[j] = mfma32(xr, gi, accB[j]);
+                accB[j] = mfma32(-xi, gr, accB[j]);
             }
+        }
+    }
+    float* Gm = OUT + (long)m * C * C * 2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = 4 * wave + j, i0 = 32 * (q >> 2), o0 = 32 * (q & 3);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            f32x2* dst = reinterpret_cast<f32x2*>(Gm + ((long)(i0 + mfma_row(lane, r)) * C + o0 + col) * 2);
+            f32x2 v = {accA[j][r], accB[j][r]};
+            if (accumulate) v += *dst;
+            *dst = v;
         }
     }
 }
 
-// ---- C = 128, second organisation of fwd / dgrad (round 5): the weights never pass through LDS.  The first organisation staged a 64-wide
-// half of the mode's 128 KB weight tile in LDS with four ds_write_b32 per 16 B load and ran ONE workgroup per CU (99 KB of LDS): 0.56 ms per
-// launch at the fsi shape for 0.54 GB of weights (1.4 TB/s) -- neither the matrix pipe (0.13 ms) nor the bytes (0.1 ms) but the staging.
+// ---- C = 128 fwd / dgrad (round 5): the weights never pass through LDS.  The first organisation (removed) staged a 64-wide half of the
+// mode's 128 KB weight tile in LDS with four ds_write_b32 per 16 B load and ran ONE workgroup per CU (99 KB of LDS): 0.56 ms per launch at the
+// fsi shape for 0.54 GB of weights (1.4 TB/s) -- neither the matrix pipe (0.13 ms) nor the bytes (0.1 ms) but the staging.
 // Here a wave owns 32 output columns of BOTH planes and loads its B operands straight from global memory in MFMA layout: forward, lane
 // (col, half) reads the complex number W[i = 2 s + half][o = n0 + col] (8 B; 256 B contiguous per row across the lanes) and feeds four
 // products (re / im of both output planes); data gradient, the lane walks ITS row W[i = n0 + col][:] in 16 B pieces (two complex numbers =
@@ -731,23 +648,15 @@ __global__ __launch_bounds__(256) void mode_mfma128d_kernel(const float* __restr
         }
     }
 }
-static bool mode128_direct() {            // RPB_MODE128_LDS=1: the first organisation (weight halves staged in LDS)
-    static const bool off = getenv("RPB_MODE128_LDS") && atoi(getenv("RPB_MODE128_LDS")) == 1;
-    return !off;
-}
-static size_t mode128_lds(int mode) {
-    const size_t xs = 2 * 32 * MM_LD128, ws = mode == 0 ? 2 * 128 * MM_LD : (mode == 1 ? 2 * 64 * MM_LD128 : 2 * 32 * MM_LD128);
-    return (xs + ws) * 4;
-}
 template <int MODE>
 static int launch_mode128(const float* X, const float* W, const float* GY, float* OUT, int B, int M, int accumulate, hipStream_t st) {
-    if (MODE != 2 && mode128_direct()) {
+    if (MODE != 2) {
         hipLaunchKernelGGL((mode_mfma128d_kernel<MODE>), dim3(M), dim3(256), 0, st, X, W, GY, OUT, B, M);
         return RPB_OK;
     }
-    const size_t lds = mode128_lds(MODE);
-    (void)hipFuncSetAttribute((const void*)mode_mfma128_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mode_mfma128_kernel<MODE>), dim3(M), dim3(256), lds, st, X, W, GY, OUT, B, M, accumulate);
+    const size_t lds = 2 * (2 * 32 * MM_LD128) * 4;
+    (void)hipFuncSetAttribute((const void*)mode_mfma128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(mode_mfma128_kernel, dim3(M), dim3(256), lds, st, X, GY, OUT, B, M, accumulate);
     return RPB_OK;
 }
 
@@ -775,8 +684,8 @@ static int mc_check(const void* a, const void* b, const void* c, int B, int M, i
 extern "C" int rpb_mode_contract_fwd(const float* X, const float* W, float* Y, int B, int M, int C, void* stream) {
     if (int e = mc_check(X, W, Y, B, M, C)) return e;
     if (mode_bf16_on(C)) {
-        if (B <= 32 && mode_persist_on() && mode_persist_fwd()) {
-            const int grid = M < mode_persist_wgs(0) * rpb_num_cus() ? M : mode_persist_wgs(0) * rpb_num_cus();
+        if (B <= 32) {
+            const int grid = M < MB_PERSIST_WGS * rpb_num_cus() ? M : MB_PERSIST_WGS * rpb_num_cus();
             hipLaunchKernelGGL((mode_bf16_kernel<0, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, X, W, (const float*)nullptr, Y, B, M, 0);
         } else {
             hipLaunchKernelGGL((mode_bf16_kernel<0>), dim3(M), dim3(256), 0, (hipStream_t)stream, X, W, (const float*)nullptr, Y, B, M, 0);
@@ -803,8 +712,8 @@ extern "C" int rpb_mode_contract_fwd(const float* X, const float* W, float* Y, i
 extern "C" int rpb_mode_contract_dgrad(const float* GY, const float* W, float* GX, int B, int M, int C, void* stream) {
     if (int e = mc_check(GY, W, GX, B, M, C)) return e;
     if (mode_bf16_on(C)) {
-        if (B <= 32 && mode_persist_on()) {
-            const int grid = M < mode_persist_wgs(0) * rpb_num_cus() ? M : mode_persist_wgs(0) * rpb_num_cus();
+        if (B <= 32) {
+            const int grid = M < MB_PERSIST_WGS * rpb_num_cus() ? M : MB_PERSIST_WGS * rpb_num_cus();
             hipLaunchKernelGGL((mode_bf16_kernel<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, W, GY, GX, B, M, 0);
         } else {
             hipLaunchKernelGGL((mode_bf16_kernel<1>), dim3(M), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, W, GY, GX, B, M, 0);
@@ -839,12 +748,7 @@ extern "C" int rpb_mode_contract_wgrad(const float* X, const float* GY, float* G
                                        void* stream) {
     if (int e = mc_check(X, GY, GW, B, M, C)) return e;
     if (mode_bf16_on(C)) {
-        if (B <= 32 && mode_persist_on() && mode_persist_wgrad()) {      // measured slower (288 registers: one workgroup per CU): off
-            const int grid = M < mode_persist_wgs(2) * rpb_num_cus() ? M : mode_persist_wgs(2) * rpb_num_cus();
-            hipLaunchKernelGGL((mode_bf16_kernel<2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, X, (const float*)nullptr, GY, GW, B, M, accumulate);
-        } else {
-            hipLaunchKernelGGL((mode_bf16_kernel<2>), dim3(M), dim3(256), 0, (hipStream_t)stream, X, (const float*)nullptr, GY, GW, B, M, accumulate);
-        }
+        hipLaunchKernelGGL((mode_bf16_kernel<2>), dim3(M), dim3(256), 0, (hipStream_t)stream, X, (const float*)nullptr, GY, GW, B, M, accumulate);
         RPB_CHECK_LAUNCH("mode_contract_wgrad");
     }
     if (mode_mfma_on(C)) {

@@ -19,7 +19,7 @@ struct PjfArgs {
     XForm xf;             // BatchNorm of the last layer: mean, invstd, gamma, beta (gelu must be 0)
 };
 
-// rpb_pjg.hip: 1 when the 32x32x16 kernel takes this shape (DO == 2 and not switched off with RPB_HEAD_PJG=0)
+// rpb_pjg.hip: 1 when the 32x32x16 kernel takes this shape (DO == 2)
 int pjg_supported(int DO);
 size_t pjg_lds();
 int pjg_launch(PjfArgs& p, bool loss, int grid, hipStream_t st);

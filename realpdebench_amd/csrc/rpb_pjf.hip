@@ -36,17 +36,9 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define PF_WAVES 4
 #define PF_TS 132          // row stride (floats) of the wave's transposition tile: 4 * 132 = 16 (mod 32) -> conflict-free ds_write_b32
 #define PF_DOMAX 4
-// PF_PIPE=1 asks the scheduler (sched_group_barrier) to alternate each region's MFMAs with the neighbouring stage's VALU work.  Measured
-// at B = 32: 4.27-4.31 ms with the forced interleaving, 4.00 ms without (the compiler's own order), 4.04 ms for the phase-by-phase
-// version -- one wave per SIMD is bound by its issue slots (~4 cycles per instruction + 12 more per MFMA), not by missing overlap.
-#ifndef PF_PIPE
-#define PF_PIPE 0
-#endif
-#if PF_PIPE
-#define PF_SGB(m, n, id) __builtin_amdgcn_sched_group_barrier(m, n, id)
-#else
-#define PF_SGB(m, n, id)
-#endif
+// The compiler's own instruction order: forcing each region's MFMAs to alternate with the neighbouring stage's VALU work (sched_group_barrier)
+// measured at B = 32 4.27-4.31 ms against 4.00 ms, 4.04 ms for the phase-by-phase version -- one wave per SIMD is bound by its issue slots
+// (~4 cycles per instruction + 12 more per MFMA), not by missing overlap.
 
 namespace {
 __device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
@@ -340,11 +332,6 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #pragma unroll
             for (int t0 = 0; t0 < 8; t0 += 2) mac_pair(0, t0);
             split_A(1);
-#pragma unroll
-            for (int i = 0; i < 96; ++i) {
-                PF_SGB(0x008, 1, 0);
-                PF_SGB(0x002, 1, 0);
-            }
             __builtin_amdgcn_sched_barrier(0);
             if (LOSS) {
                 // ---- region 3 (fused forward): all second-K-step products, then one 16-cell row tile at a time:
@@ -426,13 +413,6 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
                             act(j, 2 * pp - 1);
                         }
                     }
-                    if (pp > 0 && pp < 4) {
-    #pragma unroll
-                        for (int i = 0; i < 24; ++i) {
-                            PF_SGB(0x008, 1, 0);
-                            PF_SGB(0x002, 11, 0);
-                        }
-                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -486,11 +466,6 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #undef PF_X3
                     if (t < 7) {                                     // the next hidden tile's split rides between this tile's MFMAs
                         split_G(t + 1);
-#pragma unroll
-                        for (int i = 0; i < 22; ++i) {
-                            PF_SGB(0x008, 1, 0);
-                            PF_SGB(0x002, 2, 0);
-                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -550,11 +525,6 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #undef PF_B3
                     if (s < 3) {
                         split_T(s + 1);
-#pragma unroll
-                        for (int i = 0; i < 22; ++i) {
-                            PF_SGB(0x008, 1, 0);
-                            PF_SGB(0x002, 2, 0);
-                        }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -616,8 +586,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 static size_t pjf_lds() { return (size_t)(2 * 3 * 8 * 64 + 4 * 3 * 4 * 64) * 16 + (256 + PF_HID + PF_DOMAX * PF_HID) * 4 + (size_t)PF_WAVES * 16 * PF_TS * 4; }
 
 static bool pjf_off() {
-    static const bool off = (getenv("RPB_PROJ_F32") && atoi(getenv("RPB_PROJ_F32")) == 1) ||
-                            (getenv("RPB_HEAD_BWD_FUSED") && atoi(getenv("RPB_HEAD_BWD_FUSED")) == 0);
+    static const bool off = getenv("RPB_PROJ_F32") && atoi(getenv("RPB_PROJ_F32")) == 1;
     return off;
 }
 

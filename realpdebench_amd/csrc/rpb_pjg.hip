@@ -34,11 +34,7 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 #define PG_GH_PLANE 2048                   // bytes of one gh plane of 32 hidden units x 32 cells
 #define PG_GH_BUF (3 * PG_GH_PLANE)
 #define PG_GH_WAVE (2 * PG_GH_BUF)
-// PG_PIPE = n > 0: ask the scheduler for n vector instructions behind every MFMA of the hidden-tile loop (0: its own order)
-#ifndef PG_PIPE
-#define PG_PIPE 0
-#endif
-// PG_PIPE1 = n > 0: the same for contraction 1 (n vector instructions + one LDS read behind every MFMA of a K-step)
+// PG_PIPE1 = n > 0: ask the scheduler for n vector instructions + one LDS read behind every MFMA of a K-step of contraction 1
 #ifndef PG_PIPE1
 #define PG_PIPE1 2     /* measured: 3.79-3.85 -> 3.64 ms (the compiler lumps 7-9 instructions into some MFMA gaps and none into others) */
 #endif
@@ -58,12 +54,9 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 #define PG_T(i)
 #endif
 
-#ifndef RPB_HEAD_AUX
-#define RPB_HEAD_AUX 0   /* cache policy of the tile loads / stores (2 = nt): experiment switch */
-#endif
 namespace {
 __device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, RPB_HEAD_AUX));
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
 __device__ __forceinline__ f32x2 ld8(rsrc_t r, int voff) {
     return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0));
@@ -72,7 +65,7 @@ __device__ __forceinline__ f32x2 ld8(rsrc_t r, int voff) {
 // dword and the row swap its second result); a scalar copy first is safe
 __device__ __forceinline__ float asf(unsigned u) { return __builtin_bit_cast(float, u); }
 __device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, RPB_HEAD_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
 }
 __device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
 __device__ __forceinline__ unsigned pack_hi(float a, float b) {
@@ -590,15 +583,6 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
 #undef PG_BL
                 }
                 if (nt < 3) gh_stage(nt + 1);
-#if PG_PIPE
-                if (nt < 3) {
-#pragma unroll
-                    for (int i = 0; i < 48; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);           // one MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x002, PG_PIPE, 0);     // PG_PIPE vector instructions
-                    }
-                }
-#endif
                 PG_T(8)
             }
             PG_T(9)
@@ -666,8 +650,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
 size_t pjg_lds() { return (size_t)(4 * 4 * 3 * 64 + 8 * 2 * 3 * 64) * 16 + (PG_HID + 64 + PG_WAVES * 64) * 4 + (size_t)PG_WAVES * PG_GH_WAVE; }
 
 int pjg_supported(int DO) {
-    static const bool off = getenv("RPB_HEAD_PJG") && atoi(getenv("RPB_HEAD_PJG")) == 0;
-    return !off && DO == 2;
+    return DO == 2;
 }
 
 int pjg_launch(PjfArgs& p, bool loss, int grid, hipStream_t st) {

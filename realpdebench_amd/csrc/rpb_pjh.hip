@@ -35,12 +35,9 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 #define PH_PIPE 2
 #endif
 
-#ifndef RPB_HEAD_AUX
-#define RPB_HEAD_AUX 0   /* cache policy of the tile loads / stores (2 = nt): experiment switch */
-#endif
 namespace {
 __device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, RPB_HEAD_AUX));
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
 __device__ __forceinline__ float asf(unsigned u) { return __builtin_bit_cast(float, u); }
 __device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
@@ -72,9 +69,6 @@ __device__ __forceinline__ f32x16v mfma32(bf16x8 a, bf16x8 b, f32x16v c) {
 // products hi*lo + lo*hi + hi*hi on v_mfma_f32_32x32x16_f16 (dropped term <= 2^-22 |a b|); the planes travel in the bf16x8 containers,
 // slot 0 = hi, slot 1 = lo.  W1' carries 2^PH_H2W (fp16's range), undone in the two affine uses of u inside GELU.
 #define PH_H2W 4
-#ifndef RPB_H2_FMAMIX
-#define RPB_H2_FMAMIX 0   /* measured (profiles/r06b_ab.txt): the head +1 % with v_fma_mix_f32, the eval cell_mix launches -1.5 .. -7 % (rpb_cmx.hip keeps 1) */
-#endif
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2w __attribute__((ext_vector_type(2)));
@@ -85,18 +79,9 @@ __device__ __forceinline__ void split8h(const float (&v)[8], bf16x8& h, bf16x8& 
         const f32x2w ab = {v[2 * q], v[2 * q + 1]};
         const f16x2v hh = __builtin_convertvector(ab, f16x2v);                       // v_cvt_pk_f16_f32 (RNE)
         uh[q] = __builtin_bit_cast(unsigned, hh);
-#if RPB_H2_FMAMIX
-        // residual a - float(hi) as ONE v_fma_mix_f32 per value (f16 half * -1 + f32; exact): 4 instead of 5 instructions per value pair
-        // (left alone the compiler converts both halves and subtracts packed: 2 x v_cvt_f32_f16 + v_pk_add_f32)
-        float r0, r1;
-        const unsigned hu = uh[q];
-        const float a0 = ab[0], a1 = ab[1];
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hu), "v"(a0));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hu), "v"(a1));
-        const f32x2w r = {r0, r1};
-#else
-        const f32x2w r = ab - __builtin_convertvector(hh, f32x2w);                   // exact in fp32
-#endif
+        // residual a - float(hi), exact in fp32.  (One v_fma_mix_f32 per value instead, as rpb_cmx.hip does, measured the head 1 % slower:
+        // profiles/r06b_ab.txt)
+        const f32x2w r = ab - __builtin_convertvector(hh, f32x2w);
         const f16x2v ll = __builtin_convertvector(r, f16x2v);
         ul[q] = __builtin_bit_cast(unsigned, ll);
     }
@@ -573,10 +558,8 @@ static size_t pjh_lds(int CW = 64) { return (size_t)((CW / 16) * 4 * 3 * 64) * 1
 // 1 when this kernel takes the shape: C = 64, at most four fc2 outputs, exact-erf GELU, fp32 storage, no GELU inside the input transform
 bool rpb_pjh_supported(int C, int DO, int act, const XForm& xf, bool a_bf16) {
     static const bool off = getenv("RPB_HEAD_PJH") && atoi(getenv("RPB_HEAD_PJH")) == 0;
-    static const bool bf_off = getenv("RPB_HEAD_PJH_BF16") && atoi(getenv("RPB_HEAD_PJH_BF16")) == 0;
-    if (a_bf16 && (bf_off || xf.mean)) return false;     // bf16 storage: plain activations only (the eval cell_mix applied the BatchNorm)
-    static const bool c128_off = getenv("RPB_HEAD_PJH_128") && atoi(getenv("RPB_HEAD_PJH_128")) == 0;
-    if (C == 128) return !off && !c128_off && !a_bf16 && DO >= 1 && DO <= 4 && (act == 0 || act == 1) && !(xf.mean && xf.gelu);
+    if (a_bf16 && xf.mean) return false;     // bf16 storage: plain activations only (the eval cell_mix applied the BatchNorm)
+    if (C == 128) return !off && !a_bf16 && DO >= 1 && DO <= 4 && (act == 0 || act == 1) && !(xf.mean && xf.gelu);
     return !off && C == 64 && DO >= 1 && DO <= 4 && act == 0 && !(xf.mean && xf.gelu);
 }
 

@@ -5,9 +5,6 @@
 #include "rpb_common.h"
 
 #define PW_THREADS 256
-#ifndef RPB_ADAM_NT
-#define RPB_ADAM_NT (RPB_STREAM_AUX == 2)     /* Adam streams 2.8 GB once: nontemporal like the row kernels (rpb_common.h) */
-#endif
 
 static inline int pw_grid(long work_items, int per_cu = 8) {
     long g = (work_items + PW_THREADS - 1) / PW_THREADS;
@@ -143,7 +140,7 @@ static void lift_pad_launch(int grid, size_t lds, hipStream_t st, const float* x
                        cm, out_bf16);
 }
 
-// csrc/rpb_lift_mx.hip: the bf16-output lift at C_in = 16, C = 64 as one MFMA K-step (RPB_LIFT_MX=0 keeps the vector kernel below)
+// csrc/rpb_lift_mx.hip: the bf16-output lift at C_in = 16, C = 64 as one MFMA K-step (other input widths: the vector kernel below)
 bool rpb_lift_mx_supported(int Cin, int C);
 int rpb_lift_mx_launch(const float* x, const float* gt, const float* gh, const float* gw, const float* w0, const float* b0, void* out_bf16,
                        int B, int T, int H, int W, int Tp, int Hp, int Wp, hipStream_t st);
@@ -663,7 +660,7 @@ __global__ __launch_bounds__(PW_THREADS) void adam_kernel(float* __restrict__ p,
                                                           float inv_sqrt_bc2) {
     const long n4 = n >> 2;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n4; idx += (long)gridDim.x * blockDim.x) {
-#if RPB_ADAM_NT     /* nontemporal loads / stores */
+#if RPB_STREAM_AUX == 2     /* Adam streams 2.8 GB once: nontemporal loads / stores like the row kernels (rpb_common.h) */
         f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + idx);
         const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + idx);
         f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + idx);
@@ -680,7 +677,7 @@ __global__ __launch_bounds__(PW_THREADS) void adam_kernel(float* __restrict__ p,
             adam_update(pk, gv[k], mk, vk, gscale, b1, b2, eps, step_size, inv_sqrt_bc2);
             pv[k] = pk, mv[k] = mk, vv[k] = vk;
         }
-#if RPB_ADAM_NT
+#if RPB_STREAM_AUX == 2
         __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + idx);
         __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + idx);
         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + idx);

@@ -20,7 +20,6 @@ TN GEMMs, rpb_afno_mlp mode 1 / rpb_afno_wgrad, rpb_gn_tokens_bwd); there is no 
 exists for state_dict compatibility; its output is discarded by the wrapper (model/dpot.py:224) and never computed here.
 """
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -325,30 +324,21 @@ class DPOT(_ModelBase):
         Wf, Wb, ecos = new(E, T * E), new(T * E, E), new(T, E)
         ops.dpot_tagg_prep(ta.w.data, gamma, pl["tt"], Wf, Wb, ecos, T, E)
         X = new(Mt, E)
-        comp = os.environ.get("RPB_DPOT_COMPOSITE", "1") != "0"
-        Etok = WcT = WsumT = posb = None
-        if comp:
-            # PatchEmbed's second conv, + pos_embed and the TimeAggregator are one linear map of the 35-wide hidden layer: contract the
-            # weights first -- WcT[j][(t, k)] = sum_i (cos(t gamma_i) w[t][i][j]) W2[i][k] (20 small GEMMs), the constant part
-            # (b2 + pos[xy]) sum_t Wb_t -- and the aggregation is ONE token GEMM with K = T * 64 instead of T * E (29x fewer FLOPs on the
-            # largest product of the model; the [B n^2 T][E] token tensor is never materialised).  The layer-0 algebra of the FNO path again.
-            W2pT = W2p.t().contiguous()
-            WcT = new(E, T * E1p)                                              # rows (j, t) of Wf x W2^T: one GEMM, M = E * T
-            ops.gemm_nt(Wf, W2pT, WcT, E * T, E1p, E)
-            ops.gemm_nt(H1, WcT, X, Mt, E, T * E1p)
-            WsumT = new(E, E)                                                  # [j][i] = sum_t Wb[(t, i)][j]
-            ops.reduce_partials_batched(Wf, E, T, E, WsumT)
-            posb = pos + pe2.bias.data                                         # [n^2][E]: parameter-sized
-            PosT = new(n * n, E)
-            ops.gemm_nt(posb, WsumT, PosT, n * n, E, E)
-            ops.rowtable_add(X, PosT, Mt, E, 1, n * n)
-        else:
-            Etok = new(M1, E)
-            ops.gemm_nt(H1, W2p, Etok, M1, E, E1p, bias=pe2.bias.data)
-            ops.rowtable_add(Etok, pos, M1, E, T, n * n)
-            # ---- TimeAggregator: one GEMM over K = (t, channel)
-            ops.gemm_nt(Etok, Wf, X, Mt, E, T * E)
-        if not (comp and training):
+        # PatchEmbed's second conv, + pos_embed and the TimeAggregator are one linear map of the 35-wide hidden layer: contract the
+        # weights first -- WcT[j][(t, k)] = sum_i (cos(t gamma_i) w[t][i][j]) W2[i][k] (20 small GEMMs), the constant part
+        # (b2 + pos[xy]) sum_t Wb_t -- and the aggregation is ONE token GEMM with K = T * 64 instead of T * E (29x fewer FLOPs on the
+        # largest product of the model; the [B n^2 T][E] token tensor is never materialised).  The layer-0 algebra of the FNO path again.
+        W2pT = W2p.t().contiguous()
+        WcT = new(E, T * E1p)                                              # rows (j, t) of Wf x W2^T: one GEMM, M = E * T
+        ops.gemm_nt(Wf, W2pT, WcT, E * T, E1p, E)
+        ops.gemm_nt(H1, WcT, X, Mt, E, T * E1p)
+        WsumT = new(E, E)                                                  # [j][i] = sum_t Wb[(t, i)][j]
+        ops.reduce_partials_batched(Wf, E, T, E, WsumT)
+        posb = pos + pe2.bias.data                                         # [n^2][E]: parameter-sized
+        PosT = new(n * n, E)
+        ops.gemm_nt(posb, WsumT, PosT, n * n, E, E)
+        ops.rowtable_add(X, PosT, Mt, E, 1, n * n)
+        if not training:
             del Wf
         # ---- blocks
         ntok = B * mk * mky
@@ -407,8 +397,8 @@ class DPOT(_ModelBase):
             Ho, Wo = self.shape_out[1:3]
             pred = self._resize_apply(pred.view(B * To, H, W, Cdo), rs["out"]).view(B, To, Ho, Wo, Cdo)
         if training:
-            save.update(B=B, Cd=Cd, P=P, H1=H1, H1pre=H1pre, W2p=W2p, Etok=Etok, Wb=Wb, ecos=ecos, gamma=gamma, tapes=tapes, Xlast=X, Wt=Wt,
-                        comp=comp, WcT=WcT, WsumT=WsumT, posb=posb, Wf=Wf if comp else None,
+            save.update(B=B, Cd=Cd, P=P, H1=H1, H1pre=H1pre, W2p=W2p, Wb=Wb, ecos=ecos, gamma=gamma, tapes=tapes, Xlast=X, Wt=Wt,
+                        WcT=WcT, WsumT=WsumT, posb=posb, Wf=Wf,
                         U=U, Upre=Upre, V=V, Vpre=Vpre, W3p=W3p)
         return pred
 
@@ -461,7 +451,7 @@ class DPOT(_ModelBase):
         wpart = new(splits * nb * 4 * bs * bs)
         # every block ends ~10 partial reductions (weight / bias / norm gradients) that nobody reads before the pass is over: they are
         # queued and run as ONE grouped launch after the loop (68 launches of ~15 us were 1.0 of the 9.8 ms step)
-        defer = ops.deferred_reductions(os.environ.get("RPB_DPOT_DEFER_REDUCE", "1") != "0")
+        defer = ops.deferred_reductions()
         with defer:
             for blk, tp in zip(reversed(list(net.blocks)), reversed(sv["tapes"])):
                 fl, m0, m2 = blk.filter, blk.mlp[0], blk.mlp[2]
@@ -507,44 +497,27 @@ class DPOT(_ModelBase):
         E1p = _rup(E1, 32)
         Kp = (Cm + 3) * ps * ps
         dw, dgamma = torch.empty_like(ta.w), new(E)
-        if sv["comp"]:
-            # adjoint of the contracted map X0 = Hb WcT^T + (b2 + pos) Wsum  (Hb = the hidden layer as [B n^2][T * 64] rows)
-            Hb, W2p, WcT = sv["H1"], sv["W2p"], sv["WcT"]
-            KT = T * E1p
-            GP = new(n * n, E)
-            ops.rowtable_grad(g, GP, B, E, 1, n * n)                            # sum over the samples
-            Wsum = Tr(sv["WsumT"])                                              # [i][j]
-            dposb = new(n * n, E)
-            ops.gemm_nt(GP, Wsum, dposb, n * n, E, E)
-            grads[net.pos_embed] = dposb.view(n, n, E).permute(2, 0, 1).unsqueeze(0).contiguous()
-            grads[pe2.bias] = self._colsum(dposb, n * n, E)
-            dWsum, _ = _wgrad(sv["posb"], GP, n * n, E, E)                      # [i][j]
-            dWcT, _ = _wgrad(g, Hb, Mt, E, KT, ldg=E, lda=KT)                   # [j][(t, k)]
-            gH1 = new(M1, E1p)
-            ops.gemm_nt(g, Tr(WcT), gH1, Mt, KT, E, act=2, aux=sv["H1pre"])      # d hidden pre-activation, rows [B n^2][T * 64]
-            dWf = new(E, T * E)                                                 # [j][(t, i)] = sum_k dWcT[j][(t, k)] W2[i][k]: rows (j, t)
-            ops.gemm_nt(dWcT, W2p, dWf, E * T, E, E1p)
-            dW2p, _ = _wgrad(sv["Wf"], dWcT, E * T, E, E1p, ldg=E, lda=E1p)     # [i][k] = sum_(j,t) Wf[(j,t)][i] dWcT[(j,t)][k]
-            dWb = dWf.view(E, T, E).permute(1, 2, 0).contiguous()               # parameter-sized re-layout to [(t, i)][j]
-            ops.dpot_tagg_finish(dWb, ta.w.data, sv["gamma"], pl["tt"], dw, dgamma, T, E, dWsum=dWsum)
-            del dWb, dWf
-            grads[pe2.weight] = dW2p[:, :E1].reshape(pe2.weight.shape).contiguous()
-        else:
-            Etok = sv["Etok"]
-            dWb, _ = _wgrad(Etok, g, Mt, T * E, E, ldg=T * E, lda=E)                 # [(t,i)][j] = sum_m E[m][(t,i)] g[m][j]
-            ops.dpot_tagg_finish(dWb, ta.w.data, sv["gamma"], pl["tt"], dw, dgamma, T, E)
-            del dWb
-            gE = new(M1, E)
-            ops.gemm_nt(g, sv["Wb"], gE, Mt, T * E, E)
-            # ---- pos_embed, PatchEmbed
-            dpos = new(n * n, E)
-            ops.rowtable_grad(gE, dpos, B, E, T, n * n)
-            grads[net.pos_embed] = dpos.view(n, n, E).permute(2, 0, 1).unsqueeze(0).contiguous()
-            dW2p, dbp2 = _wgrad(gE, sv["H1"], M1, E, E1p)
-            grads[pe2.weight], grads[pe2.bias] = dW2p[:, :E1].reshape(pe2.weight.shape).contiguous(), dbp2
-            gH1 = torch.zeros(M1, E1p, **f)
-            ops.gemm_nt(gE, Tr(sv["W2p"]), gH1, M1, E1, E, act=2, aux=sv["H1pre"], ldo=E1p)
-            del gE
+        # adjoint of the contracted map X0 = Hb WcT^T + (b2 + pos) Wsum  (Hb = the hidden layer as [B n^2][T * 64] rows)
+        Hb, W2p, WcT = sv["H1"], sv["W2p"], sv["WcT"]
+        KT = T * E1p
+        GP = new(n * n, E)
+        ops.rowtable_grad(g, GP, B, E, 1, n * n)                            # sum over the samples
+        Wsum = Tr(sv["WsumT"])                                              # [i][j]
+        dposb = new(n * n, E)
+        ops.gemm_nt(GP, Wsum, dposb, n * n, E, E)
+        grads[net.pos_embed] = dposb.view(n, n, E).permute(2, 0, 1).unsqueeze(0).contiguous()
+        grads[pe2.bias] = self._colsum(dposb, n * n, E)
+        dWsum, _ = _wgrad(sv["posb"], GP, n * n, E, E)                      # [i][j]
+        dWcT, _ = _wgrad(g, Hb, Mt, E, KT, ldg=E, lda=KT)                   # [j][(t, k)]
+        gH1 = new(M1, E1p)
+        ops.gemm_nt(g, Tr(WcT), gH1, Mt, KT, E, act=2, aux=sv["H1pre"])      # d hidden pre-activation, rows [B n^2][T * 64]
+        dWf = new(E, T * E)                                                 # [j][(t, i)] = sum_k dWcT[j][(t, k)] W2[i][k]: rows (j, t)
+        ops.gemm_nt(dWcT, W2p, dWf, E * T, E, E1p)
+        dW2p, _ = _wgrad(sv["Wf"], dWcT, E * T, E, E1p, ldg=E, lda=E1p)     # [i][k] = sum_(j,t) Wf[(j,t)][i] dWcT[(j,t)][k]
+        dWb = dWf.view(E, T, E).permute(1, 2, 0).contiguous()               # parameter-sized re-layout to [(t, i)][j]
+        ops.dpot_tagg_finish(dWb, ta.w.data, sv["gamma"], pl["tt"], dw, dgamma, T, E, dWsum=dWsum)
+        del dWb, dWf
+        grads[pe2.weight] = dW2p[:, :E1].reshape(pe2.weight.shape).contiguous()
         grads[ta.w] = dw
         if self.time_agg == "exp_mlp":
             grads[ta.gamma] = dgamma.view(1, E)

@@ -15,14 +15,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, ops
+from .. import ops
 from ..dft import SpectralPlan, mode_major_to_ref_weights, ref_weights_to_mode_major
 from .model import Model
 
 HID = 128              # fc1 width, fno.py:103
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
-_EVAL_GRAPH = os.environ.get("RPB_EVAL_GRAPH", "0") == "1"      # eval forward replayed from a hipGraph (FNO3d._forward_graphed)
 _ALIGN = 64            # floats: every parameter segment starts on a 256 B boundary
 
 
@@ -35,8 +34,6 @@ class _Workspace:
         self.bf16 = (not training) and model.storage == "bf16"       # eval / rollout only: activations stored as bf16
         # eval / rollout on fp32 storage only: the opt-in two-fp16-plane arithmetic of the fused eval launches (FNO3d.set_arith)
         self.arith = model.arith if (not training and not self.bf16) else "f32"
-        self.graph = self.graph_out = self.graph_x = self.graph_key = None      # eval: hipGraph of one forward (FNO3d._forward_graphed)
-        self.graph_calls = 0
         self.generation = 0          # bumped by every training-mode forward: a backward whose graph saw an older value must not run
         C, L, plan = model.width, model.n_layers, model.plan
         f = dict(device=device, dtype=torch.float32)
@@ -46,7 +43,6 @@ class _Workspace:
         # layer 0 entirely on the feature fields (csrc/rpb_feat.hip): the 64-channel lifted tensor A0 is never materialised
         self.FW = 8 if model.dim_in + 4 <= 8 else 32
         self.featfull = (type(model)._lift_fwd is FNO3d._lift_fwd and C == 64 and not self.bf16 and model.dim_in + 4 <= 32
-                         and os.environ.get("RPB_LAYER0_GENERIC") != "1" and os.environ.get("RPB_LAYER0_A0") != "1"
                          and ops.cell_mix_writes_gz(d.ncell, C, C, 2 * plan.KW, d.Wp, True))
         self.A0 = None if self.featfull else torch.empty(d.ncell, C, **fa)
         if self.featfull:
@@ -61,9 +57,8 @@ class _Workspace:
         self.fuse_w = (not training and C == 64 and os.environ.get("RPB_EVAL_FUSE_W", "1") != "0"
                        and ops.cell_mix_eval_dft_supported(d.ncell, 2 * plan.KW, d.Wp, 2 * plan.KW))
         # bf16 storage (BASELINE.json configs[4]), round 4: the spectral intermediates that are as large as the bf16 activations -- the
-        # fused W stage's rows Y1f and the inverse H stage's rows z2 -- are stored as bf16 as well (RPB_BF16_SPECTRA=0: fp32 as in round 3)
-        self.spec_bf16 = (self.bf16 and self.fuse_w and os.environ.get("RPB_BF16_SPECTRA", "1") != "0"
-                          and 2 * plan.KH <= 64 and 2 * d.Hp > 64 and (plan.KW * C) % 64 == 0)
+        # fused W stage's rows Y1f and the inverse H stage's rows z2 -- are stored as bf16 as well
+        self.spec_bf16 = (self.bf16 and self.fuse_w and 2 * plan.KH <= 64 and 2 * d.Hp > 64 and (plan.KW * C) % 64 == 0)
         self.Y1f = (torch.empty(G1 * N1, device=device, dtype=torch.bfloat16 if self.spec_bf16 else torch.float32)
                     if self.fuse_w else None)
         self.Z2 = torch.empty(G1 * N1, device=device, dtype=torch.bfloat16) if self.spec_bf16 else self.Y1
@@ -84,7 +79,7 @@ class _Workspace:
         self.out = torch.empty(d.ncrop, model.dim_out, **f)
         # layer-0 algebra (csrc/rpb_feat.hip): the first spectral layer transforms the Cin + 4 feature FIELDS instead of the 64
         # lifted channels; in training its data gradient is never formed (only fc0's 64 x (Cin + 4) gradient is needed)
-        self.feat0 = (type(model)._lift_fwd is FNO3d._lift_fwd and C == 64 and os.environ.get("RPB_LAYER0_GENERIC") != "1")
+        self.feat0 = type(model)._lift_fwd is FNO3d._lift_fwd and C == 64
         if self.feat0:
             T_, H_, W_, Cin = d.T, d.H, d.W, model.dim_in
             self.NB = (B * Cin + 4 + 63) // 64 * 64
@@ -109,34 +104,25 @@ class _Workspace:
                 self.dconv = torch.empty(C * (Cin + 4), **f)
         if training:
             self.G = [torch.empty(d.ncell, C, **f) for _ in range(2)]
-            # projection-head backward: bf16-pipe kernels that recompute gh (no gu tensor) when the shape allows, else the
-            # round-1 chain through gu
-            # projection-head backward (csrc/rpb_pjx.hip): "gu" (default where supported) = round-1 proj_bwd + cell_wgrad with the
-            # fc1 dgrad on the bf16 pipe reading gu; "recompute" (RPB_PROJ_RECOMPUTE=1) = no gu tensor at all, both kernels rebuild
-            # gh -- measured slower (act' on 128 hidden units per cell twice); None = the round-1 chain
-            ok = (C == 64 and type(model)._lift_fwd is FNO3d._lift_fwd and ops.proj_bwd_fused_supported(C, model.dim_out, d.W, d.Wp))
-            self.proj_mode = None if not ok else ("recompute" if os.environ.get("RPB_PROJ_RECOMPUTE") == "1" else "gu")
-            self.proj_fused = self.proj_mode == "recompute"
-            # round 3: the whole head backward in one pass, gh never in HBM (csrc/rpb_pjf.hip); RPB_HEAD_BWD_FUSED=0 restores the chain
+            # projection-head backward where the one-pass head below is not supported: round-1 proj_bwd + cell_wgrad through gu, with
+            # the fc1 dgrad on the bf16 pipe reading gu where the shape allows (csrc/rpb_pjx.hip), else the round-1 gather.  (Rebuilding
+            # gh in the dgrad and wgrad kernels instead of storing gu measured slower: act' on 128 hidden units per cell twice.)
+            self.proj_gu = (C == 64 and type(model)._lift_fwd is FNO3d._lift_fwd
+                            and ops.proj_bwd_fused_supported(C, model.dim_out, d.W, d.Wp))
+            # round 3: the whole head backward in one pass, gh never in HBM (csrc/rpb_pjf.hip)
             self.head_fused = (C == 64 and type(model)._lift_fwd is FNO3d._lift_fwd and
                                ops.head_bwd_supported(C, model.dim_out, d.W, d.Wp, False, model.proj_act))
-            if self.head_fused:
-                self.proj_fused = False
-            self.gu = None if (self.proj_fused or self.head_fused) else torch.empty(d.ncrop, HID, **f)
-            if ok:
+            self.gu = None if self.head_fused else torch.empty(d.ncrop, HID, **f)
+            if self.proj_gu:
                 self.pd_slots = ops.proj_dgrad_slots(d)
             if self.head_fused:
                 self.hb_slots, self.hb_row = ops.head_bwd_slots(d), ops.head_bwd_row(model.dim_out)
                 self.hb_part = torch.empty(self.hb_slots * self.hb_row, **f)
                 self.hb_tot = torch.empty(self.hb_row, **f)
                 self.hb_loss_part = torch.empty(self.hb_slots, **f)
-                # fused trainer: the head's forward + loss ride in the backward launch (RPB_HEAD_LOSS_FUSED=0: proj_fwd + mse + head_bwd)
+                # fused trainer: the head's forward + loss ride in the backward launch
                 # (fc2 widths 3-4: the fused variant keeps 32 more accumulators and spills -- measured slower at the cylinder's native C = 3)
-                self.head_loss_fused = os.environ.get("RPB_HEAD_LOSS_FUSED", "1") != "0" and model.dim_out <= 2
-            if self.proj_fused:
-                self.pw_slots, self.pw_row, self.pw_roles = ops.proj_wgrad_slots(d), ops.proj_wgrad_row(model.dim_out), ops.proj_wgrad_roles()
-                self.pw_part = torch.empty(self.pw_slots * self.pw_row, **f)
-                self.pw_sum = torch.empty(self.pw_roles * self.pw_row, **f)
+                self.head_loss_fused = model.dim_out <= 2
             # BatchNorm-backward sums are produced by the kernels that write the gradient (cell_mix STATS=2)
             self.bnb_rows_gather = ops.cell_mix_stat_rows(d.ncell, HID, C, 0, 1, False, True)
             self.bnb_rows_conv = ops.cell_mix_stat_rows(d.ncell, C, C, 2 * plan.KW, d.Wp, True, True)
@@ -144,10 +130,9 @@ class _Workspace:
             self.bn_sums = torch.empty(2 * C, **f)
             # width 128 (configs/fsi/fno.yaml, the Galerkin regressor): the fp32-MFMA cell_mix with the BatchNorm-backward sums in its
             # epilogue spills (8.6 ms at the fsi shape against 2.5 ms without the sums: tools/fsi_probe.py); the plain launch plus the
-            # streaming reduction over (s, g) is 3.3 ms.  RPB_BNB_FUSED_128=1 restores the fused launch.
+            # streaming reduction over (s, g) is 3.3 ms.
             # The bf16-pipe instance at C = 128 (csrc/rpb_cmx.hip, output halves) carries the sums again.
-            self.bnb_unfused = (C == 128 and os.environ.get("RPB_BNB_FUSED_128") != "1"
-                                and not ops.cell_mix_writes_gz(d.ncell, C, C, 2 * plan.KW, d.Wp, True))
+            self.bnb_unfused = (C == 128 and not ops.cell_mix_writes_gz(d.ncell, C, C, 2 * plan.KW, d.Wp, True))
             if self.bnb_unfused:
                 self.bnr_rows = ops.bn_bwd_rows()
                 self.bnr_part = torch.empty(self.bnr_rows * 2 * C, **f)
@@ -155,9 +140,8 @@ class _Workspace:
             self.proj_part = torch.empty(self.proj_rows * (model.dim_out * HID + HID + model.dim_out), **f)
             self.fused_bwd = C <= 64             # rpb_bn_bwd_row: BN-backward apply + adjoint W stage + conv wgrad in one pass
             # width 128: BN-backward apply + adjoint W stage in one pass as two 64-channel half launches of the C = 64 row kernel
-            # (rpb_bn_bwd_row_c128; the weight gradient stays with rpb_cell_wgrad).  RPB_BWD_ROW_128=0: bn_bwd_apply + axis_gemm.
-            self.row128 = (C == 128 and os.environ.get("RPB_BWD_ROW_128", "1") != "0"
-                           and ops.bn_bwd_row_c128_supported(d.Wp, 2 * plan.KW))
+            # (rpb_bn_bwd_row_c128; the weight gradient stays with rpb_cell_wgrad); else bn_bwd_apply + axis_gemm.
+            self.row128 = C == 128 and ops.bn_bwd_row_c128_supported(d.Wp, 2 * plan.KW)
             if self.row128:
                 self.row128_part = torch.empty(2 * ops.bn_bwd_row_slots(B * d.Tp * d.Hp) * (64 * 64 + 64), **f)
             self.wg_rows_c = (ops.bn_bwd_row_slots(B * d.Tp * d.Hp) if self.fused_bwd
@@ -395,7 +379,7 @@ class FNO3d(Model):
             raise NotImplementedError("the f16x2 eval arithmetic is built for FNO3d at width 64 with modes3 <= 16")
         if arith != self.arith:
             self.arith = arith
-            self._ws = {k: v for k, v in self._ws.items() if k[1]}       # drop the eval workspaces (their graphs hold the old launches)
+            self._ws = {k: v for k, v in self._ws.items() if k[1]}       # drop the eval workspaces (they hold the old arithmetic)
         return self
 
     # ------------------------------------------------------------------ device-side constants
@@ -588,24 +572,6 @@ class FNO3d(Model):
                                   GP("fc2.bias"), ws.bn_sums)
             if self.dp is not None:
                 self.dp.bucket_ready(gflat)                      # fc1 / fc2 gradients are final: start their all-reduce
-        elif ws.proj_fused:
-            # bf16 matrix pipe, no gu tensor: each kernel recomputes gh = (fc2^T gout) * act'(fc1 a + b1) in the operand
-            # orientation it needs (csrc/rpb_pjx.hip).  wgrad first: its partials feed the first all-reduce bucket
-            w1, b1, w2 = P("fc1.weight"), P("fc1.bias"), P("fc2.weight")
-            ops.proj_wgrad(a_last, w1, b1, w2, gout, ws.pw_part, d, DO, xf_last, act=self.proj_act)
-            roles, row = ws.pw_roles, ws.pw_row
-            HB = HID // roles
-            # slot = k * roles + role: one reduction over k leaves [role][row]; the four blocks then move into the arena
-            ops.reduce_partials(ws.pw_part, ws.pw_slots // roles, roles * row, out_f32=ws.pw_sum)
-            tot = ws.pw_sum.view(roles, row)
-            GP("fc1.weight").view(roles, HB * C).copy_(tot[:, :HB * C])
-            GP("fc2.weight").view(DO, roles, HB).copy_(tot[:, HB * C:HB * C + DO * HB].view(roles, DO, HB).permute(1, 0, 2))
-            GP("fc1.bias").view(roles, HB).copy_(tot[:, HB * C + DO * HB:HB * C + DO * HB + HB])
-            GP("fc2.bias").copy_(tot[0, HB * C + DO * HB + HB:])
-            if self.dp is not None:
-                self.dp.bucket_ready(gflat)                      # fc1 / fc2 gradients are final: start their all-reduce
-            ops.proj_dgrad(a_last, w1, b1, w2, gout, g, ws.bn_part, d, DO, xf_last, act=self.proj_act)
-            ops.reduce_partials(ws.bn_part, ws.pd_slots, 2 * C, out_f32=ws.bn_sums)
         else:
             ops.proj_bwd(a_last, P("fc1.weight"), P("fc1.bias"), P("fc2.weight"), P("fc2.bias"), gout, ws.gu,
                          ws.proj_part, d, DO, xf=xf_last, act=self.proj_act)
@@ -622,22 +588,9 @@ class FNO3d(Model):
                 self.dp.bucket_ready(gflat)                      # fc1 / fc2 gradients are final: start their all-reduce
             # fc1 dgrad scattered into the padded layout; its epilogue also accumulates the BatchNorm-backward sums
             # (sum gz, sum gz*shat) of the last Fourier layer, so no separate reduction pass reads g again
-            if ws.proj_mode == "gu":           # bf16 matrix pipe, 16 B stores, line-persistent waves (csrc/rpb_pjx.hip)
-                ops.proj_dgrad(a_last, P("fc1.weight"), P("fc1.bias"), P("fc2.weight"), None, g, ws.bn_part, d, DO, xf_last,
-                               act=self.proj_act, gu=ws.gu)
+            if ws.proj_gu:                     # bf16 matrix pipe, 16 B stores, line-persistent waves (csrc/rpb_pjx.hip)
+                ops.proj_dgrad(a_last, P("fc1.weight"), ws.gu, g, ws.bn_part, d, DO, xf_last)
                 ops.reduce_partials(ws.bn_part, ws.pd_slots, 2 * C, out_f32=ws.bn_sums)
-            elif C == 128 and os.environ.get("RPB_GATHER_BNB_FUSED_128", "1") == "0":
-                # width 128, rounds 5-6a: the fp32 gather instance with the BatchNorm-backward sums in its epilogue spilled (3.2 ms at the
-                # fsi shape), so the plain gather + a streaming reduction over (s, g) ran instead.  Round 6b: the gather is csrc/rpb_pjh.hip's
-                # matrix-pipe kernel and carries the sums (MODE 3) -- the branch below; RPB_GATHER_BNB_FUSED_128=0 keeps the two launches
-                ops.cell_mix(ws.gu, P("fc1.weight"), None, None, None, g, None, d.ncell, HID, C, 0, 1, transpose_w=True,
-                             gather=True, crop6=d.crop6)
-                xfb = self._layer_xf(ws, L - 1, True)
-                if not hasattr(ws, "bnr_part"):
-                    ws.bnr_rows = ops.bn_bwd_rows()
-                    ws.bnr_part = torch.empty(ws.bnr_rows * 2 * C, device=g.device, dtype=torch.float32)
-                ops.bn_bwd_reduce(ws.S[L - 1], g, xfb[0], xfb[1], xfb[2], xfb[3], ws.bnr_part, d.ncell, C, xfb[4])
-                ops.reduce_partials(ws.bnr_part, ws.bnr_rows, 2 * C, out_f32=ws.bn_sums)
             else:
                 ops.cell_mix(ws.gu, P("fc1.weight"), None, None, None, g, ws.bn_part, d.ncell, HID, C, 0, 1, transpose_w=True,
                              gather=True, crop6=d.crop6, bnb=(ws.S[L - 1],) + self._layer_xf(ws, L - 1, True))
@@ -828,38 +781,9 @@ class FNO3d(Model):
             return _FNO3dFunction.apply(x, self.flat, self)
         ws = self._workspace(x.shape[0], self.training, x.device)
         if not self.training:
-            self._params_settled()      # a replayed eval graph never enters _forward_impl, where the per-bucket waits live
-        if not self.training and _EVAL_GRAPH and _lib.PROFILE is None and type(self)._forward_impl is FNO3d._forward_impl:
-            out = self._forward_graphed(x, ws)
-        else:
-            out = self._forward_impl(x, ws, training=self.training)
+            self._params_settled()
+        out = self._forward_impl(x, ws, training=self.training)
         return self._shape_output(out.clone(), x.shape[0])
-
-    def _forward_graphed(self, x, ws):
-        """Eval forward replayed from a hipGraph (the ~40 launches of one forward, 20-200 us each on the small spectral stages, leave
-        the host out of the loop: eval.py:314-319 calls this forward back to back).  The graph is captured on the third call with a
-        given workspace (the first two run eagerly: lazy allocations, function attributes) and reads the input through a fixed
-        staging buffer; it is dropped whenever a pointer it baked in (parameter arena, BatchNorm buffers) changes."""
-        key = (self.flat.data_ptr(), self.bn_running_mean.data_ptr(), self.bn_running_var.data_ptr(), torch.cuda.current_device())
-        if ws.graph is not None and ws.graph_key != key:
-            ws.graph = ws.graph_out = None
-            ws.graph_calls = 0
-        if ws.graph is None:
-            ws.graph_calls += 1
-            if ws.graph_calls < 3:
-                return self._forward_impl(x, ws, training=False)
-            if ws.graph_x is None:
-                ws.graph_x = torch.empty_like(x)
-            ws.graph_x.copy_(x)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                ws.graph_out = self._forward_impl(ws.graph_x, ws, training=False)
-            ws.graph, ws.graph_key = g, key
-        else:
-            ws.graph_x.copy_(x)
-        ws.graph.replay()
-        return ws.graph_out
 
     def train_loss(self, input, target):
         """fno.py:131-133: elementwise ``mse_loss(pred, target)`` (callers take ``.mean()``)."""

@@ -473,13 +473,11 @@ GEMM_SPLIT_WIDE_N = 8192               # ... unless the output is wide enough to
                                        # gradient, M = 4096, N = 20480: 167 vs 124 TF/s; its N = 1024 GEMMs: 83-108 vs 93-118, stay fp32)
 # K <= 256, N <= 256 with an epilogue that reads or writes a second [M][N] tensor: the exact-fp32 kernel is faster (2.6 M rows, GELU +
 # residual: 3.43 vs 4.12 ms; plain: 3.14 vs 2.49 -- DESIGN.md section 9)
-GEMM_F32_SHORT_HEAVY = os.environ.get("RPB_GEMM_F32_SHORT_HEAVY", "1") != "0"
-GEMM3X_V2 = os.environ.get("RPB_GEMM3X_V2", "1") != "0"
 GEMM3X_V2_MIN_ROWS = 4096
 GEMM_SPLIT_MIN_ROWS = 65536           # below this the GEMM is launch-bound and the weight preparation does not pay
 
 
-GEMM_SPLIT_MIN_K = int(os.environ.get("RPB_GEMM_SPLIT_MIN_K", 256))                # K = 256 (4 LDS stages per 128-row tile): 110-117 vs 104-108 TF/s, larger K 145-160 vs 120-125;
+GEMM_SPLIT_MIN_K = 256                # K = 256 (4 LDS stages per 128-row tile): 110-117 vs 104-108 TF/s, larger K 145-160 vs 120-125;
 GEMM_SPLIT_MIN_N = 256                # the K-split tiles of N = 64 / 128 lose to the fp32 kernel (64 vs 96 TF/s)
 
 
@@ -510,8 +508,8 @@ def gemm_nt(A, W, out, M, N, K, bias=None, addvec=None, residual=None, act=0, ld
     heavy_epilogue = residual is not None or aux is not None or mask is not None or pre_out is not None
     # rpb_gemm3x's 64-row-tile variant (csrc/rpb_gemm3x2.hip: N % 256 == 0 without a mask tensor, N % 128 == 0 without dropout) hides
     # the epilogue; only the 128-row kernel loses to the fp32 one on short products with a heavy epilogue
-    v2 = GEMM3X_V2 and mask is None and (N % 256 == 0 or (N % 128 == 0 and not drop))
-    if gemm_split_ok(M, N, K, lda, ldo, conv, v2) and not (GEMM_F32_SHORT_HEAVY and K <= 256 and N <= 256 and heavy_epilogue and not v2):
+    v2 = mask is None and (N % 256 == 0 or (N % 128 == 0 and not drop))
+    if gemm_split_ok(M, N, K, lda, ldo, conv, v2) and not (K <= 256 and N <= 256 and heavy_epilogue and not v2):
         wsrc = W.t if isinstance(W, Sub) else W
         wz = torch.empty(3 * N * K, dtype=torch.int16, device=wsrc.device)
         _lib.call("rpb_gemm3x_wprep", _p(W), _p(wz, torch.int16), N, K, _stream(), label="gemm3x_wprep", nbytes=10 * N * K)
@@ -924,31 +922,10 @@ def proj_dgrad_slots(d):
     return _lib.query("rpb_proj_dgrad_slots", d.B, d.Tp, d.Hp)
 
 
-def proj_dgrad(s, w1, b1, w2, gout, g, stats_part, d, DO, xf, act=0, gu=None):
-    """g [ncell][64] (padded layout) = fc1^T gh, gh = (fc2^T gout) * act'(fc1 a + b1) recomputed (a = xf(s) cropped) or read from
-    ``gu`` [ncrop][128]; stats_part = BN-backward sums."""
-    _lib.call("rpb_proj_dgrad", _p(s), _p(w1), _p(b1), _p(w2), _p(gout), _p(gu), _p(g), _p(stats_part), d.B, DO, *d.crop6,
-              *_xf(xf), int(act), _stream(), label="proj_dgrad[gu]" if gu is not None else "proj_dgrad[recompute]",
-              nbytes=4 * (d.ncrop * (d.C + (128 if gu is not None else DO)) + d.ncell * d.C),
-              flops=2 * d.ncrop * 128 * (d.C if gu is not None else 2 * d.C))
-
-
-def proj_wgrad_slots(d):
-    return _lib.query("rpb_proj_wgrad_slots", d.B, d.T, d.H)
-
-
-def proj_wgrad_row(DO):
-    return _lib.query("rpb_proj_wgrad_row", DO)
-
-
-def proj_wgrad_roles():
-    return _lib.query("rpb_proj_wgrad_roles")
-
-
-def proj_wgrad(s, w1, b1, w2, gout, part, d, DO, xf, act=0):
-    """Per-wave partial rows of d fc1.weight / d fc2.weight / d fc1.bias / d fc2.bias (layout: include/rpb.h)."""
-    _lib.call("rpb_proj_wgrad", _p(s), _p(w1), _p(b1), _p(w2), _p(gout), _p(part), d.B, DO, *d.crop6, *_xf(xf), int(act),
-              _stream(), label="proj_wgrad", nbytes=4 * d.ncrop * (d.C + DO), flops=2 * d.ncrop * 128 * 2 * d.C)
+def proj_dgrad(s, w1, gu, g, stats_part, d, DO, xf):
+    """g [ncell][64] (padded layout) = fc1^T gh, gh read from ``gu`` [ncrop][128] (a = xf(s) cropped); stats_part = BN-backward sums."""
+    _lib.call("rpb_proj_dgrad", _p(s), _p(w1), _p(gu), _p(g), _p(stats_part), d.B, DO, *d.crop6, *_xf(xf), _stream(),
+              label="proj_dgrad[gu]", nbytes=4 * (d.ncrop * (d.C + 128) + d.ncell * d.C), flops=2 * d.ncrop * 128 * d.C)
 
 
 def stream_probe(a, b, c, out, nread, threads=256):

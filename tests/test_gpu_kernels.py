@@ -584,7 +584,7 @@ def test_cell_mix_line_claim_modes_agree(ops, C, Wp, rows):
 @pytest.mark.parametrize("Wp,rows,K2", [(134, 9, 32), (70, 11, 32), (38, 5, 24), (33, 3, 7), (134, 1, 32)])
 @pytest.mark.parametrize("gelu,write_gz", [(True, True), (True, False), (False, False)])
 def test_cell_mix_with_the_conv_weight_gradient(ops, Wp, rows, K2, gelu, write_gz):
-    """rpb_cell_mix_wgrad (csrc/rpb_cmw.hip) == the STATS = 2 backward cell_mix + d convs.weight = gs^T act(BN(s_prev)), each stated in
+    """rpb_cell_mix_wgrad (the wave pairs of csrc/rpb_cmx.hip) == the STATS = 2 backward cell_mix + d convs.weight = gs^T act(BN(s_prev)), each stated in
     fp64: rows that end inside a tile (Wp % 32 != 0), fewer lines than waves, weights that are far from symmetric (transpose-detecting)."""
     torch.manual_seed(Wp * 11 + K2 + int(gelu))
     C = 64
@@ -816,16 +816,14 @@ def test_lift_bf16_wide_input_on_the_matrix_pipe(ops, T, H, W, pad, monkeypatch)
     v = a16.view(B, d.Tp, d.Hp, d.Wp, C)
     assert float(v[:, T:].abs().max() if pad else 0) == 0 and float(v[:, :, H:].abs().max()) == 0 and float(v[:, :, :, W:].abs().max()) == 0
     assert float(v[:, :T, :H, :W].abs().min()) > 0
-    # the vector kernel stays reachable (and is the bit-exact rounding of the fp32 lift)
-    # (RPB_LIFT_MX is read once per process: checked in a child process by tools, not here)
 
 
 @pytest.mark.parametrize("B,T,H,W,pad,DO,gelu,act", [(2, 3, 5, 32, 2, 2, False, 0), (1, 2, 4, 48, 3, 1, False, 0),
                                                       (1, 2, 3, 40, 6, 3, True, 1)])
-def test_projection_backward_without_gu(ops, B, T, H, W, pad, DO, gelu, act):
-    """rpb_proj_dgrad / rpb_proj_wgrad (bf16 matrix pipe, gh recomputed, never stored) against fp64 autograd of
-    fno.py:121-125 on the cropped cells: gradient w.r.t. the padded layer output (zeros in the margin), the BatchNorm-backward
-    sums, and the four parameter gradients; row lengths that are not a multiple of the 32-cell wave tile included."""
+def test_projection_dgrad_from_gu(ops, B, T, H, W, pad, DO, gelu, act):
+    """rpb_proj_dgrad (bf16 matrix pipe, gh read from gu as rpb_proj_bwd writes it) against fp64 autograd of fno.py:121-125 on the
+    cropped cells: gradient w.r.t. the padded layer output (zeros in the margin) and the BatchNorm-backward sums; row lengths that are not
+    a multiple of the 32-cell wave tile included."""
     torch.manual_seed(B * 100 + W)
     C = 64
     d = ops.Dims(B, T, H, W, 2, C, pad)
@@ -853,32 +851,14 @@ def test_projection_backward_without_gu(ops, B, T, H, W, pad, DO, gelu, act):
     g = torch.full((d.ncell, C), float("nan"), device="cuda")
     rows = ops.proj_dgrad_slots(d)
     part = torch.zeros(rows, 2, C, device="cuda")
-    args = (S, dev(w1.detach()), dev(b1.detach()), dev(w2.detach()), dev(gout))
-    ops.proj_dgrad(*args, g, part, d, DO, xf, act=act)
-    assert rel_l2(g.cpu(), g_ref) < 3e-6
-    tot = part.double().sum(0).cpu()
-    assert rel_l2(tot[0], g_ref.sum(0)) < 2e-5 and rel_l2(tot[1], (g_ref * sh.detach()).sum(0)) < 2e-5
-    # the same dgrad reading gh from HBM (the default path: rpb_proj_bwd writes it, cell_wgrad reads it too)
+    # gh as rpb_proj_bwd writes it (the default path: cell_wgrad reads it too)
     u2 = (a.detach() @ w1.detach().t() + b1.detach()).requires_grad_(True)
     v2 = torch.nn.functional.silu(u2) if act == 1 else torch.nn.functional.gelu(u2)
     (v2 @ w2.detach().t()).backward(gout)
-    g.fill_(float("nan"))
-    part.zero_()
-    ops.proj_dgrad(S, dev(w1.detach()), dev(b1.detach()), dev(w2.detach()), None, g, part, d, DO, xf, act=act, gu=dev(u2.grad))
+    ops.proj_dgrad(S, dev(w1.detach()), dev(u2.grad), g, part, d, DO, xf)
     assert rel_l2(g.cpu(), g_ref) < 3e-6
     tot = part.double().sum(0).cpu()
     assert rel_l2(tot[0], g_ref.sum(0)) < 2e-5 and rel_l2(tot[1], (g_ref * sh.detach()).sum(0)) < 2e-5
-    slots, row, roles = ops.proj_wgrad_slots(d), ops.proj_wgrad_row(DO), ops.proj_wgrad_roles()
-    HB = 128 // roles
-    wp = torch.full((slots, row), float("nan"), device="cuda")
-    ops.proj_wgrad(*args, wp, d, DO, xf, act=act)
-    tot = wp.double().view(slots // roles, roles, row).sum(0).cpu()           # [role][row]
-    dw1 = tot[:, :HB * 64].reshape(128, 64)
-    dw2 = tot[:, HB * 64:HB * 64 + DO * HB].reshape(roles, DO, HB).permute(1, 0, 2).reshape(DO, 128)
-    db1 = tot[:, HB * 64 + DO * HB:HB * 64 + DO * HB + HB].reshape(128)
-    db2 = tot[:, HB * 64 + DO * HB + HB:].sum(0)
-    assert rel_l2(dw1, w1.grad) < 5e-6 and rel_l2(dw2, w2.grad) < 5e-6
-    assert rel_l2(db1, b1.grad) < 5e-6 and rel_l2(db2, b2.grad) < 5e-6
 
 
 @pytest.mark.parametrize("B,T,H,W,pad,DO", [(2, 3, 5, 32, 2, 2), (1, 2, 4, 48, 3, 1), (1, 2, 3, 40, 6, 3), (2, 2, 3, 128, 6, 2),
