@@ -3,7 +3,7 @@
 //   out[g][o][n] = sum_k M[o][k] * in[g][k][n]        n contiguous, k / o strided, g = batch
 //
 // (every stage of rfftn / irfftn of fno.py:48,63 and their adjoints) with both operands split into three bf16 planes and the
-// products on v_mfma_f32_16x16x32_bf16 -- the fp32-grade arithmetic of rpb_cmx.hip / rpb_conv3x.hip (hi*lo + lo*hi + mid*mid +
+// products on v_mfma_f32_16x16x32_bf16 -- the fp32-grade arithmetic of rpb_mma.h (hi*lo + lo*hi + mid*mid +
 // hi*mid + mid*hi + hi*hi, fp32 accumulate; Rel-L2 vs fp64 ~2e-7).
 //
 // Why: as fp32 MFMA the H stages are matrix-pipe-bound (832 x 32 x 2 x 134 MFMAs of 64 cycles = 0.30 ms of pipe time for a
@@ -14,65 +14,10 @@
 // store is 16 B per lane / 256 B per row as well.  The matrix is split once per workgroup into LDS in A-operand order
 // (16-row tiles: O = 48 is exact).
 #include "rpb_axg.h"
+#include "rpb_mma.h"
 // (cache policy of the streaming loads / stores: RPB_STREAM_AUX, rpb_common.h -- nt by default since round 5)
 #include <stdlib.h>
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-namespace {
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, RPB_STREAM_AUX));
-}
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, RPB_STREAM_AUX);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-// the same with only the first `npairs` element pairs live (wave-uniform): the rest are zero planes at no vector cost
-__device__ __forceinline__ void split8n(const float (&v)[8], int npairs, bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh = {0u, 0u, 0u, 0u}, um = uh, ul = uh;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q >= npairs) break;
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-}  // namespace
 
 #define AXG_WAVES 8
 
@@ -159,11 +104,11 @@ __global__ __launch_bounds__(NW * 64) void axg_kernel(AxgArgs a) {
         }
         for (int p = 0; p < passes; ++p) {
             asm volatile("" ::: "memory");
-            f32x4v acc[MT][4];
+            f32x4 acc[MT][4];
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc[i][t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
             u32x4 zr[8];
             auto issue = [&](int ks) {
                 const bool tail = !BFIN && ks == KS - 1;
@@ -175,9 +120,9 @@ __global__ __launch_bounds__(NW * 64) void axg_kernel(AxgArgs a) {
                         zr[e][0] = w[0];
                         zr[e][1] = w[1];
                     } else if (!tail) {
-                        zr[e] = ld16(ri, ioff + (32 * ks + e) * istep);
+                        zr[e] = ld16<RPB_STREAM_AUX>(ri, ioff + (32 * ks + e) * istep);
                     } else if (e < epl) {                                     // (uniform) rows past epl are not even requested
-                        zr[e] = ld16(ri, ioff_tail + (32 * ks + e) * istep);
+                        zr[e] = ld16<RPB_STREAM_AUX>(ri, ioff_tail + (32 * ks + e) * istep);
                     }
                 }
             };
@@ -210,7 +155,7 @@ __global__ __launch_bounds__(NW * 64) void axg_kernel(AxgArgs a) {
                                 for (int t = 0; t < 4; ++t) v[t][e] = 0.f;
                                 continue;
                             }
-                            const f32x4v x4 = __builtin_bit_cast(f32x4v, zr[e]);
+                            const f32x4 x4 = __builtin_bit_cast(f32x4, zr[e]);
                             // channel pairs: packed fp32 math; the two pairs' erf polynomials in lock-step (rpb_common.h, gelu2x2)
                             f32x2 xa = f32x2{x4[0], x4[1]}, xb = f32x2{x4[2], x4[3]};
                             if (XF) {
@@ -280,10 +225,10 @@ __global__ __launch_bounds__(NW * 64) void axg_kernel(AxgArgs a) {
                 if (mt >= mtiles) break;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    f32x4v o;
+                    f32x4 o;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) o[t] = acc[i][t][r];
-                    st16(o, ro, ooff + (16 * mt + r) * (int)a.out_o * 4);
+                    st16<RPB_STREAM_AUX>(o, ro, ooff + (16 * mt + r) * (int)a.out_o * 4);
                 }
             }
         }
@@ -336,7 +281,7 @@ __global__ __launch_bounds__(AXG_WAVES * 64) void axg_resident_kernel(AxgArgs a)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) zr[ks][e] = ld16(ri, ioff + (32 * ks + e) * (int)a.in_k * 4);   // ks >= KS: out of range -> 0
+            for (int e = 0; e < 8; ++e) zr[ks][e] = ld16<RPB_STREAM_AUX>(ri, ioff + (32 * ks + e) * (int)a.in_k * 4);   // ks >= KS: out of range -> 0
     };
     long it = (long)blockIdx.x * AXG_WAVES + wave;
     if (it < items) issue(it);
@@ -351,17 +296,17 @@ __global__ __launch_bounds__(AXG_WAVES * 64) void axg_resident_kernel(AxgArgs a)
             for (int t = 0; t < 4; ++t) {
                 float v[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(f32x4v, zr[ks][e])[t];
+                for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(f32x4, zr[ks][e])[t];
                 split8(v, Bh[ks][t], Bm[ks][t], Bl[ks][t]);
             }
         if (it + nslots < items) issue(it + nslots);            // the next item's input is in flight during all passes below
         for (int p = 0; p < passes; ++p) {
             asm volatile("" ::: "memory");
-            f32x4v acc[MT][4];
+            f32x4 acc[MT][4];
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc[i][t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+                for (int t = 0; t < 4; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 if (ks >= KS) break;
@@ -392,7 +337,7 @@ __global__ __launch_bounds__(AXG_WAVES * 64) void axg_resident_kernel(AxgArgs a)
                 if (mt >= mtiles) break;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    f32x4v o;
+                    f32x4 o;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) o[t] = acc[i][t][r];
                     if (a.out_bf16) {       // spectra stored as bf16 (round to nearest even): 8 B per lane, 128 B per row and strip
@@ -404,7 +349,7 @@ __global__ __launch_bounds__(AXG_WAVES * 64) void axg_resident_kernel(AxgArgs a)
                         pk[1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{o[2], o[3]}, bf16x2v));
                         __builtin_amdgcn_raw_buffer_store_b64(pk, ro, ooff + (16 * mt + r) * (int)a.out_o * 2, 0, 0);
                     } else {
-                        st16(o, ro, ooff + (16 * mt + r) * (int)a.out_o * 4);
+                        st16<RPB_STREAM_AUX>(o, ro, ooff + (16 * mt + r) * (int)a.out_o * 4);
                     }
                 }
             }

@@ -13,47 +13,12 @@
 // 48 + 96 bf16 MFMAs instead of 96 fp32 ones (6144 -> 2304 matrix-pipe cycles).  One wave per SIMD (accumulators 64 + 32, two steps
 // of three input streams in flight: ~96 KB of loads per CU), rows of Wp cells walked in 32-cell steps.
 #include "rpb_bwr.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 #define BW_WAVES 4
 
-namespace {
 // (cache policy of the streaming loads / stores: RPB_STREAM_AUX, rpb_common.h -- nt by default since round 5)
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, RPB_STREAM_AUX));
-}
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, RPB_STREAM_AUX);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-}  // namespace
 
 // six products of the three-plane split, small terms first, four independent accumulation chains advancing together
 #define BW_MAC6(ACC, AH, AM, AL, BH, BM, BL)                                            \
@@ -97,22 +62,22 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
 
     // per-lane constants of the lane's channels 4 n16 .. 4 n16 + 3
     const int c0 = 4 * n16;
-    const f32x4v mu = *reinterpret_cast<const f32x4v*>(a.mean + c0), is = *reinterpret_cast<const f32x4v*>(a.invstd + c0);
-    const f32x4v ga = *reinterpret_cast<const f32x4v*>(a.gamma + c0), be = *reinterpret_cast<const f32x4v*>(a.beta + c0);
-    const f32x4v m1 = *reinterpret_cast<const f32x4v*>(a.sums + c0) * a.inv_count;
-    const f32x4v m2 = *reinterpret_cast<const f32x4v*>(a.sums + CS + c0) * a.inv_count;
-    const f32x4v gis = ga * is;
-    f32x4v xmu = {0.f, 0.f, 0.f, 0.f}, xis = xmu, xga = xmu, xbe = xmu;
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(a.mean + c0), is = *reinterpret_cast<const f32x4*>(a.invstd + c0);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(a.gamma + c0), be = *reinterpret_cast<const f32x4*>(a.beta + c0);
+    const f32x4 m1 = *reinterpret_cast<const f32x4*>(a.sums + c0) * a.inv_count;
+    const f32x4 m2 = *reinterpret_cast<const f32x4*>(a.sums + CS + c0) * a.inv_count;
+    const f32x4 gis = ga * is;
+    f32x4 xmu = {0.f, 0.f, 0.f, 0.f}, xis = xmu, xga = xmu, xbe = xmu;
     if (XBN) {
-        xmu = *reinterpret_cast<const f32x4v*>(a.xf.mean + c0);
-        xis = *reinterpret_cast<const f32x4v*>(a.xf.invstd + c0);
-        xga = *reinterpret_cast<const f32x4v*>(a.xf.gamma + c0);
-        xbe = *reinterpret_cast<const f32x4v*>(a.xf.beta + c0);
+        xmu = *reinterpret_cast<const f32x4*>(a.xf.mean + c0);
+        xis = *reinterpret_cast<const f32x4*>(a.xf.invstd + c0);
+        xga = *reinterpret_cast<const f32x4*>(a.xf.gamma + c0);
+        xbe = *reinterpret_cast<const f32x4*>(a.xf.beta + c0);
     }
-    const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4v accW[4][NOX ? 1 : 4];                         // d conv weight: tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n16 <-> in channel 4 n16 + ui
-    f32x4v accY[MT][4];                                   // Y1 of the current row: row 16 mt + 4 mg + r = mode, column n16 of tile u <-> channel 4 n16 + u
-    f32x4v bsum = z4;
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 accW[4][NOX ? 1 : 4];                         // d conv weight: tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n16 <-> in channel 4 n16 + ui
+    f32x4 accY[MT][4];                                   // Y1 of the current row: row 16 mt + 4 mg + r = mode, column n16 of tile u <-> channel 4 n16 + u
+    f32x4 bsum = z4;
 #pragma unroll
     for (int uo = 0; uo < 4; ++uo)
 #pragma unroll
@@ -138,27 +103,27 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int vo = (32 * q + 4 * e + kg) * CB + n16 * 16;
-            sv[e] = ld16(rs, vo);
-            yv[e] = ld16(ry, vo);
+            sv[e] = ld16<RPB_STREAM_AUX>(rs, vo);
+            yv[e] = ld16<RPB_STREAM_AUX>(ry, vo);
         }
         if (!NOX) {
             const rsrc_t rx = make_rsrc(a.x + off, nb);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] = ld16(rx, (32 * q + 4 * e + kg) * 256 + n16 * 16);
+            for (int e = 0; e < 8; ++e) xv[e] = ld16<RPB_STREAM_AUX>(rx, (32 * q + 4 * e + kg) * 256 + n16 * 16);
         }
     };
     auto compute = [&](long g, int q, const u32x4 (&sv)[8], const u32x4 (&yv)[8], const u32x4 (&xv)[8]) {
         const rsrc_t ro = make_rsrc(a.gs ? a.gs + g * (long)Wp * CS + coff : a.s, a.gs ? row_bytes : 0u);   // gs == NULL: stores dropped
-        f32x4v gsv[8];
+        f32x4 gsv[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const f32x4v sh = (__builtin_bit_cast(f32x4v, sv[e]) - mu) * is;
-            f32x4v gz = __builtin_bit_cast(f32x4v, yv[e]);
+            const f32x4 sh = (__builtin_bit_cast(f32x4, sv[e]) - mu) * is;
+            f32x4 gz = __builtin_bit_cast(f32x4, yv[e]);
             if (GELU) gz = gz * gelu_grad4(sh * ga + be);
-            f32x4v v = gis * ((gz - m1) - sh * m2);
+            f32x4 v = gis * ((gz - m1) - sh * m2);
             v = (32 * q + 4 * e + kg < Wp) ? v : z4;     // cells past the row end read zeros, which BatchNorm does not map to zero
             gsv[e] = v;
-            st16(v, ro, (32 * q + 4 * e + kg) * CB + n16 * 16);          // past the row end: dropped by the descriptor
+            st16<RPB_STREAM_AUX>(v, ro, (32 * q + 4 * e + kg) * CB + n16 * 16);          // past the row end: dropped by the descriptor
             bsum += v;
         }
         bf16x8 Gh[4], Gm[4], Gl[4];                      // gs planes: column / row n16 of tile u <-> channel 4 n16 + u, K = the lane group's 8 cells
@@ -194,10 +159,10 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
         // ---- dWc[out][in] += gs^T x
         if (!NOX) {
             bf16x8 Xh[4], Xm[4], Xl[4];
-            f32x4v xt[8];
+            f32x4 xt[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                f32x4v xx = __builtin_bit_cast(f32x4v, xv[e]);
+                f32x4 xx = __builtin_bit_cast(f32x4, xv[e]);
                 if (XBN) {
                     xx = bn4(xx, xmu, xis, xga, xbe);
                     if (XGELU) xx = gelu4(xx);
@@ -237,7 +202,7 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = 16 * mt + 4 * kg + r;
-                    if (o < K2) *reinterpret_cast<f32x4v*>(yp + (long)o * CS) = f32x4v{accY[mt][0][r], accY[mt][1][r], accY[mt][2][r], accY[mt][3][r]};
+                    if (o < K2) *reinterpret_cast<f32x4*>(yp + (long)o * CS) = f32x4{accY[mt][0][r], accY[mt][1][r], accY[mt][2][r], accY[mt][3][r]};
                 }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
@@ -284,7 +249,7 @@ __global__ __launch_bounds__(BW_WAVES * 64, 1) void bwr_kernel(BwrArgs a) {
         for (int r = 0; r < 4; ++r) {
             const int o = 4 * (4 * kg + r) + uo;
             if (!NOX)
-                *reinterpret_cast<f32x4v*>(part + o * 64 + 4 * n16) = f32x4v{accW[uo][0][r], accW[uo][1][r], accW[uo][2][r], accW[uo][3][r]};
+                *reinterpret_cast<f32x4*>(part + o * 64 + 4 * n16) = f32x4{accW[uo][0][r], accW[uo][1][r], accW[uo][2][r], accW[uo][3][r]};
         }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {

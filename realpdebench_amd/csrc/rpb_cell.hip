@@ -513,7 +513,7 @@ extern "C" int rpb_cell_mix_eval_dft(const float* x, const float* Wm, const floa
     c.FWt = FWt; c.y1out = y1; c.K2f = K2f; c.gw_planes = scratch;
     return rpb_cmx_launch(c, 0, (hipStream_t)stream);
 }
-// The same launch on the opt-in "f16x2" arithmetic (csrc/rpb_cmx.hip, template parameter H2): operands as two fp16 planes (round to nearest
+// The same launch on the opt-in "f16x2" arithmetic (csrc/rpb_mma.h; csrc/rpb_cmx.hip, template parameter H2): operands as two fp16 planes (round to nearest
 // even: one fp32 unit in the last place), three products per fp32 product, dropped term <= 2^-22 |a b| -- below the fp32 grade of the
 // default path, which is why it is a separate, explicitly named entry point.  spec_exp: floor(log2(Tp * Hp * Wp)) - 1 (the exact
 // power-of-two rescaling of GWt / z2 that keeps both inside fp16's range).

@@ -20,95 +20,21 @@
 //    once per line (a tile-granular version fetched every row ~3x from HBM: 10.3 GB of traffic for 8.56 GB algorithmic);
 //    GW and the conv weights are split once per workgroup into LDS in operand order.
 #include "rpb_cmx.h"
+#include "rpb_mma.h"
 #include <atomic>
 #include <mutex>
 // (cache policy of the streaming loads / stores: RPB_STREAM_AUX, rpb_common.h -- nt by default since round 5)
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, RPB_STREAM_AUX));
-}
 // CMX_WG_X_DEFAULT: the weight-gradient pairs' mix wave loads gs with the default policy (its wgrad wave fetches the same lines a tile later)
 #ifndef CMX_WG_X_DEFAULT
 #define CMX_WG_X_DEFAULT 1
 #endif
-template <int AUX>
-__device__ __forceinline__ u32x4 ld16a(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, AUX));
-}
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, RPB_STREAM_AUX);
-}
 // the SMALL streams -- the z2 rows this launch reads (written by the inverse H stage right before it) and the Y1 rows the fused W stage writes
 // (read by the next H stage right after it), 0.9 GB each at the headline shape -- keep the policy of the large ones: a round-6 sweep of
 // per-tensor policies found no better one (the 256 MB MALL could hold the tail of the producer / the head of the consumer)
-template <int AUX>
-__device__ __forceinline__ void st16a(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, AUX);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-// (a, b) fp32 -> one dword of two truncated bf16 (a low half, b high half)
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-// 8 fp32 -> three bf16x8 planes (exact: hi + mid + lo == v)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-// H2 (the opt-in "f16x2" eval arithmetic, CmxArgs::h2): operands as TWO fp16 planes, both rounded to nearest even (x = hi + lo to one fp32
-// unit in the last place: 11 + 11 significand bits and the sign of lo), three products hi*lo + lo*hi + hi*hi on v_mfma_f32_16x16x32_f16;
-// the dropped lo*lo term is <= 2^-22 |a b| -- the grade of "3xTF32", NOT the 2^-24 grade of the default path.  Half the matrix-pipe time
-// and 2.5 instead of 5.5 vector instructions per split value.  The planes travel in the bf16x8 containers of the default path (bit
-// patterns only): plane slot 0 = hi, slot 1 = lo.  fp16's range is handled by exact power-of-two scalings, see CmxArgs::spec_exp.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2w __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split8h(const float (&v)[8], bf16x8& h, bf16x8& l) {
-    u32x4 uh, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2w ab = {v[2 * q], v[2 * q + 1]};
-        const f16x2v hh = __builtin_convertvector(ab, f16x2v);                       // v_cvt_pk_f16_f32 (RNE)
-        uh[q] = __builtin_bit_cast(unsigned, hh);
-        // residual a - float(hi) as ONE v_fma_mix_f32 per value (f16 half * -1 + f32; exact): 4 instead of 5 instructions per value pair
-        // (left alone the compiler converts both halves and subtracts packed: 2 x v_cvt_f32_f16 + v_pk_add_f32)
-        float r0, r1;
-        const unsigned hu = uh[q];
-        const float a0 = ab[0], a1 = ab[1];
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hu), "v"(a0));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hu), "v"(a1));
-        const f32x2w r = {r0, r1};
-        const f16x2v ll = __builtin_convertvector(r, f16x2v);
-        ul[q] = __builtin_bit_cast(unsigned, ll);
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16h(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+// H2 (CmxArgs::h2): the opt-in "f16x2" eval arithmetic of rpb_mma.h (split8h<true>, mfma16h); fp16's range: CmxArgs::spec_exp.
 
 // waves per workgroup (= per CU): the z2 planes of a line take 12 KB of LDS per wave: 8 waves + operands = 147 KB
 #ifndef CMX_WAVES_A
@@ -233,7 +159,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
         }
         bf16x8 h, md, lo;
         if (H2X) {
-            split8h(v, h, md);
+            split8h<true>(v, h, md);
             lo = md;
         } else {
             split8(v, h, md, lo);
@@ -253,7 +179,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
         }
         bf16x8 h, md, lo;
         if (H2) {
-            split8h(v, h, md);
+            split8h<true>(v, h, md);
             lo = md;
         } else {
             split8(v, h, md, lo);
@@ -275,7 +201,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
             }
             bf16x8 h, md, lo;
             if (H2) {
-                split8h(v, h, md);
+                split8h<true>(v, h, md);
                 lo = md;
             } else {
                 split8(v, h, md, lo);
@@ -318,8 +244,8 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
             const int slot = (int)blockIdx.x * CMX_WG_PAIRS + pair;
             const unsigned line_bytes = (unsigned)Wp * 256u;
             const int ooff = (4 * kg) * 256 + m * 16;        // accumulator layout: cell 4 mg + r of MFMA tile j, channels 4 n .. 4 n + 3
-            const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
-            f32x4v accW[4][4];                               // tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n <-> in channel 4 n + ui
+            const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+            f32x4 accW[4][4];                               // tile (uo, ui): row 4 mg + r <-> out channel 4 (4 mg + r) + uo, column n <-> in channel 4 n + ui
 #pragma unroll
             for (int uo = 0; uo < 4; ++uo)
 #pragma unroll
@@ -334,7 +260,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) gb[j][r] = ld16(rx, qo + ooff + j * 4096 + r * 256);
+                    for (int r = 0; r < 4; ++r) gb[j][r] = ld16<RPB_STREAM_AUX>(rx, qo + ooff + j * 4096 + r * 256);
             };
             int* fl = flags + 2 * pair;
             const u32x4* mb = MBs + pair * 8 * 64 + lane;
@@ -354,7 +280,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[4 * j + r] = __builtin_bit_cast(f32x4v, gb[j][r])[u];
+                        for (int r = 0; r < 4; ++r) v[4 * j + r] = __builtin_bit_cast(f32x4, gb[j][r])[u];
                     split8(v, Gh[u], Gm[u], Gl[u]);
                 }
                 issue_g(gn, qn, gn < G);                     // next tile's gs: in flight while this wave waits for / multiplies act(z)
@@ -374,7 +300,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[4 * j + r] = __builtin_bit_cast(f32x4v, av[j][r])[u];
+                        for (int r = 0; r < 4; ++r) v[4 * j + r] = __builtin_bit_cast(f32x4, av[j][r])[u];
                     split8(v, Xh[u], Xm[u], Xl[u]);
                 }
                 ++k;
@@ -394,7 +320,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = 4 * (4 * kg + r) + uo;
-                    *reinterpret_cast<f32x4v*>(wp + o * 64 + 4 * m) = f32x4v{accW[uo][0][r], accW[uo][1][r], accW[uo][2][r], accW[uo][3][r]};
+                    *reinterpret_cast<f32x4*>(wp + o * 64 + 4 * m) = f32x4{accW[uo][0][r], accW[uo][1][r], accW[uo][2][r], accW[uo][3][r]};
                 }
             return;
         }
@@ -458,17 +384,17 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
         if (FEAT) {                 // 32 B of fields 8 kg .. 8 kg + 7 (lane groups past FW: an offset outside the descriptor -> 0)
             if (ks == 0) {
                 const int off = 8 * kg < FW ? (32 * q + 16 * j + m) * FW * 4 + kg * 32 : 0x7ffffff0;
-                xa[j][0] = ld16(rx, off);
-                xa[j][1] = ld16(rx, off + 16);
+                xa[j][0] = ld16<RPB_STREAM_AUX>(rx, off);
+                xa[j][1] = ld16<RPB_STREAM_AUX>(rx, off + 16);
             }
         } else if (BF) {
-            xa[j][ks] = ld16(rx, q * 4096 + j * 2048 + m * 128 + ks * 64 + kg * 16);
+            xa[j][ks] = ld16<RPB_STREAM_AUX>(rx, q * 4096 + j * 2048 + m * 128 + ks * 64 + kg * 16);
         } else {
 #pragma unroll
             // (C = 128: the two workgroups of a pair read the same x lines, the second out of L2 / MALL -- default policy there; measured:
             //  fsi step 43.0 -> 44.5 ms with nontemporal x loads)
             for (int hf = 0; hf < 2; ++hf)
-                xa[j][2 * (C2 ? (ks & 1) : ks) + hf] = ld16a<(C2 || (WG && CMX_WG_X_DEFAULT)) ? 0 : RPB_STREAM_AUX>(rx, q * (32 * CB) + xoff + j * (16 * CB) + (2 * ks + hf) * 64);
+                xa[j][2 * (C2 ? (ks & 1) : ks) + hf] = ld16<(C2 || (WG && CMX_WG_X_DEFAULT)) ? 0 : RPB_STREAM_AUX>(rx, q * (32 * CB) + xoff + j * (16 * CB) + (2 * ks + hf) * 64);
         }
     };
     u32x4 zr[8];
@@ -486,11 +412,11 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
         }
         const rsrc_t rz = make_rsrc(a.z2 + g * K2 * CC + 64 * hsel, (unsigned)K2 * (unsigned)CB - 256u * (unsigned)hsel);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) zr[e] = ld16a<RPB_STREAM_AUX>(rz, (8 * kg + e) * CB + m * 16);
+        for (int e = 0; e < 8; ++e) zr[e] = ld16<RPB_STREAM_AUX>(rz, (8 * kg + e) * CB + m * 16);
     };
 
     u32x4* Zw = Zs + wave * ZST * 64 + lane;
-    f32x4v Yacc[DFT ? 2 : 1][DFT ? 4 : 1];
+    f32x4 Yacc[DFT ? 2 : 1][DFT ? 4 : 1];
     // one wave tile: (gi, q) = the tile computed from the register image `xa`; (ngi, nq) = the tile whose loads take the image's place
     // (the next tile, or with PF2 the one after it; ngi >= G: none)
     // WG: pin the (wave-uniform) line indices to SGPRs -- with the second wave role in the kernel the compiler keeps them in VGPRs and
@@ -519,11 +445,11 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
             const bool half_tile = (SPLITL && !LASTC) ? false : (32 * q + 16 >= Wp);   // uniform: the second MFMA tile lies past the line end
             asm volatile("" ::: "memory");   // keep the (tile-invariant) LDS operand reads inside the loop: hoisted, they cost 150 VGPRs
 
-            f32x4v acc[2][4];
+            f32x4 acc[2][4];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc[j][t] = f32x4v{bv[t], bv[t], bv[t], bv[t]};     // the bias rides in the accumulator
+                for (int t = 0; t < 4; ++t) acc[j][t] = f32x4{bv[t], bv[t], bv[t], bv[t]};     // the bias rides in the accumulator
             u32x4 spre[2][4];
             // ---- channel mixing: K = 64 = 2 steps of 32.  Per step: x registers -> A planes (lazy BN+GELU of the producer
             //      applied here), then the freed registers take the next wave tile's loads, in flight during everything below
@@ -542,7 +468,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                         for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) v[4 * hf + c] = __builtin_bit_cast(f32x4v, xa[j][hf])[c];
+                            for (int c = 0; c < 4; ++c) v[4 * hf + c] = __builtin_bit_cast(f32x4, xa[j][hf])[c];
                         split8(v, Ah[j], Am[j], Al[j]);
                         continue;
                     }
@@ -550,10 +476,10 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
                         const int i = 2 * ks + hf;
-                        const f32x4v xv = __builtin_bit_cast(f32x4v, xa[j][C2 ? 2 * (ks & 1) + hf : i]);
+                        const f32x4 xv = __builtin_bit_cast(f32x4, xa[j][C2 ? 2 * (ks & 1) + hf : i]);
                         if (has_xf) {
-                            const f32x4v sc = *reinterpret_cast<const f32x4v*>(xfp + 16 * i + 4 * kg);
-                            const f32x4v sh = *reinterpret_cast<const f32x4v*>(xfp + CC + 16 * i + 4 * kg);
+                            const f32x4 sc = *reinterpret_cast<const f32x4*>(xfp + 16 * i + 4 * kg);
+                            const f32x4 sh = *reinterpret_cast<const f32x4*>(xfp + CC + 16 * i + 4 * kg);
                             // channel pairs: packed fp32 math, the two pairs' erf polynomials in lock-step (rpb_common.h, gelu2x2)
                             f32x2 z0 = pk_fma(f32x2{xv[0], xv[1]}, f32x2{sc[0], sc[1]}, f32x2{sh[0], sh[1]});
                             f32x2 z1 = pk_fma(f32x2{xv[2], xv[3]}, f32x2{sc[2], sc[3]}, f32x2{sh[2], sh[3]});
@@ -567,7 +493,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                             for (int c = 0; c < 4; ++c) v[4 * hf + c] = xv[c];
                         }
                     }
-                    if (H2X) split8h(v, Ah[j], Am[j]);
+                    if (H2X) split8h<true>(v, Ah[j], Am[j]);
                     else split8(v, Ah[j], Am[j], Al[j]);
                 }
                 if (C2 && ks < 2) {                 // C = 128: this tile's K-steps 2, 3 take the slots of 0, 1
@@ -591,12 +517,12 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                             }
                             float v[8];
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(f32x4v, zr[e])[t];
+                            for (int e = 0; e < 8; ++e) v[e] = __builtin_bit_cast(f32x4, zr[e])[t];
                             bf16x8 zh, zm, zl;
                             if (H2) {
 #pragma unroll
                                 for (int e = 0; e < 8; ++e) v[e] = __builtin_ldexpf(v[e], -a.spec_exp);
-                                split8h(v, zh, zm);
+                                split8h<true>(v, zh, zm);
                                 Zw[(0 * 4 + t) * 64] = __builtin_bit_cast(u32x4, zh);
                                 Zw[(1 * 4 + t) * 64] = __builtin_bit_cast(u32x4, zm);
                                 continue;
@@ -612,7 +538,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) spre[j][r] = ld16(rs, q * (32 * CB) + ooff + j * (16 * CB) + r * CB);
+                            for (int r = 0; r < 4; ++r) spre[j][r] = ld16<RPB_STREAM_AUX>(rs, q * (32 * CB) + ooff + j * (16 * CB) + r * CB);
                     }
                 }
 #pragma unroll
@@ -698,7 +624,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const bool valid = !MASKED || (32 * q + 16 * j + 4 * kg + r < Wp);
-                        f32x4v o, avr;
+                        f32x4 o, avr;
                         // channel pairs (packed fp32 math); the erf polynomials of the two pairs run in lock-step (gelu2x2 / gelu_both_as2x2)
                         f32x2 vv[2], shv[2], gpv[2], acv[2];
 #pragma unroll
@@ -707,7 +633,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                             vv[tt] = f32x2{acc[j][t][r], acc[j][t + 1][r]};
                             if (STATS == 0 && oxf) vv[tt] = pk_fma(vv[tt], f32x2{bp[t].is, bp[t + 1].is}, f32x2{bp[t].be, bp[t + 1].be});
                             if (STATS == 2) {
-                                const f32x4v sp = __builtin_bit_cast(f32x4v, spre[j][r]);
+                                const f32x4 sp = __builtin_bit_cast(f32x4, spre[j][r]);
                                 shv[tt] = (f32x2{sp[t], sp[t + 1]} - f32x2{bp[t].mu, bp[t + 1].mu}) * f32x2{bp[t].is, bp[t + 1].is};
                                 acv[tt] = pk_fma(shv[tt], f32x2{bp[t].ga, bp[t + 1].ga}, f32x2{bp[t].be, bp[t + 1].be});      // z
                                 gpv[tt] = pk2(1.f);
@@ -762,7 +688,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                                     acc[j][t][r] = __builtin_bit_cast(float, (pk[t >> 1] >> (16 * (t & 1))) << 16);
                             }
                         } else {
-                            st16(o, ro, q * (32 * CB) + ooff + j * (16 * CB) + r * CB);
+                            st16<RPB_STREAM_AUX>(o, ro, q * (32 * CB) + ooff + j * (16 * CB) + r * CB);
                         }
                         if (WG) MBw[(4 * j + r) * 64] = __builtin_bit_cast(u32x4, avr);
                     }
@@ -780,7 +706,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) Yacc[i][t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+                        for (int t = 0; t < 4; ++t) Yacc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
                 bf16x8 fh[2], fm[2], fl[2];
 #pragma unroll
@@ -809,7 +735,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                     }
                     bf16x8 yh, ym, yl;
                     if (H2) {
-                        split8h(v, yh, ym);
+                        split8h<true>(v, yh, ym);
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
                             Yacc[i][t] = mfma16h(fh[i], ym, Yacc[i][t]);
@@ -850,7 +776,7 @@ __global__ __launch_bounds__((C2 ? C2 : (WG ? 2 * CMX_WG_PAIRS : (DFT ? CMX_WAVE
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            st16a<RPB_STREAM_AUX>(f32x4v{Yacc[i][0][r], Yacc[i][1][r], Yacc[i][2][r], Yacc[i][3][r]}, ry, (16 * i + 4 * kg + r) * 256 + m * 16);
+                            st16<RPB_STREAM_AUX>(f32x4{Yacc[i][0][r], Yacc[i][1][r], Yacc[i][2][r], Yacc[i][3][r]}, ry, (16 * i + 4 * kg + r) * 256 + m * 16);
                     }
                 }
             }
@@ -1015,7 +941,7 @@ __global__ void cmx_gw_prep_kernel(const float* __restrict__ GW, u32x4* __restri
     }
     bf16x8 h, md, lo;
     if (h2_exp >= 0) {
-        split8h(v, h, md);
+        split8h<true>(v, h, md);
         lo = md;
     } else {
         split8(v, h, md, lo);

@@ -44,7 +44,7 @@ int rpb_num_cus();   // cached hipDeviceAttributeMultiprocessorCount of the curr
 // item index changes the compiler's schedule of that instance), so they keep the static deal.
 int rpb_line_claim_mode();
 
-// ---------------------------------------------------------------------------------- MFMA
+// ---------------------------------------------------------------------------------- MFMA (fp32 pipe; the bf16 / fp16 pipe: rpb_mma.h)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -100,49 +100,6 @@ __device__ __forceinline__ unsigned tile_bytes(long rows_left, int tile_rows, in
         if (RPB_STREAM_AUX == 2) __builtin_nontemporal_store((V), reinterpret_cast<f32x4*>(P)); \
         else *reinterpret_cast<f32x4*>(P) = (V);                                        \
     } while (0)
-
-// bf16 STORAGE (BASELINE.json configs[4]): an operand that was stored as bf16 carries a rounding of 2^-9 of its value, and it is multiplied
-// with the planes of an fp32 constant (conv / fc1 weights, DFT stage matrices).  The constant's third plane contributes 2^-16 of the product:
-// 1 / 128 of the error the stored operand already has.  RPB_BF16_CONST_PLANES = 2 (default) drops that product -- two MFMAs per stored plane
-// instead of three in every kernel of the bf16-storage forward; 3 keeps it (round 4).  fp32 storage is not touched.
-#ifndef RPB_BF16_CONST_PLANES
-#define RPB_BF16_CONST_PLANES 2
-#endif
-
-// ---------------------------------------------------------------------------------- the three-plane operand split
-// x = hi + mid + lo EXACTLY with three bf16 numbers, two ways:
-//   RPB_SPLIT_RNE = 0 (default)  truncation at every level (v_perm packs): mid < 2^-7 |x|, lo < 2^-15 |x|, so the three products the
-//       six-product scheme drops (mid*lo, lo*mid, lo*lo) are 2^-24 |a b| typically (rms 2^-24.1) and reach 2^-21.3 in the worst case;
-//   RPB_SPLIT_RNE = 1  round to nearest even at every level (gfx950: v_cvt_pk_bf16_f32 converts a pair): |mid| <= 2^-8 |x|, |lo| <= 2^-16 |x|,
-//       still exact (the last residual has at most 8 significant bits), dropped terms <= 2^-24.2 |a b| worst case, 2^-27.5 rms
-//       (tools/split_error.py).  Fewer instructions (4.5 against 5.5 per value) but NOT faster: the conversions and packed subtracts
-//       issue at the packed rate -- measured (profiles/r06b_ab4_split_rne.txt, A/B twice on one box): train step 35.63 / 35.67 ms with the
-//       truncating split, 36.04 / 36.09 with the rounding one (the wave-pair backward cell_mix 2.95 -> 3.05 ms), eval forward equal
-//       (11.35 ms).  Every parity test passes either way; the build switch is for a caller that wants the tighter worst case for 1.1 %.
-// (The split3 passes of csrc/rpb_conv3x.hip -- memory-bound -- have rounded since round 2.)
-#ifndef RPB_SPLIT_RNE
-#define RPB_SPLIT_RNE 0
-#endif
-typedef __bf16 rpb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float rpb_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void rpb_split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-#if RPB_SPLIT_RNE
-    const rpb_f32x2 ab = {a, b};
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector(ab, rpb_bf16x2));
-    const rpb_f32x2 r = ab - rpb_f32x2{__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xffff0000u)};        // exact
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, rpb_bf16x2));
-    const rpb_f32x2 s = r - rpb_f32x2{__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xffff0000u)};         // exact
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(s, rpb_bf16x2));                                                  // exact: <= 8 significant bits
-#else
-    const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
-    h = __builtin_amdgcn_perm(ub, ua, 0x07060302u);
-    const float ra = a - __builtin_bit_cast(float, ua & 0xffff0000u), rb = b - __builtin_bit_cast(float, ub & 0xffff0000u);
-    const unsigned uc = __builtin_bit_cast(unsigned, ra), ud = __builtin_bit_cast(unsigned, rb);
-    m = __builtin_amdgcn_perm(ud, uc, 0x07060302u);
-    const float sa = ra - __builtin_bit_cast(float, uc & 0xffff0000u), sb = rb - __builtin_bit_cast(float, ud & 0xffff0000u);
-    l = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, sb), __builtin_bit_cast(unsigned, sa), 0x07060302u);
-#endif
-}
 
 // ---------------------------------------------------------------------------------- math
 // Branch-free erf:  erf(x) = sign(x) * (1 - 2^(t*S(t))),  t = min(|x|, 4),  S = degree-8 weighted-minimax fit of
@@ -202,19 +159,10 @@ __device__ __forceinline__ f32x2 gelu_grad2(f32x2 x) {
     return cdf + x * (pk2(0.39894228040143267794f) * e);
 }
 
-// gelu(x) and gelu'(x) from ONE erf (the backward cell_mix needs the layer input act(z) for the weight gradient next to act'(z))
-__device__ __forceinline__ void gelu_both2(f32x2 x, f32x2& g, f32x2& gp) {
-    const f32x2 h = pk2(0.5f) * (pk2(1.0f) + fast_erf2(x * pk2(0.70710678118654752440f)));
-    const f32x2 q = (pk2(-0.72134752044448170368f) * x) * x;
-    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
-    g = (pk2(0.5f) * x) * (pk2(1.0f) + fast_erf2(x * pk2(0.70710678118654752440f)));      // same expression as gelu2 (CSE'd erf)
-    gp = h + x * (pk2(0.39894228040143267794f) * e);
-}
-
 // TWO packed pairs in lock-step.  A dependent v_pk_fma_f32 needs a wait state after its producer (the compiler fills it with s_nop 0)
 // and cannot issue back to back; left alone the compiler evaluates one nine-term chain after the other (shortest live ranges), so a wave
 // spends the polynomial waiting on itself.  Written as two interleaved chains every instruction has an independent neighbour.
-// Element-wise the operations -- and therefore the results -- are those of fast_erf2 / gelu2 / gelu_both2.
+// Element-wise the operations -- and therefore the results -- are those of fast_erf2 / gelu2.
 // A scheduling barrier behind every step keeps the interleaving: the scheduler may not move instructions across the step boundaries.
 __device__ __forceinline__ void fast_erf2x2(f32x2 xa, f32x2 xb, f32x2& ra, f32x2& rb) {
     const f32x2 ta = __builtin_elementwise_min(__builtin_elementwise_abs(xa), pk2(4.0f));

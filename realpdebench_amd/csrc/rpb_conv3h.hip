@@ -11,11 +11,9 @@
 // Layout and tiling are those of conv3x_kernel: a workgroup owns 128 consecutive tokens, stages the 130 rows of each (kt, kh) and
 // 64-channel chunk in LDS (two planes: 2 x 33 KB per stage buffer instead of 2 x 50 KB), the w boundary is applied to the A operand,
 // weights are pre-arranged in MFMA B-operand order Wz[tap][Ci/16][2 planes][N/32][64 lanes][8] fp16.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
 
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4h __attribute__((ext_vector_type(4)));
 template <int V>
 struct ICh {
     static constexpr int value = V;
@@ -23,10 +21,6 @@ struct ICh {
 
 #define CH_BM 128
 #define CH_ROWS (CH_BM + 2)
-
-__device__ __forceinline__ f32x16 mfma_f16(u32x4h a, u32x4h b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8h, a), __builtin_bit_cast(f16x8h, b), c, 0, 0, 0);
-}
 
 // x * 2^e -> (hi, lo) fp16 bit patterns, both RNE; non-finite values give a non-finite hi (and lo = NaN): they propagate
 __device__ __forceinline__ void split2h(float x, int e, unsigned& h, unsigned& l) {
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(256) void amax_bits_kernel(const float* __restrict_
         const long m = idx / c4n;
         const int c4 = (int)(idx - m * c4n);
         // loaded as unsigned: a bit cast of each element of an f32x4 compiled to a compare of element 0 only
-        const u32x4h v = *reinterpret_cast<const u32x4h*>(x + m * ldx + c4 * 4);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(x + m * ldx + c4 * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const unsigned u = v[i] & 0x7FFFFFFFu;
@@ -187,7 +181,7 @@ struct Conv3hArgs {
 template <int WN>
 __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     constexpr int KS = 4 / WN;
-    extern __shared__ u32x4h lds4h[];
+    extern __shared__ u32x4 lds4h[];
     // two stage buffers of [2 planes][4 chunks][2 halves][CH_ROWS] x 16 B, then [9][CH_ROWS] row validity per (kt, kh)
     unsigned char* rv = reinterpret_cast<unsigned char*>(lds4h + 2 * 16 * CH_ROWS);
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
@@ -225,7 +219,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     f32x16 acc[4][2];
 #pragma unroll
     for (int tm = 0; tm < 4; ++tm) acc[tm][0] = acc[tm][1] = zero16();
-    const u32x4h z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     const long MC = a.M * a.Ci;
 
     // software pipeline of conv3x_kernel: next stage's A loads spread over the current stage's tap steps, next tap step's B operands
@@ -235,30 +229,30 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     const uint16_t* wbase = a.Wz + ((long)(n0 >> 5) * 64 + lane) * 8;
     const long wplane = (long)NT * 512;                                // fp16 elements between the planes of one (tap, chunk)
     const long wchunk = 2 * wplane, wtap = (long)NCC * wchunk;
-    auto bload = [&](const uint16_t* src, u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+    auto bload = [&](const uint16_t* src, u32x4 (&b)[2][2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn) b[tn][p] = *reinterpret_cast<const u32x4h*>(src + p * wplane + tn * 512);
+            for (int tn = 0; tn < 2; ++tn) b[tn][p] = *reinterpret_cast<const u32x4*>(src + p * wplane + tn * 512);
     };
-    u32x4h bc[2][2], bn[2][2];
-    const u32x4h* As = lds4h;
-    u32x4h ac[2], an[2];
-    auto lda = [&](int s, int kw, int tm, u32x4h (&av)[2]) __attribute__((always_inline)) {
+    u32x4 bc[2][2], bn[2][2];
+    const u32x4* As = lds4h;
+    u32x4 ac[2], an[2];
+    auto lda = [&](int s, int kw, int tm, u32x4 (&av)[2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) av[p] = As[((p * 4 + s) * 2 + half) * CH_ROWS + tm * 32 + col + kw];
     };
-    auto mfma6 = [&](int tm, int kw, u32x4h (&av)[2], const u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+    auto mfma6 = [&](int tm, int kw, u32x4 (&av)[2], const u32x4 (&b)[2][2]) __attribute__((always_inline)) {
         if ((kw == 0 && wlo[tm]) || (kw == 2 && whi[tm])) av[0] = av[1] = z4;
         // small terms first; the two co tiles alternate so consecutive MFMAs are independent
-        acc[tm][0] = mfma_f16(av[1], b[0][0], acc[tm][0]);
-        acc[tm][1] = mfma_f16(av[1], b[1][0], acc[tm][1]);
-        acc[tm][0] = mfma_f16(av[0], b[0][1], acc[tm][0]);
-        acc[tm][1] = mfma_f16(av[0], b[1][1], acc[tm][1]);
-        acc[tm][0] = mfma_f16(av[0], b[0][0], acc[tm][0]);
-        acc[tm][1] = mfma_f16(av[0], b[1][0], acc[tm][1]);
+        acc[tm][0] = mfma32h(av[1], b[0][0], acc[tm][0]);
+        acc[tm][1] = mfma32h(av[1], b[1][0], acc[tm][1]);
+        acc[tm][0] = mfma32h(av[0], b[0][1], acc[tm][0]);
+        acc[tm][1] = mfma32h(av[0], b[1][1], acc[tm][1]);
+        acc[tm][0] = mfma32h(av[0], b[0][0], acc[tm][0]);
+        acc[tm][1] = mfma32h(av[0], b[1][0], acc[tm][1]);
     };
-    auto tap_step = [&](int s, int kw, bool more, const u32x4h (&b)[2][2]) __attribute__((always_inline)) {
+    auto tap_step = [&](int s, int kw, bool more, const u32x4 (&b)[2][2]) __attribute__((always_inline)) {
         lda(s, kw, 1, an);
         __builtin_amdgcn_sched_barrier(0);
         mfma6(0, kw, ac, b);
@@ -276,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
         mfma6(3, kw, an, b);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto bsel = [&](auto pc) -> u32x4h(&)[2][2] {
+    auto bsel = [&](auto pc) -> u32x4(&)[2][2] {
         if constexpr (decltype(pc)::value) return bn;
         else return bc;
     };
@@ -284,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     constexpr int NLD = (CH_ROWS * 16 + 255) / 256;
     static_assert(NLD == 9, "staging macros below are written for 9 loads per thread");
 #define CH_FOR9(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#define CH_DECL(J) u32x4h sv##J = z4; bool ok##J = false;
+#define CH_DECL(J) u32x4 sv##J = z4; bool ok##J = false;
     CH_FOR9(CH_DECL)
 #define CH_LOAD(J)                                                                                            \
     if constexpr (J >= j0 && J < j1) {                                                                        \
@@ -293,7 +287,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
         const int p = rem >> 3, sh = rem & 7; /* sh = 2 * chunk + half: 8 x 16 B = one 128 B line */          \
         ok##J = idx < CH_ROWS * 16 && rv[g * CH_ROWS + (row < CH_ROWS ? row : 0)];                            \
         const long off = ok##J ? (long)p * MC + (rowbase + row) * a.Ci + c * 64 + sh * 8 : 0;                 \
-        sv##J = *reinterpret_cast<const u32x4h*>(a.P + off);                                                  \
+        sv##J = *reinterpret_cast<const u32x4*>(a.P + off);                                                  \
     }
 #define CH_STORE(J)                                                                                           \
     {                                                                                                         \
@@ -307,7 +301,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
         const long rowbase = m0 - 1 + ((long)(kt - 1) * a.H + (kh - 1)) * a.W;
         CH_FOR9(CH_LOAD)
     };
-    auto stage_store = [&](u32x4h* dst) __attribute__((always_inline)) { CH_FOR9(CH_STORE) };
+    auto stage_store = [&](u32x4* dst) __attribute__((always_inline)) { CH_FOR9(CH_STORE) };
     bload(wbase + (long)kp * wchunk, bc);                               // (g 0, c 0, s = kp, kw 0)
     stage_load(0, 0, ICh<0>{}, ICh<NLD>{});
     stage_store(lds4h);

@@ -17,11 +17,9 @@
 // lane (row i, half) is one ds_read_b128 and 32 lanes read 512 contiguous bytes.  Each of the 4 waves computes a
 // 128 token x 64 co tile (4 x 2 MFMA tiles, 128 accumulator registers); waves are spread over co first (WN of them) and the
 // remaining factor KS = 4 / WN splits the 16-channel chunks of a stage, reduced through LDS at the end.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector: selects stay in registers (HIP's uint4 struct did not)
 template <int V>
 struct IC {
     static constexpr int value = V;
@@ -29,10 +27,6 @@ struct IC {
 
 #define CX_BM 128
 #define CX_ROWS (CX_BM + 2)
-
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 // round-to-nearest-even bf16 of x (as the upper 16 bits of an fp32)
 __device__ __forceinline__ unsigned bf16_rne(float x) {
@@ -213,18 +207,18 @@ __global__ __launch_bounds__(256, 1) void conv3x_kernel(Conv3xArgs a) {
                      b0l = __builtin_bit_cast(bf16x8, b[0][2]), b1h = __builtin_bit_cast(bf16x8, b[1][0]),
                      b1m = __builtin_bit_cast(bf16x8, b[1][1]), b1l = __builtin_bit_cast(bf16x8, b[1][2]);
         // small terms first; the two co tiles alternate so consecutive MFMAs are independent
-        acc[tm][0] = mfma_bf16(al, b0h, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(al, b1h, acc[tm][1]);
-        acc[tm][0] = mfma_bf16(ah, b0l, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(ah, b1l, acc[tm][1]);
-        acc[tm][0] = mfma_bf16(am, b0m, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(am, b1m, acc[tm][1]);
-        acc[tm][0] = mfma_bf16(am, b0h, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(am, b1h, acc[tm][1]);
-        acc[tm][0] = mfma_bf16(ah, b0m, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(ah, b1m, acc[tm][1]);
-        acc[tm][0] = mfma_bf16(ah, b0h, acc[tm][0]);
-        acc[tm][1] = mfma_bf16(ah, b1h, acc[tm][1]);
+        acc[tm][0] = mfma32b(al, b0h, acc[tm][0]);
+        acc[tm][1] = mfma32b(al, b1h, acc[tm][1]);
+        acc[tm][0] = mfma32b(ah, b0l, acc[tm][0]);
+        acc[tm][1] = mfma32b(ah, b1l, acc[tm][1]);
+        acc[tm][0] = mfma32b(am, b0m, acc[tm][0]);
+        acc[tm][1] = mfma32b(am, b1m, acc[tm][1]);
+        acc[tm][0] = mfma32b(am, b0h, acc[tm][0]);
+        acc[tm][1] = mfma32b(am, b1h, acc[tm][1]);
+        acc[tm][0] = mfma32b(ah, b0m, acc[tm][0]);
+        acc[tm][1] = mfma32b(ah, b1m, acc[tm][1]);
+        acc[tm][0] = mfma32b(ah, b0h, acc[tm][0]);
+        acc[tm][1] = mfma32b(ah, b1h, acc[tm][1]);
     };
     auto tap_step = [&](int s, int kw, bool more, const u32x4 (&b)[2][3]) __attribute__((always_inline)) {   // kw: compile-time constant
         lda(s, kw, 1, an);
@@ -610,7 +604,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_wgrad_kernel(WgxArgs a) {
         }
         if (do_bias) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) accb = mfma_bf16(__builtin_bit_cast(bf16x8, ga[p]), __builtin_bit_cast(bf16x8, ones), accb);
+            for (int p = 0; p < 3; ++p) accb = mfma32b(__builtin_bit_cast(bf16x8, ga[p]), __builtin_bit_cast(bf16x8, ones), accb);
         }
         u32x4 xb[3][3];                                                 // all nine X operands of the step before its MFMAs
 #pragma unroll
@@ -623,9 +617,9 @@ __global__ __launch_bounds__(256, 1) void conv3x_wgrad_kernel(WgxArgs a) {
         for (int kh = 0; kh < 3; ++kh) {
             // (A plane, B plane): lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi; the three kw taps alternate
 #define WX_MF(PA, PB)                                                                                                             \
-    acc[kh * 3 + 0] = mfma_bf16(__builtin_bit_cast(bf16x8, g0[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 0]);    \
-    acc[kh * 3 + 1] = mfma_bf16(__builtin_bit_cast(bf16x8, ga[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 1]);    \
-    acc[kh * 3 + 2] = mfma_bf16(__builtin_bit_cast(bf16x8, g2[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 2]);
+    acc[kh * 3 + 0] = mfma32b(__builtin_bit_cast(bf16x8, g0[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 0]);    \
+    acc[kh * 3 + 1] = mfma32b(__builtin_bit_cast(bf16x8, ga[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 1]);    \
+    acc[kh * 3 + 2] = mfma32b(__builtin_bit_cast(bf16x8, g2[PA]), __builtin_bit_cast(bf16x8, xb[kh][PB]), acc[kh * 3 + 2]);
             WX_MF(2, 0) WX_MF(0, 2) WX_MF(1, 1) WX_MF(1, 0) WX_MF(0, 1) WX_MF(0, 0)
 #undef WX_MF
         }
@@ -828,14 +822,14 @@ __global__ __launch_bounds__(256, 1) void conv3x_wgrad_ring_kernel(WgrArgs a) {
     auto mma = [&](const Ops& o_) __attribute__((always_inline)) {
         if (do_bias) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) accb = mfma_bf16(__builtin_bit_cast(bf16x8, o_.ga[p]), __builtin_bit_cast(bf16x8, ones), accb);
+            for (int p = 0; p < 3; ++p) accb = mfma32b(__builtin_bit_cast(bf16x8, o_.ga[p]), __builtin_bit_cast(bf16x8, ones), accb);
         }
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
 #define WX_MF(PA, PB)                                                                                                                   \
-    acc[kh * 3 + 0] = mfma_bf16(__builtin_bit_cast(bf16x8, o_.g0[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 0]);    \
-    acc[kh * 3 + 1] = mfma_bf16(__builtin_bit_cast(bf16x8, o_.ga[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 1]);    \
-    acc[kh * 3 + 2] = mfma_bf16(__builtin_bit_cast(bf16x8, o_.g2[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 2]);
+    acc[kh * 3 + 0] = mfma32b(__builtin_bit_cast(bf16x8, o_.g0[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 0]);    \
+    acc[kh * 3 + 1] = mfma32b(__builtin_bit_cast(bf16x8, o_.ga[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 1]);    \
+    acc[kh * 3 + 2] = mfma32b(__builtin_bit_cast(bf16x8, o_.g2[PA]), __builtin_bit_cast(bf16x8, o_.xb[kh][PB]), acc[kh * 3 + 2]);
             WX_MF(2, 0) WX_MF(0, 2) WX_MF(1, 1) WX_MF(1, 0) WX_MF(0, 1) WX_MF(0, 0)
 #undef WX_MF
         }

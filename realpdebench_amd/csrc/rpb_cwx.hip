@@ -7,45 +7,12 @@
 // mg = lane >> 4) loads, for the 32 cells of a tile, 16 B = channels 4 n .. 4 n + 3 (of one 64-channel half) of cells 16 j + 4 mg + r:
 // 8 loads per factor, each instruction 4 whole 256 B half rows -- the accumulator layout of csrc/rpb_cmx.hip, whose values for one channel
 // sub-index u are exactly an MFMA operand with k <-> cell.  Both factors are split into three bf16 planes in registers (truncation
-// splits, six products per fp32 product, fp32 accumulate: the arithmetic of rpb_cmx.hip) and a wave accumulates ONE 64 x 64 quadrant of
+// splits, six products per fp32 product, fp32 accumulate: the arithmetic of rpb_mma.h) and a wave accumulates ONE 64 x 64 quadrant of
 // dW (16 tiles of 16 x 16, 96 MFMAs per 32 cells, 64 accumulator registers).  Partial rows as rpb_cell_wgrad's: [stream][128 * 128 + 128],
 // summed by rpb_reduce_partials.
 #include "rpb_cmx.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ float asf(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-// 8 fp32 -> three bf16x8 planes (exact: hi + mid + lo == v)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 struct CwxArgs {
     const float* gs;   // [ncell][128]
@@ -84,10 +51,10 @@ __global__ __launch_bounds__(256, 2) void cwx128s_kernel(CwxArgs a) {
         sc = has_xf ? f32x2{a.xf.invstd[c] * a.xf.gamma[c], a.xf.invstd[c + 1] * a.xf.gamma[c + 1]} : pk2(1.f);
         be = has_xf ? f32x2{a.xf.beta[c], a.xf.beta[c + 1]} - f32x2{a.xf.mean[c], a.xf.mean[c + 1]} * sc : pk2(0.f);
     }
-    const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     // tile (p, q): rows <-> out channel 64 oh + 4 (4 mg + r) + uo(p), columns <-> in channel 64 ih + 4 n + ui(q); p, q = 0, 1: the pair this
     // wave prepared (uo = 2 ih + p, ui = 2 oh + q), p, q = 2, 3: the partner's (uo = 2 (1 - ih) + p - 2, ui = 2 (1 - oh) + q - 2)
-    f32x4v accW[4][4];
+    f32x4 accW[4][4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -191,9 +158,9 @@ __global__ __launch_bounds__(256, 2) void cwx128s_kernel(CwxArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int o = 64 * oh + 4 * (4 * mg + r) + (p ^ (2 * ih));
-            const f32x4v own_first = {accW[p][0][r], accW[p][1][r], accW[p][2][r], accW[p][3][r]};
-            const f32x4v partner_first = {accW[p][2][r], accW[p][3][r], accW[p][0][r], accW[p][1][r]};
-            *reinterpret_cast<f32x4v*>(wp + (long)o * 128 + 64 * ih + 4 * n) = oh ? partner_first : own_first;
+            const f32x4 own_first = {accW[p][0][r], accW[p][1][r], accW[p][2][r], accW[p][3][r]};
+            const f32x4 partner_first = {accW[p][2][r], accW[p][3][r], accW[p][0][r], accW[p][1][r]};
+            *reinterpret_cast<f32x4*>(wp + (long)o * 128 + 64 * ih + 4 * n) = oh ? partner_first : own_first;
         }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {

@@ -9,42 +9,15 @@
 // Epilogue = rpb_gemm_nt's (bias, broadcast vector, GELU / GELU' / ReLU / ReLU', dropout mask or in-kernel Philox dropout,
 // residual), 16 B per lane through a wave-private LDS tile.  Replaces, for K % 64 == 0 and N in {64, 128, 256 k}, the nn.Linear
 // calls listed at rpb_gemm_nt in include/rpb.h.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include "rpb_gemm3x2.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 g3_bf16x8;
-typedef __bf16 g3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned g3_u32x4 __attribute__((ext_vector_type(4)));
 template <int V>
 struct G3IC {
     static constexpr int value = V;
 };
 
 #define G3_BM 128
-
-__device__ __forceinline__ f32x16 g3_mfma(g3_u32x4 a, g3_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g3_bf16x8, a), __builtin_bit_cast(g3_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void g3_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {x0, x1};
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, g3_bf16x2));                 // v_cvt_pk_bf16_f32 (RNE)
-    const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xFFFF0000u)};
-    const f32x2 r1 = v - hf;                                                                  // exact
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, g3_bf16x2));
-    const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xFFFF0000u)};
-    const f32x2 r2 = r1 - mf;                                                                 // exact
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, g3_bf16x2));
-}
-__device__ __forceinline__ void g3_split8(f32x4 v0, f32x4 v1, g3_u32x4& h, g3_u32x4& m, g3_u32x4& l) {
-    unsigned hh[4], mm[4], ll[4];
-    g3_split_pair(v0[0], v0[1], hh[0], mm[0], ll[0]);
-    g3_split_pair(v0[2], v0[3], hh[1], mm[1], ll[1]);
-    g3_split_pair(v1[0], v1[1], hh[2], mm[2], ll[2]);
-    g3_split_pair(v1[2], v1[3], hh[3], mm[3], ll[3]);
-    h = g3_u32x4{hh[0], hh[1], hh[2], hh[3]};
-    m = g3_u32x4{mm[0], mm[1], mm[2], mm[3]};
-    l = g3_u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
 
 // ---------------------------------------------------------------------------------- weights in B-operand order
 // W [N][K] fp32 -> Wz[K/16][3 planes][N/32][64 lanes][8] bf16, lane = (n & 31) + 32 * k-half, element e <-> k = 16 cc + 8 half + e
@@ -57,12 +30,12 @@ __global__ __launch_bounds__(256) void gemm3x_wprep_kernel(const float* __restri
     const long r = idx >> 6;
     const int nt = (int)(r % NT), cc = (int)(r / NT);
     const float* src = W + (long)(nt * 32 + (lane & 31)) * K + cc * 16 + (lane >> 5) * 8;
-    g3_u32x4 h, m, l;
-    g3_split8(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), h, m, l);
+    u32x4 h, m, l;
+    split8_rne(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4), h, m, l);
     const long dst = ((((long)cc * 3) * NT + nt) * 64 + lane) * 8;
-    *reinterpret_cast<g3_u32x4*>(Wz + dst) = h;
-    *reinterpret_cast<g3_u32x4*>(Wz + dst + (long)NT * 512) = m;
-    *reinterpret_cast<g3_u32x4*>(Wz + dst + 2L * NT * 512) = l;
+    *reinterpret_cast<u32x4*>(Wz + dst) = h;
+    *reinterpret_cast<u32x4*>(Wz + dst + (long)NT * 512) = m;
+    *reinterpret_cast<u32x4*>(Wz + dst + 2L * NT * 512) = l;
 }
 
 extern "C" int rpb_gemm3x_wprep(const float* W, void* Wz, int N, int K, void* stream) {
@@ -93,7 +66,7 @@ struct Gemm3xArgs {
 template <int WN>
 __global__ __launch_bounds__(256, 1) void gemm3x_kernel(Gemm3xArgs a) {
     constexpr int KS = 4 / WN, SPS = 4 / KS;                            // K-split factor; my 16-column chunks per stage
-    extern __shared__ g3_u32x4 lds4[];                                  // two stage buffers [3 planes][4 chunks][2 halves][128 rows] x 16 B
+    extern __shared__ u32x4 lds4[];                                  // two stage buffers [3 planes][4 chunks][2 halves][128 rows] x 16 B
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nw = wave % WN, kp = wave / WN;
@@ -112,16 +85,16 @@ __global__ __launch_bounds__(256, 1) void gemm3x_kernel(Gemm3xArgs a) {
     const int nc64 = a.K >> 6;
     const uint16_t* wbase = a.Wz + ((long)(n0 >> 5) * 64 + lane) * 8;
     const long wplane = (long)NT * 512, wchunk = 3 * wplane;
-    auto bload = [&](const uint16_t* src, g3_u32x4 (&b)[2][3]) __attribute__((always_inline)) {
+    auto bload = [&](const uint16_t* src, u32x4 (&b)[2][3]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int tn = 0; tn < 2; ++tn) b[tn][p] = *reinterpret_cast<const g3_u32x4*>(src + p * wplane + tn * 512);
+            for (int tn = 0; tn < 2; ++tn) b[tn][p] = *reinterpret_cast<const u32x4*>(src + p * wplane + tn * 512);
     };
-    g3_u32x4 bc[2][3], bn[2][3];
-    const g3_u32x4* As = lds4;
-    g3_u32x4 ac[3], an[3];
-    auto lda_ = [&](int s, int tm, g3_u32x4 (&av)[3]) __attribute__((always_inline)) {
+    u32x4 bc[2][3], bn[2][3];
+    const u32x4* As = lds4;
+    u32x4 ac[3], an[3];
+    auto lda_ = [&](int s, int tm, u32x4 (&av)[3]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p) av[p] = As[((p * 4 + s) * 2 + half) * G3_BM + tm * 32 + col];
     };
@@ -131,18 +104,18 @@ __global__ __launch_bounds__(256, 1) void gemm3x_kernel(Gemm3xArgs a) {
             if (tm < 3) lda_(s, tm + 1, an);
             else if (more) lda_(s + KS, 0, an);
             __builtin_amdgcn_sched_barrier(0);
-            acc[tm][0] = g3_mfma(ac[2], bc[0][0], acc[tm][0]);          // small terms first; the two column tiles alternate
-            acc[tm][1] = g3_mfma(ac[2], bc[1][0], acc[tm][1]);
-            acc[tm][0] = g3_mfma(ac[0], bc[0][2], acc[tm][0]);
-            acc[tm][1] = g3_mfma(ac[0], bc[1][2], acc[tm][1]);
-            acc[tm][0] = g3_mfma(ac[1], bc[0][1], acc[tm][0]);
-            acc[tm][1] = g3_mfma(ac[1], bc[1][1], acc[tm][1]);
-            acc[tm][0] = g3_mfma(ac[1], bc[0][0], acc[tm][0]);
-            acc[tm][1] = g3_mfma(ac[1], bc[1][0], acc[tm][1]);
-            acc[tm][0] = g3_mfma(ac[0], bc[0][1], acc[tm][0]);
-            acc[tm][1] = g3_mfma(ac[0], bc[1][1], acc[tm][1]);
-            acc[tm][0] = g3_mfma(ac[0], bc[0][0], acc[tm][0]);
-            acc[tm][1] = g3_mfma(ac[0], bc[1][0], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[2], bc[0][0], acc[tm][0]);          // small terms first; the two column tiles alternate
+            acc[tm][1] = mfma32b(ac[2], bc[1][0], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[0], bc[0][2], acc[tm][0]);
+            acc[tm][1] = mfma32b(ac[0], bc[1][2], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[1], bc[0][1], acc[tm][0]);
+            acc[tm][1] = mfma32b(ac[1], bc[1][1], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[1], bc[0][0], acc[tm][0]);
+            acc[tm][1] = mfma32b(ac[1], bc[1][0], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[0], bc[0][1], acc[tm][0]);
+            acc[tm][1] = mfma32b(ac[0], bc[1][1], acc[tm][1]);
+            acc[tm][0] = mfma32b(ac[0], bc[0][0], acc[tm][0]);
+            acc[tm][1] = mfma32b(ac[0], bc[1][0], acc[tm][1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int p = 0; p < 3; ++p) ac[p] = an[p];
@@ -168,8 +141,8 @@ __global__ __launch_bounds__(256, 1) void gemm3x_kernel(Gemm3xArgs a) {
 #define G3_STORE(J)                                                                             \
     {                                                                                           \
         const int idx = tid + J * 256, row = idx >> 3, sh = idx & 7;                            \
-        g3_u32x4 h, m, l;                                                                       \
-        g3_split8(oks##J ? sa##J : zf, oks##J ? sb##J : zf, h, m, l);                                 \
+        u32x4 h, m, l;                                                                       \
+        split8_rne(oks##J ? sa##J : zf, oks##J ? sb##J : zf, h, m, l);                                 \
         dst[(0 * 8 + sh) * G3_BM + row] = h;                                                    \
         dst[(1 * 8 + sh) * G3_BM + row] = m;                                                    \
         dst[(2 * 8 + sh) * G3_BM + row] = l;                                                    \
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void gemm3x_kernel(Gemm3xArgs a) {
         constexpr int j0 = decltype(j0c)::value, j1 = decltype(j1c)::value;
         G3_FOR4(G3_LOAD)
     };
-    auto stage_store = [&](g3_u32x4* dst) __attribute__((always_inline)) { G3_FOR4(G3_STORE) };
+    auto stage_store = [&](u32x4* dst) __attribute__((always_inline)) { G3_FOR4(G3_STORE) };
 
     // epilogue scratch lives behind the two stage buffers (the next tile's first stage is already in one of them)
     float* red = reinterpret_cast<float*>(lds4 + 2 * 24 * G3_BM);       // [(KS-1) * WN slots][2 tiles][16 regs][64 lanes] <= 24 KB

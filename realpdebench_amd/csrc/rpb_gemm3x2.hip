@@ -15,44 +15,17 @@
 //     and one DPP quad broadcast per owner hands every lane the word that holds its (row, column) bit.
 // Not covered (rpb_gemm3x keeps them): mask tensors, N = 64 / 128.
 #include "rpb_gemm3x2.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 g2_bf16x8;
-typedef __bf16 g2_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned g2_u32x4 __attribute__((ext_vector_type(4)));
-
 #define G2_BM 64
-
-__device__ __forceinline__ f32x16 g2_mfma(g2_u32x4 a, g2_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(g2_bf16x8, a), __builtin_bit_cast(g2_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void g2_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {x0, x1};
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, g2_bf16x2));                 // v_cvt_pk_bf16_f32 (RNE)
-    const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xFFFF0000u)};
-    const f32x2 r1 = v - hf;                                                                  // exact
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, g2_bf16x2));
-    const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xFFFF0000u)};
-    const f32x2 r2 = r1 - mf;                                                                 // exact
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, g2_bf16x2));
-}
-__device__ __forceinline__ void g2_split8(f32x4 v0, f32x4 v1, g2_u32x4& h, g2_u32x4& m, g2_u32x4& l) {
-    unsigned hh[4], mm[4], ll[4];
-    g2_split_pair(v0[0], v0[1], hh[0], mm[0], ll[0]);
-    g2_split_pair(v0[2], v0[3], hh[1], mm[1], ll[1]);
-    g2_split_pair(v1[0], v1[1], hh[2], mm[2], ll[2]);
-    g2_split_pair(v1[2], v1[3], hh[3], mm[3], ll[3]);
-    h = g2_u32x4{hh[0], hh[1], hh[2], hh[3]};
-    m = g2_u32x4{mm[0], mm[1], mm[2], mm[3]};
-    l = g2_u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
 
 // ACT: G2Args::act; RES: a residual is added; the epilogue is straight-line code per instantiation (with run-time switches its 64
 // unrolled elements spill 70-90 registers)
 // NB: 32-column blocks per wave -- 2: the workgroup covers 256 columns; 1: 128 columns (N = 128, 384, ..: short products, HBM-bound)
 template <int ACT, bool RES, bool DROP, int NB = 2>
 __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
-    extern __shared__ g2_u32x4 lds4[];                                  // two stage buffers [3 planes][8 pieces of 8 k][64 rows] x 16 B
+    extern __shared__ u32x4 lds4[];                                  // two stage buffers [3 planes][8 pieces of 8 k][64 rows] x 16 B
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long ntiles = (a.M + G2_BM - 1) / G2_BM;
@@ -75,11 +48,11 @@ __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
     const int ldo4 = a.ldo * 4;
     const int lane_off = (4 * half * a.ldo + col) * 4;                  // byte offset of (row 4 * half, column col) inside a 32 x 32 block
 
-    auto bload = [&](const uint16_t* src, g2_u32x4 (&b)[NB][3]) __attribute__((always_inline)) {
+    auto bload = [&](const uint16_t* src, u32x4 (&b)[NB][3]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int tn = 0; tn < NB; ++tn) b[tn][p] = *reinterpret_cast<const g2_u32x4*>(src + p * wplane + tn * 512);
+            for (int tn = 0; tn < NB; ++tn) b[tn][p] = *reinterpret_cast<const u32x4*>(src + p * wplane + tn * 512);
     };
     // ---- A staging: 64 rows x 8 pieces of 8 columns per stage = 2 pieces (2 float4 loads each) per thread
     f32x4 sa0 = zf, sb0 = zf, sa1 = zf, sb1 = zf;
@@ -101,20 +74,20 @@ __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
             if (!ok) sa1 = sb1 = zf;
         }
     };
-    auto stage_store = [&](g2_u32x4* dst) __attribute__((always_inline)) {
+    auto stage_store = [&](u32x4* dst) __attribute__((always_inline)) {
         const int row = tid >> 3, sh = tid & 7;
-        g2_u32x4 h, m, l;
-        g2_split8(sa0, sb0, h, m, l);
+        u32x4 h, m, l;
+        split8_rne(sa0, sb0, h, m, l);
         dst[(0 * 8 + sh) * G2_BM + row] = h;
         dst[(1 * 8 + sh) * G2_BM + row] = m;
         dst[(2 * 8 + sh) * G2_BM + row] = l;
-        g2_split8(sa1, sb1, h, m, l);
+        split8_rne(sa1, sb1, h, m, l);
         dst[(0 * 8 + sh) * G2_BM + 32 + row] = h;
         dst[(1 * 8 + sh) * G2_BM + 32 + row] = m;
         dst[(2 * 8 + sh) * G2_BM + 32 + row] = l;
     };
 
-    g2_u32x4 bc[NB][3], bn[NB][3];                                          // W operands of the current / next 16-k chunk (chunks wrap: tile after tile)
+    u32x4 bc[NB][3], bn[NB][3];                                          // W operands of the current / next 16-k chunk (chunks wrap: tile after tile)
     bload(wbase, bc);
     stage_load(tile * G2_BM, 0);
     stage_store(lds4);
@@ -138,11 +111,11 @@ __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
             const bool last = c + 1 == nc64;
             const bool more = !last || next_tile;                       // a next stage exists (of this tile or of the next one)
             if (more) stage_load(last ? m0n : m0, last ? 0 : c + 1);
-            const g2_u32x4* As = lds4 + buf * 24 * G2_BM;
+            const u32x4* As = lds4 + buf * 24 * G2_BM;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 bload(wbase + (long)((s == 3 && last) ? 0 : c * 4 + s + 1) * wchunk, bn);
-                g2_u32x4 av[2][3];
+                u32x4 av[2][3];
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -150,10 +123,10 @@ __global__ __launch_bounds__(256, 2) void gemm3x2_kernel(G2Args a) {
                 __builtin_amdgcn_sched_barrier(0);                      // loads of chunk s + 1 stay here: hoisted over the unrolled chunks they spill
                 // (A plane, W plane): lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi -- small terms first; four accumulators alternate
 #define G2_MF(PA, PB)                                                               \
-    acc[0][0] = g2_mfma(av[0][PA], bc[0][PB], acc[0][0]);                           \
-    if (NB == 2) acc[0][NB - 1] = g2_mfma(av[0][PA], bc[NB - 1][PB], acc[0][NB - 1]); \
-    acc[1][0] = g2_mfma(av[1][PA], bc[0][PB], acc[1][0]);                           \
-    if (NB == 2) acc[1][NB - 1] = g2_mfma(av[1][PA], bc[NB - 1][PB], acc[1][NB - 1]);
+    acc[0][0] = mfma32b(av[0][PA], bc[0][PB], acc[0][0]);                           \
+    if (NB == 2) acc[0][NB - 1] = mfma32b(av[0][PA], bc[NB - 1][PB], acc[0][NB - 1]); \
+    acc[1][0] = mfma32b(av[1][PA], bc[0][PB], acc[1][0]);                           \
+    if (NB == 2) acc[1][NB - 1] = mfma32b(av[1][PA], bc[NB - 1][PB], acc[1][NB - 1]);
                 G2_MF(2, 0) G2_MF(0, 2) G2_MF(1, 1) G2_MF(1, 0) G2_MF(0, 1) G2_MF(0, 0)
 #undef G2_MF
                 __builtin_amdgcn_sched_barrier(0);

@@ -13,30 +13,11 @@
 // 128 accumulator registers, two workgroups per CU), token ranges are dealt to workgroups (split-K) and the partials are finished by
 // rpb_reduce_partials like rpb_gemm_tn's.  Workgroups that share a token range (different output tiles) sit on the same XCD, so the
 // operand they share is read from HBM once and from that XCD's L2 afterwards.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 t3_bf16x8;
-typedef __bf16 t3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned t3_u32x4 __attribute__((ext_vector_type(4)));
 
 #define T3_TILE 256       // outputs per workgroup: T3_TN x T3_TILE
 #define T3_STEP 16        // tokens per step = K of one v_mfma_f32_32x32x16_bf16
-
-__device__ __forceinline__ f32x16 t3_mfma(t3_u32x4 a, t3_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(t3_bf16x8, a), __builtin_bit_cast(t3_bf16x8, b), c, 0, 0, 0);
-}
-// (x0, x1) -> one dword per plane (round-to-nearest-even bf16; the residuals are exact, so hi + mid + lo == x to 2^-24 relative)
-__device__ __forceinline__ void t3_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {x0, x1};
-    h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, t3_bf16x2));
-    const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xFFFF0000u)};
-    const f32x2 r1 = v - hf;
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, t3_bf16x2));
-    const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xFFFF0000u)};
-    const f32x2 r2 = r1 - mf;
-    l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, t3_bf16x2));
-}
 
 struct T3Args {
     const float* G;     // [M][ldg]
@@ -56,7 +37,7 @@ __global__ __launch_bounds__(256, 2) void gemm3x_tn_kernel(T3Args a) {
     constexpr int NI = T3_TN / 64;                                          // 32-row blocks of a wave's G range (wave grid 2 x 2)
     constexpr int GE = T3_TN * T3_STEP / 256;                               // G values a thread stages per step: 8
     constexpr int BUF = 3 * 2 * (T3_TN + T3_TILE);                          // 16 B units of one step buffer: [G: plane][half][T3_TN] then [A: plane][half][256]
-    extern __shared__ t3_u32x4 lds4[];
+    extern __shared__ u32x4 lds4[];
     const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave >> 1, wk = wave & 1;                             // the wave's (T3_TN / 2) x 128 quadrant of the tile
@@ -94,16 +75,16 @@ __global__ __launch_bounds__(256, 2) void gemm3x_tn_kernel(T3Args a) {
         for (int j = 0; j < T3_STEP; ++j) av[j] = buf_load_f32(ra, aofs + j * ab, 0);
     };
     // operand unit (plane p, token half hf, channel c) of operand o in step buffer b
-    auto unit = [&](int b, int o, int p, int hf, int c) __attribute__((always_inline)) -> t3_u32x4* {
+    auto unit = [&](int b, int o, int p, int hf, int c) __attribute__((always_inline)) -> u32x4* {
         return lds4 + b * BUF + (o == 0 ? (p * 2 + hf) * T3_TN : 6 * T3_TN + (p * 2 + hf) * T3_TILE) + c;
     };
     auto split_store = [&](const float* v, int b, int o, int hf, int c) __attribute__((always_inline)) {
         unsigned h[4], m[4], l[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) t3_split_pair(v[2 * e], v[2 * e + 1], h[e], m[e], l[e]);
-        *unit(b, o, 0, hf, c) = t3_u32x4{h[0], h[1], h[2], h[3]};
-        *unit(b, o, 1, hf, c) = t3_u32x4{m[0], m[1], m[2], m[3]};
-        *unit(b, o, 2, hf, c) = t3_u32x4{l[0], l[1], l[2], l[3]};
+        for (int e = 0; e < 4; ++e) rpb_split_pair_rne(v[2 * e], v[2 * e + 1], h[e], m[e], l[e]);
+        *unit(b, o, 0, hf, c) = u32x4{h[0], h[1], h[2], h[3]};
+        *unit(b, o, 1, hf, c) = u32x4{m[0], m[1], m[2], m[3]};
+        *unit(b, o, 2, hf, c) = u32x4{l[0], l[1], l[2], l[3]};
     };
     auto store_step = [&](int b) __attribute__((always_inline)) {
         split_store(gv, b, 0, ghf, gch);
@@ -115,12 +96,12 @@ __global__ __launch_bounds__(256, 2) void gemm3x_tn_kernel(T3Args a) {
         }
     };
     auto compute = [&](int b) __attribute__((always_inline)) {
-        t3_u32x4 bo[4][3];                                              // the wave's four 32-column blocks of A, three planes
+        u32x4 bo[4][3];                                              // the wave's four 32-column blocks of A, three planes
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int p = 0; p < 3; ++p) bo[j][p] = *unit(b, 1, p, half, wk * 128 + j * 32 + col);
-        t3_u32x4 ao[2][3];
+        u32x4 ao[2][3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) ao[0][p] = *unit(b, 0, p, half, wn * (T3_TN / 2) + col);
 #pragma unroll
@@ -131,10 +112,10 @@ __global__ __launch_bounds__(256, 2) void gemm3x_tn_kernel(T3Args a) {
             }
             // (G plane, A plane): lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi -- small terms first; the four column blocks alternate
 #define T3_MF(PA, PB)                                                   \
-    acc[i][0] = t3_mfma(ao[i & 1][PA], bo[0][PB], acc[i][0]);           \
-    acc[i][1] = t3_mfma(ao[i & 1][PA], bo[1][PB], acc[i][1]);           \
-    acc[i][2] = t3_mfma(ao[i & 1][PA], bo[2][PB], acc[i][2]);           \
-    acc[i][3] = t3_mfma(ao[i & 1][PA], bo[3][PB], acc[i][3]);
+    acc[i][0] = mfma32b(ao[i & 1][PA], bo[0][PB], acc[i][0]);           \
+    acc[i][1] = mfma32b(ao[i & 1][PA], bo[1][PB], acc[i][1]);           \
+    acc[i][2] = mfma32b(ao[i & 1][PA], bo[2][PB], acc[i][2]);           \
+    acc[i][3] = mfma32b(ao[i & 1][PA], bo[3][PB], acc[i][3]);
             T3_MF(2, 0) T3_MF(0, 2) T3_MF(1, 1) T3_MF(1, 0) T3_MF(0, 1) T3_MF(0, 0)
 #undef T3_MF
         }

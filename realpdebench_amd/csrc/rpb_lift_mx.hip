@@ -10,37 +10,14 @@
 //  * a wave walks whole (b,t,h) lines of the padded tensor; a wave tile = 32 consecutive cells = two 16-row MFMA tiles.  Lane
 //    (m = lane & 15, kg = lane >> 4) holds features 8 kg .. 8 kg + 7 of cell m: lane groups 0 / 1 load 32 B of the cell's inputs each
 //    (every load instruction reads 16 whole 64 B cell rows), group 2 forms (gt, gh, gw[w], 1, 0, 0, 0, 0), group 3 is zero;
-//  * both operands as three bf16 planes, six products (fp32 grade, rpb_cmx.hip): 48 MFMAs per 32 cells hide under the tile's 6 KB of HBM
+//  * both operands as three bf16 planes, six products (fp32 grade, rpb_mma.h): 48 MFMAs per 32 cells hide under the tile's 6 KB of HBM
 //    traffic, and the result equals the fp32 lift's to ~1e-7, i.e. the stored bf16 values differ from round(fp32 lift) only where the fp32
 //    result sits within ~1e-5 of a rounding boundary;
 //  * the MFMA column n of output tile t stands for channel 4 n + t (as rpb_cmx.hip): a lane's accumulators are 4 consecutive channels of
 //    4 cells -> one 8 B store per (tile, row) = 16 whole 128 B cell rows per instruction;
 //  * cells w >= W of an inside line and all cells of a pad line are written as zeros (the consumers read the whole padded tensor).
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-namespace {
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        unsigned ph, pm, pl;
-        rpb_split_pair(v[2 * q], v[2 * q + 1], ph, pm, pl);
-        uh[q] = ph;
-        um[q] = pm;
-        ul[q] = pl;
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-}  // namespace
 
 struct LiftMxArgs {
     const float* x;        // [B][T][H][W][16]
@@ -96,8 +73,8 @@ __global__ __launch_bounds__(LMX_WAVES * 64) void lift_mx_kernel(LiftMxArgs a) {
         if (kg < 2) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                xa[j][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (16 * j + m) * 64 + kg * 32, 0, RPB_STREAM_AUX));
-                xa[j][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (16 * j + m) * 64 + kg * 32 + 16, 0, RPB_STREAM_AUX));
+                xa[j][0] = ld16<RPB_STREAM_AUX>(rx, (16 * j + m) * 64 + kg * 32);
+                xa[j][1] = ld16<RPB_STREAM_AUX>(rx, (16 * j + m) * 64 + kg * 32 + 16);
             }
         }
         for (int q = 0; q < TQ; ++q) {
@@ -115,7 +92,7 @@ __global__ __launch_bounds__(LMX_WAVES * 64) void lift_mx_kernel(LiftMxArgs a) {
                 const int w = 32 * q + 16 * j + m;
                 float v[8];
                 if (kg < 2) {
-                    const f32x4v v0 = __builtin_bit_cast(f32x4v, xa[j][0]), v1 = __builtin_bit_cast(f32x4v, xa[j][1]);
+                    const f32x4 v0 = __builtin_bit_cast(f32x4, xa[j][0]), v1 = __builtin_bit_cast(f32x4, xa[j][1]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         v[e] = v0[e];
@@ -136,16 +113,16 @@ __global__ __launch_bounds__(LMX_WAVES * 64) void lift_mx_kernel(LiftMxArgs a) {
             if (kg < 2 && q + 1 < TQX) {                 // the next tile's inputs: in flight during the products and the stores
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    xa[j][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (32 * (q + 1) + 16 * j + m) * 64 + kg * 32, 0, RPB_STREAM_AUX));
-                    xa[j][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (32 * (q + 1) + 16 * j + m) * 64 + kg * 32 + 16, 0, RPB_STREAM_AUX));
+                    xa[j][0] = ld16<RPB_STREAM_AUX>(rx, (32 * (q + 1) + 16 * j + m) * 64 + kg * 32);
+                    xa[j][1] = ld16<RPB_STREAM_AUX>(rx, (32 * (q + 1) + 16 * j + m) * 64 + kg * 32 + 16);
                 }
             }
-            f32x4v acc[2][4];
+            f32x4 acc[2][4];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) {
-                    f32x4v c = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 c = {0.f, 0.f, 0.f, 0.f};
                     c = mfma16(Ah[j], Bl[tt], c);
                     c = mfma16(Al[j], Bh[tt], c);
                     c = mfma16(Am[j], Bm[tt], c);

@@ -11,7 +11,7 @@
 // so one workgroup owns one mode, streams its 32 KB (C=64) weight tile exactly once with 512 B
 // coalesced rows, and keeps the [B][2][C] coefficient tile of that mode in LDS (broadcast reads).
 // At B=32 this kernel is a pure weight stream: 100.7 MB per layer against ~50 MB of coefficients.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
 
 #define MC_THREADS 256
@@ -184,7 +184,6 @@ __global__ __launch_bounds__(MC_THREADS) void mode_wgrad_kernel(const float* __r
     }
 }
 
-
 // ---- C = 64 on the fp32 matrix pipe: per mode the complex contraction is a real GEMM with the composite [[wr, wi], [-wi, wr]]
 // (forward: [B x 128] x [128 x 128]; dgrad: the conjugate transpose; wgrad: [128 x 2B]^T products with K = batch).  One workgroup per
 // mode, 4 waves x 64 MFMAs of 32x32x2; the mode's coefficient tile(s) and its weight tile are staged in LDS planar and padded, so the
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(256) void mode_mfma_kernel(const float* __restrict_
     }
 }
 
-// ---- C = 64 on the bf16 matrix pipe from split fp32 operands (round 4; the fp32-grade arithmetic of rpb_cmx.hip: three truncation
+// ---- C = 64 on the bf16 matrix pipe from split fp32 operands (round 4; the fp32-grade arithmetic of rpb_mma.h: three truncation
 // planes per operand, six products, fp32 accumulation).  The fp32-MFMA kernel above needs 128 matrix instructions of 64 cycles per wave
 // and mode (8.2 k cycles) for a tile whose HBM time is ~2.5 k cycles: 0.06-0.095 ms per launch for 0.2 GB.  Here the same composite
 // GEMMs take 96 instructions of 16 cycles per wave; the operands are gathered from the fp32 tiles staged in LDS straight into MFMA
@@ -294,43 +293,27 @@ __global__ __launch_bounds__(256) void mode_mfma_kernel(const float* __restrict_
 //   fwd    D[b][(ro,o)] = sum_(ri,i) X[b][(ri,i)] * s W[i][o][ri ^ ro]         s = -1 for (ri, ro) = (1, 0)      M = 32, N = 128, K = 128
 //   dgrad  D[b][(ri,i)] = sum_(ro,o) gY[b][(ro,o)] * s W[i][o][ro ^ ri]        s = -1 for (ro, ri) = (0, 1)
 //   wgrad  D[i][(part,o)] = sum_(ri,b) X[b][ri][i] * G(part)[(ri,b)][o]        G(re) = (gYr, gYi), G(im) = (gYi, -gYr)   M = 64, N = 128, K = 64
-typedef __attribute__((ext_vector_type(8))) __bf16 mbf16x8;
-typedef unsigned mu32x4 __attribute__((ext_vector_type(4)));
 namespace {
-__device__ __forceinline__ float m_trunc(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned m_pack(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
 struct Planes {
-    mbf16x8 h, m, l;
+    bf16x8 h, m, l;
 };
 __device__ __forceinline__ Planes m_split(const float (&v)[8]) {
-    mu32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    return Planes{__builtin_bit_cast(mbf16x8, uh), __builtin_bit_cast(mbf16x8, um), __builtin_bit_cast(mbf16x8, ul)};
+    Planes p;
+    split8(v, p.h, p.m, p.l);
+    return p;
 }
 __device__ __forceinline__ Planes m_neg(Planes p) {            // -x: flip the sign of every plane (exact)
-    const mu32x4 sgn = {0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
-    return Planes{__builtin_bit_cast(mbf16x8, __builtin_bit_cast(mu32x4, p.h) ^ sgn), __builtin_bit_cast(mbf16x8, __builtin_bit_cast(mu32x4, p.m) ^ sgn),
-                  __builtin_bit_cast(mbf16x8, __builtin_bit_cast(mu32x4, p.l) ^ sgn)};
+    const u32x4 sgn = {0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
+    return Planes{__builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, p.h) ^ sgn), __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, p.m) ^ sgn),
+                  __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, p.l) ^ sgn)};
 }
-__device__ __forceinline__ f32x4 m_mac6(const Planes& a, const Planes& b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, c, 0, 0, 0);
+__device__ __forceinline__ f32x4 m_mac6(const Planes& a, const Planes& b, f32x4 c) {       // six products, small terms first
+    c = mfma16(a.h, b.l, c);
+    c = mfma16(a.l, b.h, c);
+    c = mfma16(a.m, b.m, c);
+    c = mfma16(a.h, b.m, c);
+    c = mfma16(a.m, b.h, c);
+    c = mfma16(a.h, b.h, c);
     return c;
 }
 }  // namespace

@@ -21,16 +21,11 @@
 //     (d fc1 = gamma_c M + beta_c db1, exact algebra: a = gamma shat + beta) -- rpb_head_bwd_finalize does both on 128 x 64 numbers.
 //
 // All three contractions run on v_mfma_f32_16x16x32_bf16 from three-plane truncation splits (six products, fp32 accumulation:
-// the fp32-grade arithmetic of rpb_cmx.hip / rpb_pjx.hip).  One wave owns a full 128 x 64 weight-gradient accumulator (128
+// the fp32-grade arithmetic of rpb_mma.h).  One wave owns a full 128 x 64 weight-gradient accumulator (128
 // registers), so the kernel runs one wave per SIMD with the 512-register budget; HBM traffic is s (crop) + gout in, g out.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include "rpb_pjf.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 #define PF_HID 128
 #define PF_WAVES 4
@@ -41,40 +36,9 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // (~4 cycles per instruction + 12 more per MFMA), not by missing overlap.
 
 namespace {
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // channel of contraction index (ks, kg, e) under the 4 x 16 B-per-cell load pattern (see rpb_cmx.hip)
 __device__ __forceinline__ int chan_of(int ks, int kg, int e) { return 16 * (2 * ks + (e >> 2)) + 4 * kg + (e & 3); }
 }  // namespace
-
 
 // six products of the three-plane split, small terms first, NC independent accumulation chains advancing together
 #define PF_MAC6(NC, ACC, AH, AM, AL, BH, BM, BL)                                       \
@@ -137,7 +101,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
     const long nslots = (long)gridDim.x * PF_WAVES;
     const long slot = (long)blockIdx.x * PF_WAVES + wave;
     const unsigned line_bytes = (unsigned)cm.Wp * 256u;
-    const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 
     // ---- pass 1: lines in the zero-pad margin (t >= T or h >= H) of the padded gradient tensor
     {
@@ -147,7 +111,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
             const int t = (int)((g / cm.Hp) % cm.Tp);
             if (h < cm.H && t < cm.T) continue;                      // uniform
             const rsrc_t ro = make_rsrc(p.g + g * cm.Wp * 64, line_bytes);
-            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16(z4, ro, off);
+            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16<0>(z4, ro, off);
         }
     }
 
@@ -167,7 +131,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
     float b2v[DOT], lacc = 0.f;
 #pragma unroll
     for (int j = 0; j < DOT; ++j) b2v[j] = (LOSS && j < DO) ? p.b2[j] : 0.f;
-    f32x4v acc3[8][4];                                   // M: [hidden tile t][channel tile u]; row 16 t + 4 mg + r, column = channel 4 n16 + u
+    f32x4 acc3[8][4];                                   // M: [hidden tile t][channel tile u]; row 16 t + 4 mg + r, column = channel 4 n16 + u
 #pragma unroll
     for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -187,12 +151,12 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xa[j][i] = ld16(rx, (32 * q + 16 * j + n16) * 256 + i * 64 + kg * 16);
+            for (int i = 0; i < 4; ++i) xa[j][i] = ld16<0>(rx, (32 * q + 16 * j + n16) * 256 + i * 64 + kg * 16);
     };
     auto issue_xr = [&](int pl, int q) {
         const rsrc_t rx = make_rsrc(p.s + (long)pl * cm.Wp * 64, (unsigned)cm.W * 256u);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xr[e] = ld16(rx, (32 * q + 16 * (e >> 2) + 4 * kg + (e & 3)) * 256 + n16 * 16);
+        for (int e = 0; e < 8; ++e) xr[e] = ld16<0>(rx, (32 * q + 16 * (e >> 2) + 4 * kg + (e & 3)) * 256 + n16 * 16);
     };
     auto issue_go = [&](int gl, int q) {                 // gl: CROPPED line, < 0 past the end
         const bool ok = gl >= 0;
@@ -200,8 +164,8 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
         if (DOT == 2 && EXACT) {                         // the lane's cells 16 j + 4 kg .. + 3 are 32 contiguous bytes of gout
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const f32x4v w0 = __builtin_bit_cast(f32x4v, ld16(rg, (32 * q + 16 * j + 4 * kg) * 8));
-                const f32x4v w1 = __builtin_bit_cast(f32x4v, ld16(rg, (32 * q + 16 * j + 4 * kg) * 8 + 16));
+                const f32x4 w0 = __builtin_bit_cast(f32x4, ld16<0>(rg, (32 * q + 16 * j + 4 * kg) * 8));
+                const f32x4 w1 = __builtin_bit_cast(f32x4, ld16<0>(rg, (32 * q + 16 * j + 4 * kg) * 8 + 16));
                 go[4 * j][0] = w0[0], go[4 * j][1] = w0[1], go[4 * j + 1][0] = w0[2], go[4 * j + 1][1] = w0[3];
                 go[4 * j + 2][0] = w1[0], go[4 * j + 2][1] = w1[1], go[4 * j + 3][0] = w1[2], go[4 * j + 3][1] = w1[3];
             }
@@ -211,7 +175,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
         for (int e = 0; e < 8; ++e) {
             const int cell = 32 * q + 16 * (e >> 2) + 4 * kg + (e & 3);
             if (DOT == 4 && EXACT) {
-                const f32x4v w = __builtin_bit_cast(f32x4v, ld16(rg, cell * 16));
+                const f32x4 w = __builtin_bit_cast(f32x4, ld16<0>(rg, cell * 16));
 #pragma unroll
                 for (int j = 0; j < 4; ++j) go[e][j] = w[j];
             } else {
@@ -247,7 +211,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
             // matrix and vector work only overlap when they alternate in the instruction stream: each region pairs the MFMAs of one
             // stage with independent VALU work of the neighbouring stage and asks the scheduler for that interleaving
             // (sched_group_barrier).  Measured before: 35 % matrix pipe busy, VALU and MFMA co-executing 3 % of the time.
-            f32x4v acc[2][8];
+            f32x4 acc[2][8];
             bf16x8 Ah[2][2], Am[2][2], Al[2][2];                     // [ks][j]: a in A-operand layout, split
             auto split_A = [&](int ks) {
 #pragma unroll
@@ -256,12 +220,12 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #pragma unroll
                     for (int hf = 0; hf < 2; ++hf) {
                         const int i = 2 * ks + hf;
-                        const f32x4v xv = __builtin_bit_cast(f32x4v, xa[j][i]);
-                        const f32x4v mu = *reinterpret_cast<const f32x4v*>(xfl + 16 * i + 4 * kg);
-                        const f32x4v is = *reinterpret_cast<const f32x4v*>(xfl + 64 + 16 * i + 4 * kg);
-                        const f32x4v ga = *reinterpret_cast<const f32x4v*>(xfl + 128 + 16 * i + 4 * kg);
-                        const f32x4v be = *reinterpret_cast<const f32x4v*>(xfl + 192 + 16 * i + 4 * kg);
-                        const f32x4v z = bn4(xv, mu, is, ga, be);
+                        const f32x4 xv = __builtin_bit_cast(f32x4, xa[j][i]);
+                        const f32x4 mu = *reinterpret_cast<const f32x4*>(xfl + 16 * i + 4 * kg);
+                        const f32x4 is = *reinterpret_cast<const f32x4*>(xfl + 64 + 16 * i + 4 * kg);
+                        const f32x4 ga = *reinterpret_cast<const f32x4*>(xfl + 128 + 16 * i + 4 * kg);
+                        const f32x4 be = *reinterpret_cast<const f32x4*>(xfl + 192 + 16 * i + 4 * kg);
+                        const f32x4 z = bn4(xv, mu, is, ga, be);
 #pragma unroll
                         for (int c = 0; c < 4; ++c) v[4 * hf + c] = z[c];
                     }
@@ -295,25 +259,25 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
             };
             // gh = (fc2^T gout) * gelu'(u) in place for hidden tile t of row tile j; d fc2, d b1: per-lane sums over the lane's cells
             auto act = [&](int j, int t) {
-                const f32x4v u = acc[j][t];                          // rows = cells 16 j + 4 kg + r  <->  go[4 j + r]
+                const f32x4 u = acc[j][t];                          // rows = cells 16 j + 4 kg + r  <->  go[4 j + r]
                 f32x2 e0, e1;
                         fast_erf2x2(u.lo * pk2(0.70710678118654752440f), u.hi * pk2(0.70710678118654752440f), e0, e1);
-                const f32x4v cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
-                const f32x4v q2 = (f32x4v{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
-                f32x4v ex;
+                const f32x4 cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
+                const f32x4 q2 = (f32x4{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
+                f32x4 ex;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ex[r] = __builtin_amdgcn_exp2f(q2[r]);
-                const f32x4v vv = u * cdf;
-                const f32x4v dd = cdf + u * (ex * 0.39894228040143267794f);
-                f32x4v gp = z4;
+                const f32x4 vv = u * cdf;
+                const f32x4 dd = cdf + u * (ex * 0.39894228040143267794f);
+                f32x4 gp = z4;
 #pragma unroll
                 for (int jj = 0; jj < DOT; ++jj) {
-                    const f32x4v gv = {go[4 * j][jj], go[4 * j + 1][jj], go[4 * j + 2][jj], go[4 * j + 3][jj]};
+                    const f32x4 gv = {go[4 * j][jj], go[4 * j + 1][jj], go[4 * j + 2][jj], go[4 * j + 3][jj]};
                     gp += gv * w2l[jj * PF_HID + 16 * t + n16];
-                    const f32x4v pr = gv * vv;
+                    const f32x4 pr = gv * vv;
                     dw2[jj][t] += (pr[0] + pr[1]) + (pr[2] + pr[3]);
                 }
-                const f32x4v gh = gp * dd;                           // cells >= W: gout == 0 -> gh == 0
+                const f32x4 gh = gp * dd;                           // cells >= W: gout == 0 -> gh == 0
                 acc[j][t] = gh;
                 db1[t] += (gh[0] + gh[1]) + (gh[2] + gh[3]);
             };
@@ -324,7 +288,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     const float bv = b1l[16 * t + n16];
-                    acc[j][t] = f32x4v{bv, bv, bv, bv};
+                    acc[j][t] = f32x4{bv, bv, bv, bv};
                 }
             split_A(0);
             __builtin_amdgcn_sched_barrier(0);
@@ -343,7 +307,7 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     if (j == 1) issue_xr(pl, q);                                      // (held back: registers) in flight during the second row tile
-                    f32x4v VV[8];
+                    f32x4 VV[8];
                     float po[4][DOT];
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -351,12 +315,12 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
                         for (int jj = 0; jj < DOT; ++jj) po[r][jj] = 0.f;
 #pragma unroll
                     for (int t = 0; t < 8; ++t) {
-                        const f32x4v u = acc[j][t];
+                        const f32x4 u = acc[j][t];
                         f32x2 e0, e1;
                         fast_erf2x2(u.lo * pk2(0.70710678118654752440f), u.hi * pk2(0.70710678118654752440f), e0, e1);
-                        const f32x4v cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
-                        const f32x4v q2 = (f32x4v{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
-                        f32x4v ex;
+                        const f32x4 cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
+                        const f32x4 q2 = (f32x4{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
+                        f32x4 ex;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ex[r] = __builtin_amdgcn_exp2f(q2[r]);
                         VV[t] = u * cdf;
@@ -386,15 +350,15 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
                     }
 #pragma unroll
                     for (int t = 0; t < 8; ++t) {
-                        f32x4v gp = z4;
+                        f32x4 gp = z4;
 #pragma unroll
                         for (int jj = 0; jj < DOT; ++jj) {
-                            const f32x4v gv = {go[4 * j][jj], go[4 * j + 1][jj], go[4 * j + 2][jj], go[4 * j + 3][jj]};
+                            const f32x4 gv = {go[4 * j][jj], go[4 * j + 1][jj], go[4 * j + 2][jj], go[4 * j + 3][jj]};
                             gp += gv * w2l[jj * PF_HID + 16 * t + n16];
-                            const f32x4v pr = gv * VV[t];
+                            const f32x4 pr = gv * VV[t];
                             dw2[jj][t] += (pr[0] + pr[1]) + (pr[2] + pr[3]);
                         }
-                        const f32x4v gh = gp * acc[j][t];
+                        const f32x4 gh = gp * acc[j][t];
                         acc[j][t] = gh;
                         db1[t] += (gh[0] + gh[1]) + (gh[2] + gh[3]);
                         if (t & 1) __builtin_amdgcn_sched_barrier(0);
@@ -424,10 +388,10 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
             // ---- region 4: M += gh^T shat: contraction over the 32 cells; lane group kg holds cells {4 kg + r, 16 + 4 kg + r}
             {
                 bf16x8 Xh[4], Xm[4], Xl[4];                          // shat in B-operand layout: column n16 of tile u = channel 4 n16 + u
-                const f32x4v bmu = *reinterpret_cast<const f32x4v*>(xfl + 4 * n16), bis = *reinterpret_cast<const f32x4v*>(xfl + 64 + 4 * n16);
-                f32x4v sh[8];
+                const f32x4 bmu = *reinterpret_cast<const f32x4*>(xfl + 4 * n16), bis = *reinterpret_cast<const f32x4*>(xfl + 64 + 4 * n16);
+                f32x4 sh[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) sh[e] = (__builtin_bit_cast(f32x4v, xr[e]) - bmu) * bis;     // rows of cells >= W: gh == 0 there
+                for (int e = 0; e < 8; ++e) sh[e] = (__builtin_bit_cast(f32x4, xr[e]) - bmu) * bis;     // rows of cells >= W: gh == 0 there
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     float v[8];
@@ -482,13 +446,13 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                f32x4v acc2[4];
+                f32x4 acc2[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) acc2[u] = z4;
                 bf16x8 Ah2[2], Am2[2], Al2[2];
                 auto split_T = [&](int s) {
-                    const f32x4v t0 = *reinterpret_cast<const f32x4v*>(Tw + n16 * PF_TS + 32 * s + 8 * kg);
-                    const f32x4v t1 = *reinterpret_cast<const f32x4v*>(Tw + n16 * PF_TS + 32 * s + 8 * kg + 4);
+                    const f32x4 t0 = *reinterpret_cast<const f32x4*>(Tw + n16 * PF_TS + 32 * s + 8 * kg);
+                    const f32x4 t1 = *reinterpret_cast<const f32x4*>(Tw + n16 * PF_TS + 32 * s + 8 * kg + 4);
                     float v[8];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
@@ -533,13 +497,13 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
                 // row 4 mg + r of the row tile = cell 32 q + 16 j + 4 kg + r; the lane's 4 column tiles are channels 4 n16 .. 4 n16 + 3
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const f32x4v o = {acc2[0][r], acc2[1][r], acc2[2][r], acc2[3][r]};
-                    st16(o, ro, (32 * q + 16 * j + 4 * kg + r) * 256 + n16 * 16);      // cells >= Wp: dropped; W .. Wp-1: zeros (gh == 0)
+                    const f32x4 o = {acc2[0][r], acc2[1][r], acc2[2][r], acc2[3][r]};
+                    st16<0>(o, ro, (32 * q + 16 * j + 4 * kg + r) * 256 + n16 * 16);      // cells >= Wp: dropped; W .. Wp-1: zeros (gh == 0)
                 }
             }
         }
         // margin cells 32 TQ .. Wp - 1 of the line (cells W .. 32 TQ - 1 were written as zeros by the last tile)
-        for (int off = TQ * 32 * 256 + lane * 16; off < (int)line_bytes; off += 1024) st16(z4, ro, off);
+        for (int off = TQ * 32 * 256 + lane * 16; off < (int)line_bytes; off += 1024) st16<0>(z4, ro, off);
     }
 
     if (LOSS) {
@@ -552,8 +516,8 @@ __global__ __launch_bounds__(PF_WAVES * 64, 1) void pjf_kernel(PjfArgs p) {
     for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const f32x4v o = {acc3[t][0][r], acc3[t][1][r], acc3[t][2][r], acc3[t][3][r]};
-            *reinterpret_cast<f32x4v*>(part + (16 * t + 4 * kg + r) * 64 + 4 * n16) = o;
+            const f32x4 o = {acc3[t][0][r], acc3[t][1][r], acc3[t][2][r], acc3[t][3][r]};
+            *reinterpret_cast<f32x4*>(part + (16 * t + 4 * kg + r) * 64 + 4 * n16) = o;
         }
     // per-lane sums over cells: the four lane groups hold different cells of the same hidden units -> add over kg
 #pragma unroll

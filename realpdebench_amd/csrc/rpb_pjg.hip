@@ -20,14 +20,8 @@
 //                                              B = planes of a second, B-layout view of the tile (lane = channel pair 2 n, 2 n + 1)
 //   g^T[chan][cell]     = W1^T gh^T            A = W1D planes from LDS, B = gh planes read back transposed (lane = cell, 8 hidden units)
 #include "rpb_pjf.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
 
 #define PG_HID 128
 #define PG_WAVES 4
@@ -54,129 +48,18 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 #define PG_T(i)
 #endif
 
-namespace {
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ f32x2 ld8(rsrc_t r, int voff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0));
-}
-// by VALUE: __builtin_bit_cast applied to a vector ELEMENT (v[1]) reads element 0 with hipcc 7.2 (it cost the b64 loads their second
-// dword and the row swap its second result); a scalar copy first is safe
-__device__ __forceinline__ float asf(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-// three-plane truncation split of 8 values (rpb_cmx.hip): v = h + m + l to 2^-24, each plane exact in bf16
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x16v mfma32(bf16x8 a, bf16x8 b, f32x16v c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// v = u Phi(u), d = Phi(u) + u phi(u) from one reciprocal and one exponential (see the header); scalar instructions only
-__device__ __forceinline__ void gelu_both_s(float u, float& v, float& d) {
-    const float au = __builtin_fabsf(u);
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(au, 0.23164189f, 1.0f));
-    float pl = 0.5307027145f;
-    pl = __builtin_fmaf(pl, t, -0.7265760135f);
-    pl = __builtin_fmaf(pl, t, 0.7107068705f);
-    pl = __builtin_fmaf(pl, t, -0.142248368f);
-    pl = __builtin_fmaf(pl, t, 0.127414796f);
-    const float e = __builtin_amdgcn_exp2f((u * -0.72134752044448170368f) * u);       // exp(-u^2 / 2)
-    const float Q = (pl * t) * e;                                                     // Phi(-|u|)
-    const float h = 0.5f - Q;                                                         // Phi(|u|) - 1/2
-    v = __builtin_fmaf(au, h, 0.5f * u);
-    const float w = __builtin_fmaf(au * e, 0.39894228040143267794f, h);               // Phi(|u|) - 1/2 + |u| phi(u): odd part of gelu'
-    d = 0.5f + __builtin_copysignf(w, u);
-}
-// the same on a PAIR of values with packed fp32 instructions: the activation phase of a tile has no MFMA in flight, and one wave
-// per SIMD issues a v_pk_* at the price of a scalar instruction (issue_probe: 5.3 cycles either way) -- half the issue slots
-__device__ __forceinline__ void gelu_both_p(f32x2 u, f32x2& v, f32x2& d) {
-    const f32x2 au = __builtin_elementwise_abs(u);
-    const f32x2 den = pk_fma(au, pk2(0.23164189f), pk2(1.0f));
-    const f32x2 t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-    f32x2 pl = pk_fma(pk2(0.5307027145f), t, pk2(-0.7265760135f));
-    pl = pk_fma(pl, t, pk2(0.7107068705f));
-    pl = pk_fma(pl, t, pk2(-0.142248368f));
-    pl = pk_fma(pl, t, pk2(0.127414796f));
-    const f32x2 q = (u * pk2(-0.72134752044448170368f)) * u;
-    const f32x2 e = {__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
-    const f32x2 Q = (pl * t) * e;
-    const f32x2 h = pk2(0.5f) - Q;
-    v = pk_fma(au, h, pk2(0.5f) * u);
-    const f32x2 w = pk_fma(au * e, pk2(0.39894228040143267794f), h);
-    d = pk2(0.5f) + f32x2{__builtin_copysignf(w[0], u[0]), __builtin_copysignf(w[1], u[1])};
-}
-// TWO pairs in lock-step (scheduling fences between the steps): a dependent v_pk_fma_f32 needs a wait state after its producer, and left
-// alone the compiler evaluates one chain after the other (shortest live ranges) with s_nop between the links
-#define PG_FENCE() __builtin_amdgcn_sched_barrier(0)
-__device__ __forceinline__ void gelu_both_p2(f32x2 ua, f32x2 ub, f32x2& va, f32x2& da, f32x2& vb, f32x2& db) {
-    const f32x2 aa = __builtin_elementwise_abs(ua), ab = __builtin_elementwise_abs(ub);
-    const f32x2 dna = pk_fma(aa, pk2(0.23164189f), pk2(1.0f)), dnb = pk_fma(ab, pk2(0.23164189f), pk2(1.0f));
-    const f32x2 qa = (ua * pk2(-0.72134752044448170368f)) * ua, qb = (ub * pk2(-0.72134752044448170368f)) * ub;
-    const f32x2 ta = {__builtin_amdgcn_rcpf(dna[0]), __builtin_amdgcn_rcpf(dna[1])}, tb = {__builtin_amdgcn_rcpf(dnb[0]), __builtin_amdgcn_rcpf(dnb[1])};
-    const f32x2 ea = {__builtin_amdgcn_exp2f(qa[0]), __builtin_amdgcn_exp2f(qa[1])}, eb = {__builtin_amdgcn_exp2f(qb[0]), __builtin_amdgcn_exp2f(qb[1])};
-    PG_FENCE();
-    f32x2 pa = pk_fma(pk2(0.5307027145f), ta, pk2(-0.7265760135f)), pb = pk_fma(pk2(0.5307027145f), tb, pk2(-0.7265760135f));
-    const f32x2 hua = pk2(0.5f) * ua, hub = pk2(0.5f) * ub;
-    PG_FENCE();
-    pa = pk_fma(pa, ta, pk2(0.7107068705f)), pb = pk_fma(pb, tb, pk2(0.7107068705f));
-    const f32x2 xa_ = aa * ea, xb_ = ab * eb;
-    PG_FENCE();
-    pa = pk_fma(pa, ta, pk2(-0.142248368f)), pb = pk_fma(pb, tb, pk2(-0.142248368f));
-    const f32x2 tea = ta * ea, teb = tb * eb;
-    PG_FENCE();
-    pa = pk_fma(pa, ta, pk2(0.127414796f)), pb = pk_fma(pb, tb, pk2(0.127414796f));
-    PG_FENCE();
-    const f32x2 ha = pk_fma(-pa, tea, pk2(0.5f)), hb = pk_fma(-pb, teb, pk2(0.5f));           // 1/2 - Phi(-|u|)
-    PG_FENCE();
-    va = pk_fma(aa, ha, hua), vb = pk_fma(ab, hb, hub);
-    const f32x2 wa = pk_fma(xa_, pk2(0.39894228040143267794f), ha), wb = pk_fma(xb_, pk2(0.39894228040143267794f), hb);
-    PG_FENCE();
-    da = pk2(0.5f) + f32x2{__builtin_copysignf(wa[0], ua[0]), __builtin_copysignf(wa[1], ua[1])};
-    db = pk2(0.5f) + f32x2{__builtin_copysignf(wb[0], ub[0]), __builtin_copysignf(wb[1], ub[1])};
-}
-__device__ __forceinline__ float dpp_add(float x, float y, const int ctrl) {           // x + y from the lane the DPP control names
-    switch (ctrl) {
-    case 0: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x140, 0xF, 0xF, true));   // row_mirror
-    case 1: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    case 2: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    default: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    }
-}
-}  // namespace
-
 // six products of the three-plane split, small terms first, NC independent accumulation chains advancing together
 // (FIRST(c): the chain's first product of the tile takes a literal zero as its C operand -- an inline constant of the instruction -- instead
 // of a zeroed accumulator: the compiler otherwise builds a 16-register zero block and copies it into every accumulator, 128 moves per tile)
 #define PG_MAC6(NC, ACC, AH, AM, AL, BH, BM, BL) PG_MAC6F(NC, ACC, AH, AM, AL, BH, BM, BL, PG_NOTFIRST)
 #define PG_NOTFIRST(c) false
 #define PG_MAC6F(NC, ACC, AH, AM, AL, BH, BM, BL, FIRST)                               \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AH(c_), BL(c_), FIRST(c_) ? f32x16v{} : ACC(c_)); \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AL(c_), BH(c_), ACC(c_)); \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AM(c_), BM(c_), ACC(c_)); \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AH(c_), BM(c_), ACC(c_)); \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AM(c_), BH(c_), ACC(c_)); \
-    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32(AH(c_), BH(c_), ACC(c_));
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AH(c_), BL(c_), FIRST(c_) ? f32x16{} : ACC(c_)); \
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AL(c_), BH(c_), ACC(c_)); \
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AM(c_), BM(c_), ACC(c_)); \
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AH(c_), BM(c_), ACC(c_)); \
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AM(c_), BH(c_), ACC(c_)); \
+    _Pragma("unroll") for (int c_ = 0; c_ < NC; ++c_) ACC(c_) = mfma32b(AH(c_), BH(c_), ACC(c_));
 
 // LOSS: the head's FORWARD rides along (fused trainer): p.gout is the TARGET, the kernel forms out = fc2 gelu(u) + b2,
 // gout = gscale (out - y) and the squared-error partial sums itself
@@ -229,7 +112,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
     const long nslots = (long)gridDim.x * PG_WAVES;
     const long slot = (long)blockIdx.x * PG_WAVES + wave;
     const unsigned line_bytes = (unsigned)cm.Wp * 256u;
-    const f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 
     // ---- pass 1: lines in the zero-pad margin (t >= T or h >= H) of the padded gradient tensor
     {
@@ -239,7 +122,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             const int t = (int)((g / cm.Hp) % cm.Tp);
             if (h < cm.H && t < cm.T) continue;                      // uniform
             const rsrc_t ro = make_rsrc(p.g + g * cm.Wp * 64, line_bytes);
-            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16(z4, ro, off);
+            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16<0>(z4, ro, off);
         }
     }
 
@@ -276,7 +159,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
     const bool bit3 = (n >> 3) & 1, bit2 = (n >> 2) & 1, bit1 = (n >> 1) & 1, bit0 = n & 1;
 
     float dw2[2][4], db1[4], gacc = 0.f, lacc = 0.f;
-    f32x16v accM[4][2];                                  // M: [hidden tile][channel parity]: row 32 mt + D row, column = channel 2 n + ct
+    f32x16 accM[4][2];                                  // M: [hidden tile][channel parity]: row 32 mt + D row, column = channel 2 n + ct
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         db1[t] = 0.f;
@@ -296,7 +179,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
         const bool ok = pl >= 0;
         const rsrc_t rx = make_rsrc(p.s + (long)(ok ? pl : 0) * cm.Wp * 64, ok ? (unsigned)cm.W * 256u : 0u);   // cells >= W read as 0
 #pragma unroll
-        for (int i = 0; i < 8; ++i) xa[i] = ld16(rx, (32 * q + n) * 256 + (i >> 1) * 64 + hg * 32 + (i & 1) * 16);
+        for (int i = 0; i < 8; ++i) xa[i] = ld16<0>(rx, (32 * q + n) * 256 + (i >> 1) * 64 + hg * 32 + (i & 1) * 16);
     };
     auto prefetch = [&](int pl, int q) -> unsigned {     // one dword per lane, 128 B apart: the next tile's 8 KB reach L2 a tile ahead
         const bool ok = pl >= 0;
@@ -324,14 +207,14 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             const unsigned pf = prefetch(pn, qn);
             // ---- the fc2-side inputs of the tile
             const float yv = buf_load_f32(rg, ((32 * q + celly) * 2 + (n & 1)) * 4, 0);                    // the lane's own (cell, feature) element
-            f32x4v G4[8];                                // gout [register row r][feature]: G4[k] = (r = 2k: 0, 1 | r = 2k + 1: 0, 1)
+            f32x4 G4[8];                                // gout [register row r][feature]: G4[k] = (r = 2k: 0, 1 | r = 2k + 1: 0, 1)
             if (!LOSS) {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) G4[k] = __builtin_bit_cast(f32x4v, ld16(rg, (32 * q + 8 * (k >> 1) + 4 * hg + 2 * (k & 1)) * 8));
+                for (int k = 0; k < 8; ++k) G4[k] = __builtin_bit_cast(f32x4, ld16<0>(rg, (32 * q + 8 * (k >> 1) + 4 * hg + 2 * (k & 1)) * 8));
             }
             PG_T(0)
             // ---- contraction 1: u = (s - mean) W1'^T + b1'
-            f32x16v acc[4];
+            f32x16 acc[4];
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -341,8 +224,8 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             bf16x8 Ah[2], Am[2], Al[2], bh[2][4], bm[2][4], bl[2][4];
             auto prep = [&](int ks) {
                 float v[8];
-                const f32x4v x0 = __builtin_bit_cast(f32x4v, xa[2 * ks]), x1 = __builtin_bit_cast(f32x4v, xa[2 * ks + 1]);
-                const f32x4v m0 = *reinterpret_cast<const f32x4v*>(meanl + 16 * ks + 8 * hg), m1 = *reinterpret_cast<const f32x4v*>(meanl + 16 * ks + 8 * hg + 4);
+                const f32x4 x0 = __builtin_bit_cast(f32x4, xa[2 * ks]), x1 = __builtin_bit_cast(f32x4, xa[2 * ks + 1]);
+                const f32x4 m0 = *reinterpret_cast<const f32x4*>(meanl + 16 * ks + 8 * hg), m1 = *reinterpret_cast<const f32x4*>(meanl + 16 * ks + 8 * hg + 4);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] = x0[c] - m0[c];
@@ -397,7 +280,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             f32x2 xr[16];                                // [8 kstep + e]: cell 16 kstep + 8 (e >> 2) + 4 hg + (e & 3), channels 2 n, 2 n + 1
             auto issue_xr = [&]() {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) xr[i] = ld8(rxl, (32 * q + 16 * (i >> 3) + 8 * ((i >> 2) & 1) + 4 * hg + (i & 3)) * 256 + n * 8);
+                for (int i = 0; i < 16; ++i) xr[i] = ld8<0>(rxl, (32 * q + 16 * (i >> 3) + 8 * ((i >> 2) & 1) + 4 * hg + (i & 3)) * 256 + n * 8);
             };
             // ---- activation: v = gelu(u) (kept for d fc2), gelu'(u) replaces u in the accumulators
             float VV[4][16];
@@ -411,7 +294,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
 #pragma unroll
                     for (int r = 0; r < 16; r += 4) {
                         f32x2 v, d, v2, d2;
-                        gelu_both_p2(f32x2{acc[nt][r], acc[nt][r + 1]} + pk2(b1r[nt]), f32x2{acc[nt][r + 2], acc[nt][r + 3]} + pk2(b1r[nt]), v, d, v2, d2);
+                        gelu_both_as2x2(f32x2{acc[nt][r], acc[nt][r + 1]} + pk2(b1r[nt]), f32x2{acc[nt][r + 2], acc[nt][r + 3]} + pk2(b1r[nt]), v, v2, d, d2);
                         VV[nt][r] = v[0], VV[nt][r + 1] = v[1], VV[nt][r + 2] = v2[0], VV[nt][r + 3] = v2[1];
                         acc[nt][r] = d[0], acc[nt][r + 1] = d[1], acc[nt][r + 2] = d2[0], acc[nt][r + 3] = d2[1];
                         pp[r] = pk_fma(pk2(v[0]), wp, pp[r]);
@@ -450,7 +333,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-                for (int k = 0; k < 8; ++k) G4[k] = *reinterpret_cast<const f32x4v*>(gb + 32 * hg + 4 * k);
+                for (int k = 0; k < 8; ++k) G4[k] = *reinterpret_cast<const f32x4*>(gb + 32 * hg + 4 * k);
             } else {
                 gacc += yv;                              // yv holds the lane's gout element here (cells >= W read as 0)
 #pragma unroll
@@ -458,7 +341,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
 #pragma unroll
                     for (int r = 0; r < 16; r += 4) {
                         f32x2 v, d, v2, d2;
-                        gelu_both_p2(f32x2{acc[nt][r], acc[nt][r + 1]} + pk2(b1r[nt]), f32x2{acc[nt][r + 2], acc[nt][r + 3]} + pk2(b1r[nt]), v, d, v2, d2);
+                        gelu_both_as2x2(f32x2{acc[nt][r], acc[nt][r + 1]} + pk2(b1r[nt]), f32x2{acc[nt][r + 2], acc[nt][r + 3]} + pk2(b1r[nt]), v, v2, d, d2);
                         VV[nt][r] = v[0], VV[nt][r + 1] = v[1], VV[nt][r + 2] = v2[0], VV[nt][r + 3] = v2[1];
                         acc[nt][r] = d[0], acc[nt][r + 1] = d[1], acc[nt][r + 2] = d2[0], acc[nt][r + 3] = d2[1];
                     }
@@ -503,7 +386,7 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             PG_T(5)
             // ---- per hidden tile: gh, its planes (once), the weight gradient from registers, the data gradient through LDS
-            f32x16v acc3[2];                             // g^T: [channel tile mt]: row = channel 32 mt + D row, column = cell slot n
+            f32x16 acc3[2];                             // g^T: [channel tile mt]: row = channel 32 mt + D row, column = cell slot n
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -591,13 +474,13 @@ __global__ __launch_bounds__(PG_WAVES * 64, 1) void pjg_kernel(PjfArgs p) {
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
-                    const f32x4v o = {acc3[mt][4 * a], acc3[mt][4 * a + 1], acc3[mt][4 * a + 2], acc3[mt][4 * a + 3]};
-                    st16(o, ro, (32 * q + cells) * 256 + (32 * mt + 8 * a + 4 * hg) * 4);     // cells >= Wp: dropped; W .. Wp-1: zeros (gh == 0)
+                    const f32x4 o = {acc3[mt][4 * a], acc3[mt][4 * a + 1], acc3[mt][4 * a + 2], acc3[mt][4 * a + 3]};
+                    st16<0>(o, ro, (32 * q + cells) * 256 + (32 * mt + 8 * a + 4 * hg) * 4);     // cells >= Wp: dropped; W .. Wp-1: zeros (gh == 0)
                 }
         }
         PG_T(10)
         // margin cells 32 TQ .. Wp - 1 of the line (cells W .. 32 TQ - 1 were written as zeros by the last tile)
-        for (int off = TQ * 32 * 256 + lane * 16; off < (int)line_bytes; off += 1024) st16(z4, ro, off);
+        for (int off = TQ * 32 * 256 + lane * 16; off < (int)line_bytes; off += 1024) st16<0>(z4, ro, off);
     }
 
     if (LOSS) {

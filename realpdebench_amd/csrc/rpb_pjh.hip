@@ -20,13 +20,8 @@
 // Layouts as in rpb_pjg.hip (32x32x16: A lane (m = l & 31, kg = l >> 5) holds k = 8 kg + e; D register r of lane (n, hg) is row
 // 8 (r >> 2) + 4 hg + (r & 3), column n).
 #include "rpb_pjx.h"
+#include "rpb_mma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
 
 #define PH_HID 128
 #define PH_WAVES 4
@@ -36,61 +31,9 @@ typedef float f32x16v __attribute__((ext_vector_type(16)));
 #endif
 
 namespace {
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ float asf(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-// three-plane truncation split of 8 values (rpb_cmx.hip): v = h + m + l to 2^-24, each plane exact in bf16
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x16v mfma32(bf16x8 a, bf16x8 b, f32x16v c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// H2 -- the opt-in "f16x2" eval arithmetic (rpb_cmx.hip, same contract): two fp16 planes per operand, both rounded to nearest even, three
-// products hi*lo + lo*hi + hi*hi on v_mfma_f32_32x32x16_f16 (dropped term <= 2^-22 |a b|); the planes travel in the bf16x8 containers,
-// slot 0 = hi, slot 1 = lo.  W1' carries 2^PH_H2W (fp16's range), undone in the two affine uses of u inside GELU.
+// H2 -- the opt-in "f16x2" eval arithmetic (rpb_mma.h: split8h<false>, mfma32h).  W1' carries 2^PH_H2W (fp16's range), undone in the two
+// affine uses of u inside GELU.
 #define PH_H2W 4
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2w __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split8h(const float (&v)[8], bf16x8& h, bf16x8& l) {
-    u32x4 uh, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2w ab = {v[2 * q], v[2 * q + 1]};
-        const f16x2v hh = __builtin_convertvector(ab, f16x2v);                       // v_cvt_pk_f16_f32 (RNE)
-        uh[q] = __builtin_bit_cast(unsigned, hh);
-        // residual a - float(hi), exact in fp32.  (One v_fma_mix_f32 per value instead, as rpb_cmx.hip does, measured the head 1 % slower:
-        // profiles/r06b_ab.txt)
-        const f32x2w r = ab - __builtin_convertvector(hh, f32x2w);
-        const f16x2v ll = __builtin_convertvector(r, f16x2v);
-        ul[q] = __builtin_bit_cast(unsigned, ll);
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x16v mfma32h(bf16x8 a, bf16x8 b, f32x16v c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 // gelu(a + b) with the bias folded into the two affine uses of u: bs = b / sqrt 2, hb = b / 2.  The erf is fast_erf's (rpb_common.h):
 // erf(x) = sign(x) (1 - 2^(t S(t))), t = min(|x|, 4).  SC: the scale the accumulator carries (f16x2: 2^-PH_H2W), folded into both FMAs
 template <bool H2 = false>
@@ -110,14 +53,6 @@ __device__ __forceinline__ float gelu_bias(float a, float bs, float hb) {
     const float e = __builtin_amdgcn_exp2f(p * t);
     const float hx = __builtin_fmaf(a, 0.5f * SC, hb);     // x / 2 has the sign of x / sqrt 2:  hx erf(xs) = |hx| (1 - e)
     return __builtin_fmaf(fabsf(hx), 1.0f - e, hx);
-}
-__device__ __forceinline__ float dpp_add(float x, float y, const int ctrl) {           // x + y from the lane the DPP control names
-    switch (ctrl) {
-    case 0: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x140, 0xF, 0xF, true));   // row_mirror
-    case 1: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    case 2: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    default: return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    }
 }
 }  // namespace
 
@@ -184,7 +119,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, CW == 64 ? 2 : 1) void pjh_fwd_kerne
         }
         bf16x8 h, m, lo;
         if (H2) {
-            split8h(v, h, m);
+            split8h<false>(v, h, m);
             lo = m;
         } else {
             split8(v, h, m, lo);
@@ -255,13 +190,13 @@ __global__ __launch_bounds__(PH_WAVES * 64, CW == 64 ? 2 : 1) void pjh_fwd_kerne
         const bool ok = pl >= 0;
         if (BFIN) {                                      // 128 B cell rows; channels 16 ks + 8 hg .. + 7 = 16 B
             const rsrc_t rb = make_rsrc(p.s + (long)(ok ? pl : 0) * cm.Wp * 32, ok ? (unsigned)cm.W * 128u : 0u);
-            xa[2 * ks] = ld16(rb, (32 * q + n) * 128 + ks * 32 + hg * 16);
+            xa[2 * ks] = ld16<0>(rb, (32 * q + n) * 128 + ks * 32 + hg * 16);
             return;
         }
         // (DG: `pl` is the CROPPED line index, the rows are gu's)
         const rsrc_t rx = make_rsrc(p.s + (long)(ok ? pl : 0) * (DG ? cm.W : cm.Wp) * CW, ok ? (unsigned)cm.W * (CW * 4u) : 0u);   // cells >= W read as 0
-        xa[2 * ks] = ld16(rx, (32 * q + n) * (CW * 4) + ks * 64 + hg * 32);
-        xa[2 * ks + 1] = ld16(rx, (32 * q + n) * (CW * 4) + ks * 64 + hg * 32 + 16);
+        xa[2 * ks] = ld16<0>(rx, (32 * q + n) * (CW * 4) + ks * 64 + hg * 32);
+        xa[2 * ks + 1] = ld16<0>(rx, (32 * q + n) * (CW * 4) + ks * 64 + hg * 32 + 16);
     };
     {
         const int pl0 = slot < GL ? (DG ? (int)slot : line_of((int)slot)) : -1;
@@ -311,7 +246,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, CW == 64 ? 2 : 1) void pjh_fwd_kerne
             }
             // ---- contraction 1: u = (s - mean) W1'^T, software-pipelined over the K-steps: the split of step ks + 1 is written before the
             //      24 MFMAs of step ks and does not depend on them
-            f32x16v acc[4];
+            f32x16 acc[4];
 #ifdef PH_NOMFMA
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
@@ -326,13 +261,13 @@ __global__ __launch_bounds__(PH_WAVES * 64, CW == 64 ? 2 : 1) void pjh_fwd_kerne
                     return;
                 }
                 float v[8];
-                const f32x4v x0 = __builtin_bit_cast(f32x4v, xa[2 * ks]), x1 = __builtin_bit_cast(f32x4v, xa[2 * ks + 1]);
+                const f32x4 x0 = __builtin_bit_cast(f32x4, xa[2 * ks]), x1 = __builtin_bit_cast(f32x4, xa[2 * ks + 1]);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     v[c] = x0[c] - meanr[8 * ks + c];
                     v[4 + c] = x1[c] - meanr[8 * ks + 4 + c];
                 }
-                if (H2) split8h(v, Ah[ks & 1], Am[ks & 1]);
+                if (H2) split8h<false>(v, Ah[ks & 1], Am[ks & 1]);
                 else split8(v, Ah[ks & 1], Am[ks & 1], Al[ks & 1]);
                 issue_pair(pn, qn, ks);                  // the registers are free: the next tile's loads fly through the rest of this one
             };
@@ -346,9 +281,9 @@ __global__ __launch_bounds__(PH_WAVES * 64, CW == 64 ? 2 : 1) void pjh_fwd_kerne
 #ifdef PH_NOMFMA   /* timing-only build: the products replaced by one vector instruction per group */
 #define PH_G(AP, BP, FIRST) _Pragma("unroll") for (int nt_ = 0; nt_ < 4; ++nt_) acc[nt_][0] = ((FIRST) ? 0.f : acc[nt_][0]) + __builtin_bit_cast(float, __builtin_bit_cast(u32x4, AP[ks & 1])[0] ^ __builtin_bit_cast(u32x4, BP[nt_])[1]);
 #else
-#define PH_G(AP, BP, FIRST) _Pragma("unroll") for (int nt_ = 0; nt_ < 4; ++nt_) acc[nt_] = mfma32(AP[ks & 1], BP[nt_], (FIRST) ? f32x16v{} : acc[nt_]);
+#define PH_G(AP, BP, FIRST) _Pragma("unroll") for (int nt_ = 0; nt_ < 4; ++nt_) acc[nt_] = mfma32b(AP[ks & 1], BP[nt_], (FIRST) ? f32x16{} : acc[nt_]);
 #endif
-#define PH_GH(AP, BP, FIRST) _Pragma("unroll") for (int nt_ = 0; nt_ < 4; ++nt_) acc[nt_] = mfma32h(AP[ks & 1], BP[nt_], (FIRST) ? f32x16v{} : acc[nt_]);
+#define PH_GH(AP, BP, FIRST) _Pragma("unroll") for (int nt_ = 0; nt_ < 4; ++nt_) acc[nt_] = mfma32h(AP[ks & 1], BP[nt_], (FIRST) ? f32x16{} : acc[nt_]);
                 if (BFIN) {                     // one stored plane x the planes of the constants, small terms first
                     if (RPB_BF16_CONST_PLANES > 2) {
                         PH_G(Ah, BL, ks == 0)

@@ -13,50 +13,15 @@
 //   pjx_head   (lane = cell):    the head's forward, and its backward up to gu and the fc2 / bias gradient partials.
 // (Recomputing gh inside the dgrad and weight-gradient kernels instead of storing gu was built and measured slower: 3.4 against 2.2 ms
 // for the dgrad at B = 32, the second evaluation of act' on 128 hidden units per cell costs more VALU time than the 5.4 GB it saves.)
-#include "rpb_common.h"
+#include "rpb_mma.h"
 #include "rpb_pjx.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 #define PJ_HID 128
 #define PJ_WAVES 8
 #define PJ_DOMAX 4
 
 namespace {
-__device__ __forceinline__ u32x4 ld16(rsrc_t r, int voff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ void st16(f32x4v v, rsrc_t r, int voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
-}
-__device__ __forceinline__ float trunc_bf16(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_hi(float a, float b) {
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u32x4 uh, um, ul;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = v[2 * q], b = v[2 * q + 1];
-        {
-            unsigned ph_, pm_, pl_;
-            rpb_split_pair(a, b, ph_, pm_, pl_);
-            uh[q] = ph_;
-            um[q] = pm_;
-            ul[q] = pl_;
-        }
-    }
-    h = __builtin_bit_cast(bf16x8, uh);
-    m = __builtin_bit_cast(bf16x8, um);
-    l = __builtin_bit_cast(bf16x8, ul);
-}
-__device__ __forceinline__ f32x4v mfma16(bf16x8 a, bf16x8 b, f32x4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // six products of the three-plane split, small terms first
 #define PJ_MAC6(ACC, AH, AM, AL, BH, BM, BL) \
     ACC = mfma16(AH, BL, ACC);                \
@@ -131,9 +96,9 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_dgrad_kernel(PjxArgs p) {
     const int TQ = (cm.Wp + 15) >> 4;
     const unsigned line_bytes = (unsigned)cm.Wp * 256u;
     // the lane's 16 channels 16 i + 4 kg + c (as loaded) == 16 mt2 + 4 mg + r (as produced): sums live per lane, reduced at the end
-    f32x4v ssum[4], ssq[4];
+    f32x4 ssum[4], ssq[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) ssum[i] = ssq[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) ssum[i] = ssq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (long g = slot; g < G; g += nslots) {
         const int h = (int)(g % cm.Hp);
@@ -142,8 +107,8 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_dgrad_kernel(PjxArgs p) {
         const long b = r2 / cm.Tp;
         const rsrc_t ro = make_rsrc(p.g + g * cm.Wp * 64, line_bytes);
         if (h >= cm.H || t >= cm.T) {                            // uniform: the whole line is padding -> zeros
-            const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16(z, ro, off);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            for (int off = lane * 16; off < (int)line_bytes; off += 1024) st16<0>(z, ro, off);
             continue;
         }
         const long rc = (b * cm.T + t) * cm.H + h;               // cropped line
@@ -153,30 +118,30 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_dgrad_kernel(PjxArgs p) {
             asm volatile("" ::: "memory");
             const bool live = 16 * q < cm.W;                     // uniform: the tile holds cropped cells
             if (!live) {                                         // margin cells W .. Wp-1: zeros
-                const f32x4v z = {0.f, 0.f, 0.f, 0.f};
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) st16(z, ro, (16 * q + n16) * 256 + i * 64 + kg * 16);
+                for (int i = 0; i < 4; ++i) st16<0>(z, ro, (16 * q + n16) * 256 + i * 64 + kg * 16);
                 continue;
             }
             u32x4 xa[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xa[i] = ld16(rx, (16 * q + n16) * 256 + i * 64 + kg * 16);
-            f32x4v shat[4];                                       // (s - mean) * invstd at the lane's 16 channels: reused by the sums
-            f32x4v acc[8];                                        // gh rows of the lane's cell: 32 B per K-step
+            for (int i = 0; i < 4; ++i) xa[i] = ld16<0>(rx, (16 * q + n16) * 256 + i * 64 + kg * 16);
+            f32x4 shat[4];                                       // (s - mean) * invstd at the lane's 16 channels: reused by the sums
+            f32x4 acc[8];                                        // gh rows of the lane's cell: 32 B per K-step
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                acc[i] = __builtin_bit_cast(f32x4v, ld16(rg, (16 * q + n16) * 512 + (i >> 1) * 128 + kg * 32 + (i & 1) * 16));
+                acc[i] = __builtin_bit_cast(f32x4, ld16<0>(rg, (16 * q + n16) * 512 + (i >> 1) * 128 + kg * 32 + (i & 1) * 16));
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const f32x4v xv = __builtin_bit_cast(f32x4v, xa[i]);
-                const f32x4v mu = *reinterpret_cast<const f32x4v*>(xfl + 16 * i + 4 * kg);
-                const f32x4v is = *reinterpret_cast<const f32x4v*>(xfl + 64 + 16 * i + 4 * kg);
+                const f32x4 xv = __builtin_bit_cast(f32x4, xa[i]);
+                const f32x4 mu = *reinterpret_cast<const f32x4*>(xfl + 16 * i + 4 * kg);
+                const f32x4 is = *reinterpret_cast<const f32x4*>(xfl + 64 + 16 * i + 4 * kg);
                 shat[i] = (xv - mu) * is;
             }
             // ---- g^T = W1^T gh^T: the contraction values of lane-group mg in K-step s are hidden units 32 s + 8 mg + e
-            f32x4v acc2[4];
+            f32x4 acc2[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc2[i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < 4; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 float v[8];
@@ -198,7 +163,7 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_dgrad_kernel(PjxArgs p) {
             // ---- store 4 x 16 B (channels 16 mt2 + 4 mg ..) of the lane's cell; BatchNorm-backward sums (cells >= W carry g == 0)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                st16(acc2[i], ro, (16 * q + n16) * 256 + i * 64 + kg * 16);
+                st16<0>(acc2[i], ro, (16 * q + n16) * 256 + i * 64 + kg * 16);
                 ssum[i] += acc2[i];
                 ssq[i] += acc2[i] * shat[i];
             }
@@ -259,7 +224,6 @@ extern "C" int rpb_proj_dgrad(const float* s, const float* w1, const float* gu, 
     hipLaunchKernelGGL(pjx_dgrad_kernel, dim3(grid), dim3(PJ_WAVES * 64), lds, (hipStream_t)stream, p);
     RPB_CHECK_LAUNCH("proj_dgrad");
 }
-
 
 // ------------------------------------------------------------------------------------------------------------ head forward / gu
 // The projection head itself on the bf16 matrix pipe (replaces the fp32-MFMA kernels of rpb_proj.hip for C = 64):
@@ -348,16 +312,16 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
     float b2v[DOT];
 #pragma unroll
     for (int j = 0; j < DOT; ++j) b2v[j] = (!BWD && j < DO) ? p.b2[j] : 0.f;
-    f32x4v db1[BWD ? 8 : 1], dw2[BWD ? DOT : 1][BWD ? 8 : 1];
+    f32x4 db1[BWD ? 8 : 1], dw2[BWD ? DOT : 1][BWD ? 8 : 1];
     float db2[DOT];
 #pragma unroll
     for (int j = 0; j < DOT; ++j) db2[j] = 0.f;
     if (BWD) {
 #pragma unroll
         for (int mt = 0; mt < 8; ++mt) {
-            db1[mt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            db1[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < DOT; ++j) dw2[j][mt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < DOT; ++j) dw2[j][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
     auto line_of = [&](long gl) {                                   // cropped line -> padded line
@@ -370,11 +334,11 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
         if (BFIN) {                                                  // 128 B per cell: loads ks = 0, 1 are the two K-steps
             const rsrc_t rx = make_rsrc(p.s + line_of(gl) * cm.Wp * 32, (unsigned)cm.W * 128u);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) xa[i] = ld16(rx, (16 * q + n16) * 128 + i * 64 + kg * 16);
+            for (int i = 0; i < 2; ++i) xa[i] = ld16<0>(rx, (16 * q + n16) * 128 + i * 64 + kg * 16);
         } else {
             const rsrc_t rx = make_rsrc(p.s + line_of(gl) * cm.Wp * 64, (unsigned)cm.W * 256u);      // cells >= W read as 0
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xa[i] = ld16(rx, (16 * q + n16) * 256 + i * 64 + kg * 16);
+            for (int i = 0; i < 4; ++i) xa[i] = ld16<0>(rx, (16 * q + n16) * 256 + i * 64 + kg * 16);
         }
     };
     if (slot < GL) issue(slot, 0);
@@ -385,9 +349,9 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
             asm volatile("" ::: "memory");
             const bool last = q + 1 == TQ;
             const long gn = last ? gl + nslots : gl;
-            f32x4v acc[8];
+            f32x4 acc[8];
 #pragma unroll
-            for (int mt = 0; mt < 8; ++mt) acc[mt] = *reinterpret_cast<const f32x4v*>(b1l + 16 * mt + 4 * kg);
+            for (int mt = 0; mt < 8; ++mt) acc[mt] = *reinterpret_cast<const f32x4*>(b1l + 16 * mt + 4 * kg);
             float go[DOT];
 #pragma unroll
             for (int j = 0; j < DOT; ++j) go[j] = (BWD && j < DO) ? buf_load_f32(rgo, ((16 * q + n16) * DO + j) * 4, 0) : 0.f;
@@ -402,12 +366,12 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                     const int i = BFIN ? 0 : 2 * ks + hf;
-                    const f32x4v xv = __builtin_bit_cast(f32x4v, xa[i]);
-                    const f32x4v mu = *reinterpret_cast<const f32x4v*>(xfl + 16 * i + 4 * kg);
-                    const f32x4v is = *reinterpret_cast<const f32x4v*>(xfl + 64 + 16 * i + 4 * kg);
-                    const f32x4v ga = *reinterpret_cast<const f32x4v*>(xfl + 128 + 16 * i + 4 * kg);
-                    const f32x4v be = *reinterpret_cast<const f32x4v*>(xfl + 192 + 16 * i + 4 * kg);
-                    f32x4v z = bn4(xv, mu, is, ga, be);
+                    const f32x4 xv = __builtin_bit_cast(f32x4, xa[i]);
+                    const f32x4 mu = *reinterpret_cast<const f32x4*>(xfl + 16 * i + 4 * kg);
+                    const f32x4 is = *reinterpret_cast<const f32x4*>(xfl + 64 + 16 * i + 4 * kg);
+                    const f32x4 ga = *reinterpret_cast<const f32x4*>(xfl + 128 + 16 * i + 4 * kg);
+                    const f32x4 be = *reinterpret_cast<const f32x4*>(xfl + 192 + 16 * i + 4 * kg);
+                    f32x4 z = bn4(xv, mu, is, ga, be);
                     if (xgelu) z = gelu4(z);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) v[4 * hf + c] = z[c];
@@ -439,12 +403,12 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
                 }
             if (!BWD && FC2M) {
                 // out^T [j][cell] = W2 v^T + b2: K-step s takes hidden rows {32 s + 4 mg + r, 32 s + 16 + 4 mg + r} = acc[2 s], acc[2 s + 1]
-                f32x4v o;
+                f32x4 o;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = 4 * kg + r < DO ? p.b2[4 * kg + r] : 0.f;
 #pragma unroll
                 for (int s4 = 0; s4 < 4; ++s4) {
-                    f32x4v v0, v1;
+                    f32x4 v0, v1;
                     if (silu) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -473,7 +437,7 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
                 }
                 // lane (cell n16, group mg) holds outputs j = 4 mg + r of its cell
                 if ((DO & 3) == 0) {
-                    if (4 * kg < DO) st16(o, rgo, ((16 * q + n16) * DO + 4 * kg) * 4);
+                    if (4 * kg < DO) st16<0>(o, rgo, ((16 * q + n16) * DO + 4 * kg) * 4);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -485,7 +449,7 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
                 for (int j = 0; j < DOT; ++j) po[j] = 0.f;
 #pragma unroll
                 for (int mt = 0; mt < 8; ++mt) {
-                    f32x4v vv;
+                    f32x4 vv;
                     if (silu) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -498,8 +462,8 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
                     }
 #pragma unroll
                     for (int j = 0; j < DOT; ++j) {
-                        const f32x4v w = *reinterpret_cast<const f32x4v*>(w2l + j * PJ_HID + 16 * mt + 4 * kg);
-                        const f32x4v pr = w * vv;
+                        const f32x4 w = *reinterpret_cast<const f32x4*>(w2l + j * PJ_HID + 16 * mt + 4 * kg);
+                        const f32x4 pr = w * vv;
                         po[j] += (pr[0] + pr[1]) + (pr[2] + pr[3]);
                     }
                 }
@@ -513,10 +477,10 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
             } else {
 #pragma unroll
                 for (int mt = 0; mt < 8; ++mt) {
-                    f32x4v gp = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 gp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int j = 0; j < DOT; ++j) gp += *reinterpret_cast<const f32x4v*>(w2l + j * PJ_HID + 16 * mt + 4 * kg) * go[j];
-                    f32x4v vv, dd;
+                    for (int j = 0; j < DOT; ++j) gp += *reinterpret_cast<const f32x4*>(w2l + j * PJ_HID + 16 * mt + 4 * kg) * go[j];
+                    f32x4 vv, dd;
                     if (silu) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -526,18 +490,18 @@ __global__ __launch_bounds__(PJ_WAVES * 64) void pjx_head_kernel(PjhArgs p) {
                             dd[r] = d1;
                         }
                     } else {                                        // v = u Phi(u), d = Phi(u) + u phi(u): one erf, packed pairs
-                        const f32x4v u = acc[mt];
+                        const f32x4 u = acc[mt];
                         const f32x2 e0 = fast_erf2(u.lo * pk2(0.70710678118654752440f)), e1 = fast_erf2(u.hi * pk2(0.70710678118654752440f));
-                        const f32x4v cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
-                        const f32x4v q2 = (f32x4v{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
-                        f32x4v ex;
+                        const f32x4 cdf = join4(pk2(0.5f) * (pk2(1.0f) + e0), pk2(0.5f) * (pk2(1.0f) + e1));
+                        const f32x4 q2 = (f32x4{-0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f, -0.72134752044448170368f} * u) * u;
+                        f32x4 ex;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ex[r] = __builtin_amdgcn_exp2f(q2[r]);
                         vv = u * cdf;
                         dd = cdf + u * (ex * 0.39894228040143267794f);
                     }
-                    const f32x4v guv = gp * dd;                     // cells >= W carry gout == 0 -> 0, and their store is dropped
-                    st16(guv, rgu, (16 * q + n16) * 512 + (16 * mt + 4 * kg) * 4);
+                    const f32x4 guv = gp * dd;                     // cells >= W carry gout == 0 -> 0, and their store is dropped
+                    st16<0>(guv, rgu, (16 * q + n16) * 512 + (16 * mt + 4 * kg) * 4);
                     db1[mt] += guv;
 #pragma unroll
                     for (int j = 0; j < DOT; ++j) dw2[j][mt] += vv * go[j];

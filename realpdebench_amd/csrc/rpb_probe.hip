@@ -6,7 +6,7 @@
 // once can approach.
 // Round 5: the probe streams with the policy the product kernels stream with (RPB_STREAM_AUX == 2: nontemporal loads and stores,
 // +5 % on these boxes), so that the ceiling stays the rate of a plain copy written the way the kernels are.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 
 namespace {
 __device__ __forceinline__ f32x4 pld(const f32x4* p, long i) {
@@ -68,9 +68,8 @@ extern "C" int rpb_stream_probe(const float* a, const float* b, const float* c, 
 // `waves_per_simd` waves on every SIMD.  Measured on the MI355X boxes of this project (tools/ubench/mfma_peak.hip): 1.76 PFLOP/s with
 // random operands (1.6 for the 16x16x32 shape) against 2.4-2.45 with zeros and the 2.5 PFLOP/s datasheet peak -- the bound the
 // split-bf16 convolutions / token GEMMs (six bf16 products per fp32 product) are priced against in bench.py.
-typedef __attribute__((ext_vector_type(8))) __bf16 probe_bf16x8;
 __global__ __launch_bounds__(256) void mfma_probe_kernel(const float* __restrict__ seed, float* __restrict__ out, int iters) {
-    probe_bf16x8 a[4], b[4];
+    bf16x8 a[4], b[4];
     for (int j = 0; j < 4; ++j)
         for (int i = 0; i < 8; ++i) {
             a[j][i] = (__bf16)seed[(threadIdx.x * 8 + i + 64 * j) & 4095];
@@ -78,10 +77,10 @@ __global__ __launch_bounds__(256) void mfma_probe_kernel(const float* __restrict
         }
     f32x16 c0 = zero16(), c1 = zero16(), c2 = zero16(), c3 = zero16();
     for (int it = 0; it < iters; ++it) {
-        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c1, 0, 0, 0);
-        c2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[2], c2, 0, 0, 0);
-        c3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[3], b[3], c3, 0, 0, 0);
+        c0 = mfma32b(a[0], b[0], c0);
+        c1 = mfma32b(a[1], b[1], c1);
+        c2 = mfma32b(a[2], b[2], c2);
+        c3 = mfma32b(a[3], b[3], c3);
     }
     const f32x16 r = c0 + c1 + c2 + c3;
     float s = 0.f;

@@ -1,6 +1,6 @@
 #include <cstdlib>
 // Library-wide state: last-error buffer, cached device properties, version.
-#include "rpb_common.h"
+#include "rpb_mma.h"
 
 thread_local char rpb_err_buf[512] = "";
 

@@ -711,7 +711,7 @@ def _bf16_ulps(a, b):
 def test_bf16_storage_kernels(ops, Wp, rows, K2):
     """BASELINE.json configs[4] activation storage: lift / W stage / cell_mix / projection with bf16 activations are the computation on the
     (exactly representable) bf16 inputs with the fp32 constants (weights, stage matrices) taken to 2^-16 -- two bf16 planes, round 5: the
-    third plane is 1 / 128 of the rounding a stored operand already carries (csrc/rpb_common.h, RPB_BF16_CONST_PLANES) -- rounded once to
+    third plane is 1 / 128 of the rounding a stored operand already carries (csrc/rpb_mma.h, RPB_BF16_CONST_PLANES) -- rounded once to
     nearest even on store: against fp64 on the same bf16 inputs the stored bf16 values differ by at most one unit in the last place, and
     fp32 outputs hold 3e-5 (2e-6 with -DRPB_BF16_CONST_PLANES=3)."""
     TOLB = 3e-5

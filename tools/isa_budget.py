@@ -2,6 +2,7 @@
 
     python tools/isa_budget.py realpdebench_amd/csrc/rpb_cmx.hip 'cmx_kernelILi0ELb0ELb0ELb1'      # eval cell_mix + fused W stage
     python tools/isa_budget.py realpdebench_amd/csrc/rpb_pjh.hip pjh_fwd_kernelILi2
+    python tools/isa_budget.py --compare ../parent_checkout                                          # a refactor left the device code alone?
 
 compiles the file to device assembly with the flags realpdebench_amd/build.py uses for it, finds every natural loop of the kernel
 (a backward branch to an earlier label), and prints per loop the instruction mix by issue class: MFMA (by shape), packed / scalar-form
@@ -23,9 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def compile_to_asm(src, extra=()):
+def compile_to_asm(src, extra=(), tag=""):
     from realpdebench_amd import build as B
-    out = os.path.join(tempfile.gettempdir(), os.path.basename(src)[:-4] + ".isa.s")
+    out = os.path.join(tempfile.gettempdir(), os.path.basename(src)[:-4] + tag + ".isa.s")
     cmd = [B.HIPCC] + B.FLAGS + B.EXTRA.get(os.path.basename(src), []) + list(extra) + ["--cuda-device-only", "-S", src, "-o", out]
     cmd = [c for c in cmd if c != "-fPIC"]
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -110,13 +111,48 @@ def cycles_two_waves(c):
     return 16 * c["mfma16"] + 32 * c["mfma32"], 2.6 * V
 
 
+def compare_trees(other, only, flags):
+    """Device assembly of every csrc/*.hip of this tree against the same file of the tree `other` (a checkout of another revision), both
+    compiled with THIS tree's build flags.  Lines naming the __hip_cuid_<hash> symbol differ between any two compiles and are left out."""
+    from concurrent.futures import ThreadPoolExecutor
+    from realpdebench_amd import build as B
+
+    def code(path, tag):
+        return [l for l in open(compile_to_asm(path, flags, tag)).read().split("\n") if "__hip_cuid_" not in l]
+
+    def one(src):
+        old = os.path.join(other, os.path.relpath(src, ROOT))
+        if not os.path.exists(old):
+            return src, "new file"
+        a, b = code(old, ".other"), code(src, "")
+        if a == b:
+            return src, f"identical ({len(b)} lines)"
+        n = sum(x != y for x, y in zip(a, b)) + abs(len(a) - len(b))
+        return src, f"DIFFERS: {len(a)} -> {len(b)} lines, {n} differ"
+
+    srcs = [s for s in B.sources() if not only or os.path.basename(s) in only]
+    bad = 0
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+        for src, verdict in ex.map(one, srcs):
+            print(f"{os.path.basename(src):26s} {verdict}", flush=True)
+            bad += not verdict.startswith("identical")
+    return bad
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("src")
-    ap.add_argument("kernel", help="substring of the mangled kernel name")
+    ap.add_argument("src", nargs="?")
+    ap.add_argument("kernel", nargs="?", help="substring of the mangled kernel name")
+    ap.add_argument("--compare", metavar="TREE", help="instead: compare the device assembly of every csrc/*.hip (or of the files named "
+                    "with --only) with the same file in TREE, a checkout of another revision; exit status 1 if any differs")
+    ap.add_argument("--only", action="append", default=[], help="with --compare: file name in csrc/ (repeatable)")
     ap.add_argument("--blocks", action="store_true", help="per basic block of the largest loop")
     ap.add_argument("--flag", action="append", default=[], help="extra compiler flag (e.g. -DCMX_PF2=1)")
     a = ap.parse_args()
+    if a.compare:
+        sys.exit(1 if compare_trees(os.path.abspath(a.compare), a.only, a.flag) else 0)
+    if not (a.src and a.kernel):
+        ap.error("src and kernel are required")
     asm = compile_to_asm(os.path.join(ROOT, a.src) if not os.path.isabs(a.src) else a.src, a.flag)
     for name, body in kernel_lines(asm, a.kernel):
         print(f"== {name}: {sum(mix(body).values())} instructions in all")

@@ -2,7 +2,7 @@
 """Per-product and per-dot-product error of the operand splits this repo multiplies on the 16-bit matrix pipe (numpy, no GPU):
 
   bf16x3 x 6   the default: x = hi + mid + lo exactly (three TRUNCATED bf16 planes), six products, the three smallest dropped
-  bf16x3r x 6  the same with every plane ROUNDED to nearest even (build switch -DRPB_SPLIT_RNE=1, csrc/rpb_common.h)
+  bf16x3r x 6  the same with every plane ROUNDED to nearest even (build switch -DRPB_SPLIT_RNE=1, csrc/rpb_mma.h)
   f16x2 x 3    the opt-in eval arithmetic (FNO3d.set_arith("f16x2")): two fp16 planes, both rounded to nearest even, lo*lo dropped
   f16x2 x 4    the same with the fourth product kept
   fp32         one rounded fp32 multiply / a sequential fp32 dot product (what a CPU fp32 reference does)
