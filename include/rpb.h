@@ -666,6 +666,38 @@ int rpb_afno_wgrad(const float* A, const float* G, float* part, float* dw, long 
 int rpb_dpot_unpatch(const float* O, float* pred, int B, int T, int H, int W, int Cd, int Co, int ps, int ldo, void* stream);
 int rpb_dpot_unpatch_bwd(const float* gpred, float* gO, int B, int T, int H, int W, int Cd, int Co, int ps, int ldo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * MWT3d (multiwavelet operator, realpdebench/model/MWT_libs/models.py:498-790) -- evaluation forward (additions do not change
+ * RPB_ABI_VERSION).  Activations are channels-last fp32 [B][Nx][Ny][T][36], 36 = c * k^2 = (4, 9); DESIGN.md section 15.
+ *     lift: x [B][T][H][W][Cin] -> out [B][H][W][T][36] = Lk(x)  (w [36][Cin], b [36]) */
+int rpb_mwt_lift(const float* x, const float* w, const float* b, float* out, int B, int T, int H, int W, int Cin, void* stream);
+/*     wavelet_transform: x [B][2Nx][2Ny][T][36] -> d, s [B][Nx][Ny][T][36]; ec_d, ec_s [36][9] */
+int rpb_mwt_decompose(const float* x, const float* ec_d, const float* ec_s, float* d, float* s, int B, int Nx, int Ny, int T, void* stream);
+/*     evenOdd of cat(x + us, ud): x [B][Nx][xNy][T][36] (xNy = Ny, or 1: broadcast), us, ud [B][Nx][Ny][T][36], rc [4][18][9] in the order
+ *     ee, eo, oe, oo -> out [B][2Nx][2Ny][T][36]; relu != 0 applies the ReLU between two CZ blocks */
+int rpb_mwt_reconstruct(const float* x, const float* us, const float* ud, const float* rc, float* out, int B, int Nx, int Ny, int T,
+                        int xNy, int relu, void* stream);
+/*     T0 on the coarsest view: in [rows][K] (K = 36 * shape_multiplier), w [36][K], b [36] -> out [rows][36] */
+int rpb_mwt_coarse(const float* in, const float* w, const float* b, float* out, long rows, int K, void* stream);
+/*     one truncated-DFT stage: out[outer][o][inner] = sum_k M[o][k] in[outer][k][inner], M [O][K] (stage matrices of dft.py) */
+int rpb_mwt_axis(const float* in, const float* M, float* out, long outer, int O, int K, long inner, void* stream);
+/*     per-bin complex contraction: X, Y [B][2][NB][36] planar; Wt [4 * 125][36 in][36 out][2]; tab [NB] (int32) = weight bin of each
+ *     retained output bin after the four sequential corner assignments of models.py:569-576 */
+int rpb_mwt_modes(const float* X, const float* Wt, const int* tab, float* Y, int B, int NB, void* stream);
+/*     last inverse stage (c2r along T) + ReLU + Lo: S [lines][K2][36], GT [T][K2], loT [36 in][36 out], lb [36] ->
+ *     out [lines * T][36] (+= when accumulate != 0) */
+int rpb_mwt_spec_out(const float* S, const float* GT, const float* loT, const float* lb, float* out, long lines, int T, int K2,
+                     int accumulate, void* stream);
+/*     sparseKernel3d: Conv3d(36, 36, 3, pad 1) + bias + ReLU + Linear(36, 36) + bias on the fp32 MFMA.  wprep: w [36][36][3][3][3],
+ *     lo [36][36] -> wp [27 * 9 * 3 * 64], lop [3 * 4 * 3 * 64] (lane order).  cb48: the convolution bias padded with zeros to 48 */
+int rpb_mwt_conv3_wprep(const float* w, const float* lo, float* wp, float* lop, void* stream);
+int rpb_mwt_conv3(const float* x, const float* wp, const float* cb48, const float* lop, const float* lb, float* out, int B, int Nx, int Ny,
+                  int T, int accumulate, void* stream);
+/*     head: Lc0 (w0t [36][128], b0), ReLU, Lc1 (w1 [Cout * r][128], b1) and the output permute: x [B][Nx][Ny][T][36] ->
+ *     out [B][T * r][Nx][Ny][Cout] */
+int rpb_mwt_head(const float* x, const float* w0t, const float* b0, const float* w1, const float* b1, float* out, int B, int Nx, int Ny,
+                 int T, int Cout, int r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,16 @@ SIGNATURES = {
     "rpb_col_reduce": (_I, "pip" + "ilii" + "p"),
     "rpb_pad_grid_fwd": (_I, "ppppppp" + "iiiiiiii" + "p"),
     "rpb_crop_gather": (_I, "pp" + "iiiiiiii" + "p"),
+    "rpb_mwt_lift": (_I, "pppp" + "iiiii" + "p"),
+    "rpb_mwt_decompose": (_I, "ppppp" + "iiii" + "p"),
+    "rpb_mwt_reconstruct": (_I, "ppppp" + "iiiiii" + "p"),
+    "rpb_mwt_coarse": (_I, "pppp" + "li" + "p"),
+    "rpb_mwt_axis": (_I, "ppp" + "liil" + "p"),
+    "rpb_mwt_modes": (_I, "pppp" + "ii" + "p"),
+    "rpb_mwt_spec_out": (_I, "ppppp" + "liii" + "p"),
+    "rpb_mwt_conv3_wprep": (_I, "pppp" + "p"),
+    "rpb_mwt_conv3": (_I, "pppppp" + "iiiii" + "p"),
+    "rpb_mwt_head": (_I, "pppppp" + "iiiiii" + "p"),
 }
 
 _lib = None

@@ -47,7 +47,13 @@ def load_model(train_dataset, device="cpu", **kwargs):
                 "n_blocks", "modes", "mlp_ratio", "out_layer_dim", "normalize", "act", "time_agg", "n_cls", "model_type",
                 "checkpoint_path")                            # load_model.py:108-131
         model = DPOT(shape_in=input_shape, shape_out=output_shape, **{k: kwargs[k] for k in keys}).to(device)
+    elif model_name == "mwt":
+        from .mwt import MWT3d
+        kwargs["shape_in"] = input_shape                      # load_model.py:93-107
+        kwargs["shape_out"] = output_shape
+        kwargs.pop("config", None)
+        model = MWT3d(**kwargs).to(device)
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
-                         "(supported: fno, transolver, galerkin_transformer, unet, dpot)")
+                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt)")
     return model

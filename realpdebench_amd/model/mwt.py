@@ -1,0 +1,413 @@
+"""MWT3d (multiwavelet operator) on MI355X -- drop-in for ``realpdebench.model.MWT_libs.models.MWT3d`` (reference
+realpdebench/model/MWT_libs/models.py:498-790, built by ``load_model`` like model/load_model.py:93-107) for the configuration family of
+the reference's ``configs/*/mwt.yaml``: ``k: 3, alpha: 5, c: 4, nCZ: 4, L: 0, base: legendre``.
+
+Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training backward is not built:
+every attempt to backpropagate raises ``NotImplementedError`` (``MWT_TRAIN_MSG``) instead of returning tensors without a graph.
+
+Pipeline (activations channels-last fp32 ``[B][Nx][Ny][T][36]``, 36 = (c, k^2) = (4, 9); every product runs in a HIP kernel of
+``csrc/rpb_mwt.hip``; no reference permute survives):
+  rpb_mwt_lift (the [B,T,H,W,C] permute + Lk) -> nCZ x MWT_CZ3d -> rpb_mwt_head (Lc0, ReLU, Lc1, the output permute).
+  MWT_CZ3d (models.py:651-680), Nx = H halves ``ns = log2 H`` times:
+    level i:  rpb_mwt_decompose: x -> d_i, s_i (2 x 2 gather, ec_d / ec_s)
+              Ud_i = A(d_i) + B(s_i):  A = truncated DFT (rpb_mwt_axis: T, Ny, Nx) -> rpb_mwt_modes (36 x 36 complex per retained bin,
+                       through the corner table below) -> rpb_mwt_axis (Nx, Ny) -> rpb_mwt_spec_out (c2r along T, ReLU, Lo);
+                       B = rpb_mwt_conv3 (3x3x3 convolution, ReLU, Lo) accumulating into Ud_i
+              Us_i = C(d_i):  rpb_mwt_conv3
+    coarsest: rpb_mwt_coarse (T0 on the row-major (B, 1, 1, T, 36 * W/H) view)
+    level i, upwards: rpb_mwt_reconstruct (x + Us_i, cat Ud_i, rc_*, scatter to the 2 x 2 children; the ReLU between two CZ blocks
+              rides in the top level's launch)
+``BN`` (one BatchNorm3d per CZ block) exists for ``state_dict`` compatibility and is never computed, as in the reference.
+
+Parameters carry the reference's names, shapes and dtypes (``nn`` modules of the same tree), so ``state_dict`` / ``load_state_dict``
+are the reference's; the kernel layouts (lane-ordered convolution weights, mode-major spectral weights, transposed linears) are
+derived tensors rebuilt when a parameter changed (``_prep``).
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+from numpy.polynomial import Polynomial
+from numpy.polynomial import legendre as npleg
+
+from .. import _lib
+from ..dft import _fwd_complex, _fwd_real, _inv_complex, _inv_real
+from .model import _META_KEYS, Model
+
+MWT_TRAIN_MSG = ("the MWT training step is not built yet: MWT3d on MI355X covers the evaluation forward, train_loss as a value under "
+                 "torch.no_grad(), the rollout and checkpoint I/O")
+
+
+# ----------------------------------------------------------------------------------------------------------- filter bank (numpy only)
+def _int01(p, a, b):
+    q = p.integ()
+    return q(b) - q(a)
+
+
+def _clean(a):
+    a[np.abs(a) < 1e-8] = 0
+    return a
+
+
+def legendre_filter(k):
+    """``get_filter('legendre', k)`` of the reference (MWT_libs/utils_MWT.py:22-72,131-190) without sympy / scipy: the orthonormal
+    Legendre scaling functions phi_i(x) = sqrt(2i+1) P_i(2x-1) on [0, 1], the multiwavelets psi_i by Gram-Schmidt of sqrt(2) phi_i(2x)
+    (piecewise polynomials psi1 on [0, 1/2], psi2 on [1/2, 1]) and the two-scale matrices by k-point Gauss-Legendre quadrature.
+    Returns (H0, H1, G0, G1, PHI0, PHI1), float64."""
+    k = int(k)
+    lin = lambda a, b: Polynomial([a, b])
+    P = [Polynomial(npleg.leg2poly([0.0] * i + [1.0])) for i in range(k)]
+    phi = [math.sqrt(2 * i + 1) * P[i](lin(-1.0, 2.0)) for i in range(k)]
+    phi2 = [math.sqrt(2.0) * math.sqrt(2 * i + 1) * P[i](lin(-1.0, 4.0)) for i in range(k)]
+    psi1, psi2 = [], []
+    for i in range(k):
+        p1, p2 = phi2[i], Polynomial([0.0])
+        for j in range(k):
+            proj = _int01(phi2[i] * phi[j], 0.0, 0.5)
+            p1, p2 = p1 - proj * phi[j], p2 - proj * phi[j]
+        for j in range(i):
+            proj = _int01(phi2[i] * psi1[j], 0.0, 0.5)
+            p1, p2 = p1 - proj * psi1[j], p2 - proj * psi2[j]
+        norm = math.sqrt(_int01(p1 * p1, 0.0, 0.5) + _int01(p2 * p2, 0.5, 1.0))
+        pad = lambda p: np.concatenate([p.coef, np.zeros(k)])[:k]
+        psi1.append(Polynomial(_clean(pad(p1) / norm)))
+        psi2.append(Polynomial(_clean(pad(p2) / norm)))
+    xg, wg = npleg.leggauss(k)
+    xm, wm = (xg + 1.0) / 2.0, wg / 2.0
+    psi = lambda i, x: np.where(x <= 0.5, psi1[i](x), psi2[i](x))
+    H0, H1, G0, G1 = (np.zeros((k, k)) for _ in range(4))
+    for a in range(k):
+        for b in range(k):
+            H0[a, b] = (wm * phi[a](xm / 2) * phi[b](xm)).sum() / math.sqrt(2.0)
+            G0[a, b] = (wm * psi(a, xm / 2) * phi[b](xm)).sum() / math.sqrt(2.0)
+            H1[a, b] = (wm * phi[a]((xm + 1) / 2) * phi[b](xm)).sum() / math.sqrt(2.0)
+            G1[a, b] = (wm * psi(a, (xm + 1) / 2) * phi[b](xm)).sum() / math.sqrt(2.0)
+    return _clean(H0), _clean(H1), _clean(G0), _clean(G1), np.eye(k), np.eye(k)
+
+
+def cz_buffers(k, base="legendre"):
+    """The six constant maps of MWT_CZ3d (models.py:599-648), float32: ec_s, ec_d [4 k^2, k^2]; rc_ee, rc_eo, rc_oe, rc_oo [2 k^2, k^2]."""
+    if base != "legendre":
+        raise NotImplementedError(f"MI355X MWT3d: base={base!r} is not built (no reference YAML uses it); only base='legendre'")
+    H0, H1, G0, G1, PHI0, PHI1 = legendre_filter(k)
+    H0r, G0r, H1r, G1r = _clean(H0 @ PHI0), _clean(G0 @ PHI0), _clean(H1 @ PHI1), _clean(G1 @ PHI1)
+    kr, cat = np.kron, lambda *a: torch.tensor(np.concatenate(a, axis=0), dtype=torch.float32)
+    return {
+        "ec_s": cat(kr(H0, H0).T, kr(H0, H1).T, kr(H1, H0).T, kr(H1, H1).T),
+        "ec_d": cat(kr(G0, G0).T, kr(G0, G1).T, kr(G1, G0).T, kr(G1, G1).T),
+        "rc_ee": cat(kr(H0r, H0r), kr(G0r, G0r)),
+        "rc_eo": cat(kr(H0r, H1r), kr(G0r, G1r)),
+        "rc_oe": cat(kr(H1r, H0r), kr(G1r, G0r)),
+        "rc_oo": cat(kr(H1r, H1r), kr(G1r, G1r)),
+    }
+
+
+# ----------------------------------------------------------------------------------------------------------- corner-block table
+def _axis_rows(n, modes):
+    """Retained frequency rows of a two-sided axis of length ``n`` and, per row, (high, weight index): ``[:l]`` reads weight rows
+    0..l-1, ``[-l:]`` reads them again on rows n-l..n-1; where the two overlap the later (high) assignment wins (models.py:569-576)."""
+    l = min(modes, n // 2 + 1)
+    rows = sorted(set(range(l)) | set(range(n - l, n)))
+    return rows, [(1, r - (n - l)) if r >= n - l else (0, r) for r in rows]
+
+
+def corner_table(Nx, Ny, modes):
+    """(kx rows, ky rows, tab): ``tab[(a * KY + b) * modes + kt]`` = block * modes^3 + (ix * modes + iy) * modes + kt, block 0..3 =
+    weights1..4, for the retained output bin (kx[a], ky[b], kt) of sparseKernelFT3d at an ``Nx x Ny`` level."""
+    kx, mx = _axis_rows(Nx, modes)
+    ky, my = _axis_rows(Ny, modes)
+    tab = np.empty((len(kx), len(ky), modes), dtype=np.int32)
+    for a, (hx, ix) in enumerate(mx):
+        for b, (hy, iy) in enumerate(my):
+            tab[a, b] = (hx + 2 * hy) * modes ** 3 + (ix * modes + iy) * modes + np.arange(modes)
+    return kx, ky, tab.reshape(-1)
+
+
+class LevelPlan:
+    """Truncated-DFT stage matrices (dft.py conventions) and the corner table of one ``Nx x Ny x T`` level."""
+
+    def __init__(self, Nx, Ny, T, modes, device="cpu"):
+        self.Nx, self.Ny, self.T, self.modes = Nx, Ny, T, modes
+        self.kx, self.ky, tab = corner_table(Nx, Ny, modes)
+        self.KX, self.KY = len(self.kx), len(self.ky)
+        kt = list(range(modes))
+        f = lambda m: torch.from_numpy(np.ascontiguousarray(m)).to(torch.float32).to(device)
+        self.FT = f(_fwd_real(T, kt))                       # [2 m, T]
+        self.FY = f(_fwd_complex(Ny, self.ky))              # [2 KY, 2 Ny]
+        self.FX = f(_fwd_complex(Nx, self.kx))              # [2 KX, 2 Nx]
+        self.GX = f(_inv_complex(Nx, self.kx))              # [2 Nx, 2 KX]
+        self.GY = f(_inv_complex(Ny, self.ky))              # [2 Ny, 2 KY]
+        self.GT = f(_inv_real(T, kt, float(Nx) * Ny * T))   # [T, 2 m]: c2r of irfftn incl. 1 / (Nx Ny T)
+        self.tab = torch.from_numpy(tab).to(device)
+
+
+# ----------------------------------------------------------------------------------------------------------- parameter tree
+class _SparseKernelFT3d(nn.Module):
+    def __init__(self, k, alpha, c):
+        super().__init__()
+        w = c * k ** 2
+        for i in range(1, 5):
+            p = nn.Parameter(torch.zeros(w, w, alpha, alpha, alpha, dtype=torch.cfloat))
+            nn.init.xavier_normal_(p)
+            setattr(self, f"weights{i}", p)
+        self.Lo = nn.Linear(w, w)
+
+
+class _SparseKernel3d(nn.Module):
+    def __init__(self, k, c):
+        super().__init__()
+        w = c * k ** 2
+        self.conv = nn.Sequential(nn.Conv3d(w, w, 3, 1, 1), nn.ReLU(inplace=True))
+        self.Lo = nn.Linear(w, w)
+
+
+class _CZ(nn.Module):
+    def __init__(self, k, alpha, c, mult, base, initializer):
+        super().__init__()
+        self.A = _SparseKernelFT3d(k, alpha, c)
+        self.B = _SparseKernel3d(k, c)
+        self.C = _SparseKernel3d(k, c)
+        self.T0 = nn.Linear(c * k ** 2 * mult, c * k ** 2)
+        if initializer is not None:
+            initializer(self.T0.weight)
+        for name, t in cz_buffers(k, base).items():
+            self.register_buffer(name, t)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _p(t):
+    if not t.is_cuda:
+        raise _lib.RpbError("realpdebench_amd ops need tensors on a HIP device (no CPU fallback exists)")
+    assert t.is_contiguous() and t.dtype in (torch.float32, torch.int32)
+    return t.data_ptr()
+
+
+class MWT3d(Model):
+    batch_independent = True      # no batch statistics are ever computed (BN is never called)
+    training_unavailable = MWT_TRAIN_MSG      # trainer.make_trainer refuses at construction
+
+    def __init__(self, k=3, alpha=2, c=1, nCZ=3, L=0, base="legendre", initializer=None, shape_in=None, shape_out=None, **kwargs):
+        super().__init__()
+        self.shape_in, self.shape_out = tuple(int(v) for v in shape_in), tuple(int(v) for v in shape_out)
+        T, H, W, Cin = self.shape_in
+        unsupported = []
+        if base != "legendre":
+            raise NotImplementedError(f"MI355X MWT3d: base={base!r} is not built (no reference YAML uses it); only base='legendre'")
+        if L != 0:
+            unsupported.append(f"L={L} (only L=0)")
+        if c * k ** 2 != 36:
+            unsupported.append(f"c*k^2={c * k ** 2} (the kernels are built for 36 = 4 * 3^2)")
+        if H < 2 or H & (H - 1):
+            unsupported.append(f"H={H} is not a power of two")
+        elif W % H or (W // H) & (W // H - 1):
+            unsupported.append(f"W={W} is not H * 2^j")
+        if T // 2 + 1 < alpha:
+            unsupported.append(f"T={T} keeps {T // 2 + 1} rfft bins < alpha={alpha}")
+        if self.shape_out[0] % T or tuple(self.shape_out[1:3]) != (H, W):
+            unsupported.append(f"shape_out={self.shape_out} (T_out must be a multiple of T_in on the same grid)")
+        if unsupported:
+            raise NotImplementedError("MI355X MWT3d covers the configuration family of the reference's configs/*/mwt.yaml; "
+                                      "unsupported: " + "; ".join(unsupported))
+        self.k, self.c, self.L, self.nCZ, self.alpha = int(k), int(c), int(L), int(nCZ), int(alpha)
+        self.dim_in = Cin
+        self.dim_out = self.shape_out[-1] * self.shape_out[0] // T
+        self.mult = W // H
+        self.ns = int(math.log2(H))
+        w = c * k ** 2
+        self.Lk = nn.Linear(Cin, w)
+        self.MWT_CZ = nn.ModuleList([_CZ(k, alpha, c, self.mult, base, initializer) for _ in range(nCZ)])
+        self.BN = nn.ModuleList([nn.BatchNorm3d(w) for _ in range(nCZ)])
+        self.Lc0 = nn.Linear(w, 128)
+        self.Lc1 = nn.Linear(128, self.dim_out)
+        if initializer is not None:
+            initializer(self.Lc0.weight)
+            initializer(self.Lc1.weight)
+        self._plans, self._prepped = {}, None
+
+    # ------------------------------------------------------------------ checkpoints (models.py:791-844)
+    def load_checkpoint(self, checkpoint_path, device="cpu"):
+        """Key and shape matching as in the reference: entries whose name and shape agree are loaded, the rest are reported and left.
+        Returns the bookkeeping entries like the other models; a bare weights file (which the reference's method accepts too) gives
+        the entries of an untrained run (iteration 0, no losses)."""
+        import logging
+        ck = torch.load(checkpoint_path, map_location="cpu")
+        sd = ck.get("model", ck.get("model_state_dict", ck))
+        own = self.state_dict()
+        ok = {key: v for key, v in sd.items() if key in own and tuple(v.shape) == tuple(own[key].shape)}
+        skipped = [key for key in sd if key not in ok]
+        logging.info(f"MWT3d.load_checkpoint: {len(ok)}/{len(sd)} entries match" + (f"; skipped {skipped[:5]}" if skipped else ""))
+        self.load_state_dict(ok, strict=False)
+        self.to(device)
+        blank = {"train_losses": [], "val_losses": {}, "iteration": 0, "best_iteration": 0, "best_val_loss": float("inf")}
+        book = ck if sd is not ck else {}
+        return {meta: book.get(key, blank[key]) for key, meta in _META_KEYS.items()}
+
+    # ------------------------------------------------------------------ kernel-side layouts
+    def _plan(self, Nx, Ny, device):
+        key = (Nx, Ny, str(device))
+        if key not in self._plans:
+            self._plans[key] = LevelPlan(Nx, Ny, self.shape_in[0], self.alpha, device)
+        return self._plans[key]
+
+    def _prep(self, device):
+        stamp = (str(device),) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._prepped is not None and self._prepped[0] == stamp:
+            return self._prepped[1]
+        f = dict(device=device, dtype=torch.float32)
+        czs = []
+        for cz in self.MWT_CZ:
+            d = {}
+            for name in ("B", "C"):
+                m = getattr(cz, name)
+                wp, lop = torch.empty(27 * 9 * 3 * 64, **f), torch.empty(3 * 4 * 3 * 64, **f)
+                _lib.call("rpb_mwt_conv3_wprep", _p(m.conv[0].weight.detach().contiguous()), _p(m.Lo.weight.detach().contiguous()),
+                          _p(wp), _p(lop), _stream())
+                cb = torch.zeros(48, **f)
+                cb[:36] = m.conv[0].bias.detach()
+                d[name] = (wp, cb, lop, m.Lo.bias.detach().contiguous())
+            A = cz.A
+            ws = torch.stack([getattr(A, f"weights{i}").detach() for i in range(1, 5)])          # [4][i][o][x][y][t]
+            d["Wt"] = torch.view_as_real(ws.permute(0, 3, 4, 5, 1, 2).contiguous()).contiguous()  # [4][x][y][t][i][o][2]
+            d["loT"], d["lb"] = A.Lo.weight.detach().t().contiguous(), A.Lo.bias.detach().contiguous()
+            d["T0w"], d["T0b"] = cz.T0.weight.detach().contiguous(), cz.T0.bias.detach().contiguous()
+            d["rc"] = torch.stack([cz.rc_ee, cz.rc_eo, cz.rc_oe, cz.rc_oo]).contiguous()
+            d["ec_d"], d["ec_s"] = cz.ec_d.contiguous(), cz.ec_s.contiguous()
+            czs.append(d)
+        prep = dict(cz=czs, Lkw=self.Lk.weight.detach().contiguous(), Lkb=self.Lk.bias.detach().contiguous(),
+                    w0t=self.Lc0.weight.detach().t().contiguous(), b0=self.Lc0.bias.detach().contiguous(),
+                    w1=self.Lc1.weight.detach().contiguous(), b1=self.Lc1.bias.detach().contiguous())
+        self._prepped = (stamp, prep)
+        return prep
+
+    # ------------------------------------------------------------------ the kernels, one method per family (tests call these)
+    @staticmethod
+    def k_lift(x, w, b):
+        B, T, H, W, Cin = x.shape
+        out = torch.empty(B, H, W, T, 36, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_lift", _p(x), _p(w), _p(b), _p(out), B, T, H, W, Cin, _stream(), label="mwt_lift",
+                  nbytes=4 * B * T * H * W * (Cin + 36))
+        return out
+
+    @staticmethod
+    def k_decompose(x, ec_d, ec_s):
+        B, Nx, Ny, T, _ = x.shape
+        d = torch.empty(B, Nx // 2, Ny // 2, T, 36, device=x.device, dtype=torch.float32)
+        s = torch.empty_like(d)
+        _lib.call("rpb_mwt_decompose", _p(x), _p(ec_d), _p(ec_s), _p(d), _p(s), B, Nx // 2, Ny // 2, T, _stream(), label="mwt_decompose",
+                  nbytes=4 * x.numel() + 8 * d.numel(), flops=2 * 2 * 36 * d.numel())
+        return d, s
+
+    @staticmethod
+    def k_reconstruct(x, us, ud, rc, relu):
+        B, Nx, Ny, T, _ = us.shape
+        out = torch.empty(B, 2 * Nx, 2 * Ny, T, 36, device=us.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_reconstruct", _p(x), _p(us), _p(ud), _p(rc), _p(out), B, Nx, Ny, T, x.shape[2], int(relu), _stream(),
+                  label="mwt_reconstruct", nbytes=4 * (x.numel() + 2 * us.numel() + out.numel()), flops=2 * 4 * 18 * us.numel())
+        return out
+
+    @staticmethod
+    def k_coarse(x, w, b):
+        B, T = x.shape[0], x.shape[3]
+        K = w.shape[1]
+        out = torch.empty(B, 1, 1, T, 36, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_coarse", _p(x), _p(w), _p(b), _p(out), B * T, K, _stream(), label="mwt_coarse")
+        return out
+
+    @staticmethod
+    def k_conv3(x, pack, out=None):
+        """sparseKernel3d; ``out`` given = accumulate into it."""
+        wp, cb, lop, lb = pack
+        B, Nx, Ny, T, _ = x.shape
+        acc = out is not None
+        if out is None:
+            out = torch.empty_like(x)
+        _lib.call("rpb_mwt_conv3", _p(x), _p(wp), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), _stream(), label="mwt_conv3",
+                  nbytes=4 * x.numel() * (3 if acc else 2), flops=2 * x.numel() * (27 * 36 + 36))
+        return out
+
+    @staticmethod
+    def k_axis(inp, M, outer, inner):
+        O, K = M.shape
+        out = torch.empty(outer * O * inner, device=inp.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_axis", _p(inp), _p(M), _p(out), outer, O, K, inner, _stream(), label="mwt_axis",
+                  nbytes=4 * outer * inner * (O + K), flops=2 * outer * inner * O * K)
+        return out
+
+    @staticmethod
+    def k_spectral(d, plan, Wt, loT, lb, out=None):
+        """sparseKernelFT3d on ``d`` [B][Nx][Ny][T][36]; ``out`` given = accumulate into it."""
+        B, Nx, Ny, T, C = d.shape
+        m, KX, KY = plan.modes, plan.KX, plan.KY
+        y = MWT3d.k_axis(d, plan.FT, B * Nx * Ny, C)                        # [B][Nx][Ny][(ri, kt)][36]
+        y = MWT3d.k_axis(y, plan.FY, B * Nx, m * C)                         # [B][Nx][(ri, ky)][kt][36]
+        X = MWT3d.k_axis(y, plan.FX, B, KY * m * C)                         # [B][(ri, kx)][ky][kt][36]
+        NB = KX * KY * m
+        Y = torch.empty_like(X)
+        _lib.call("rpb_mwt_modes", _p(X), _p(Wt), _p(plan.tab), _p(Y), B, NB, _stream(), label="mwt_modes",
+                  nbytes=16 * B * NB * C + 8 * NB * C * C, flops=8 * B * NB * C * C)
+        z = MWT3d.k_axis(Y, plan.GX, B, KY * m * C)                         # [B][(x, ri)][ky][kt][36]
+        z = MWT3d.k_axis(z, plan.GY, B * Nx, m * C)                         # [B][Nx][(y, ri)][kt][36]
+        acc = out is not None
+        if out is None:
+            out = torch.empty_like(d)
+        _lib.call("rpb_mwt_spec_out", _p(z), _p(plan.GT), _p(loT), _p(lb), _p(out), B * Nx * Ny, T, 2 * m, int(acc), _stream(),
+                  label="mwt_spec_out", nbytes=4 * d.numel() * (2 if acc else 1) + 4 * z.numel(), flops=2 * d.numel() * (2 * m + C))
+        return out
+
+    @staticmethod
+    def k_head(x, w0t, b0, w1, b1, Cout, r):
+        B, Nx, Ny, T, _ = x.shape
+        out = torch.empty(B, T * r, Nx, Ny, Cout, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_head", _p(x), _p(w0t), _p(b0), _p(w1), _p(b1), _p(out), B, Nx, Ny, T, Cout, r, _stream(), label="mwt_head",
+                  nbytes=4 * (x.numel() + out.numel()), flops=2 * B * Nx * Ny * T * 128 * (36 + Cout * r))
+        return out
+
+    # ------------------------------------------------------------------ forward
+    def _cz_forward(self, x, p, relu, keep=None):
+        """One MWT_CZ3d block.  ``keep`` (a dict) receives the per-level tensors d, s, A(d) + B(s) and C(d) (tests; the follow-up's
+        backward needs exactly these)."""
+        Ud, Us = [], []
+        for i in range(self.ns):
+            d, x = self.k_decompose(x, p["ec_d"], p["ec_s"])
+            plan = self._plan(d.shape[1], d.shape[2], d.device)
+            ud = self.k_spectral(d, plan, p["Wt"], p["loT"], p["lb"])
+            self.k_conv3(x, p["B"], out=ud)
+            Ud.append(ud)
+            Us.append(self.k_conv3(d, p["C"]))
+            if keep is not None:
+                keep.setdefault("d", []).append(d)
+                keep.setdefault("s", []).append(x)
+        x = self.k_coarse(x, p["T0w"], p["T0b"])
+        for i in range(self.ns - 1, -1, -1):
+            x = self.k_reconstruct(x, Us[i], Ud[i], p["rc"], relu and i == 0)
+        if keep is not None:
+            keep["Ud"], keep["Us"] = Ud, Us
+        return x
+
+    def forward(self, x):
+        # never hand back a tensor that silently carries no graph: under grad mode anything that asks for a gradient is refused
+        # (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with requires_grad off)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(MWT_TRAIN_MSG)
+        if not x.is_cuda:
+            raise RuntimeError("MWT3d runs on MI355X only: there is no CPU fallback (move the model and its input to 'cuda')")
+        if tuple(x.shape[1:]) != self.shape_in:
+            raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(x.shape)}")
+        with torch.no_grad():
+            x = x.contiguous().float()
+            p = self._prep(x.device)
+            h = self.k_lift(x, p["Lkw"], p["Lkb"])
+            for i, cz in enumerate(p["cz"]):
+                h = self._cz_forward(h, cz, relu=i < self.nCZ - 1)
+            return self.k_head(h, p["w0t"], p["b0"], p["w1"], p["b1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])
+
+    def train_loss(self, input, target):
+        """Elementwise MSE (the reference's ``mse_loss(pred, target)``), as a value: under grad mode it raises, see the module docstring."""
+        if torch.is_grad_enabled():
+            raise NotImplementedError(MWT_TRAIN_MSG)
+        pred = self.forward(input)
+        return (pred - target) ** 2

@@ -359,6 +359,8 @@ class ArenaTrainer:
 
 def make_trainer(model, lr, num_update, scheduler="cosine", step_size=1000, clip_grad_norm=0.0, micro_batch=None):
     """Fused trainer for FNO3d (one flat arena built into the model), ArenaTrainer for the nn.Parameter models."""
+    if getattr(model, "training_unavailable", None):          # eval-only models (MWT3d) stop here, not inside a step
+        raise NotImplementedError(model.training_unavailable)
     if hasattr(model, "flat"):
         if torch.distributed.is_available() and torch.distributed.is_initialized() and model.dp is None:
             from .dp import DataParallel

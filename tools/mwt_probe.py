@@ -1,0 +1,102 @@
+"""MWT3d eval forward at the cylinder shape on one MI355X: median time over >= 20 runs for B = 1, 8, 32 and a per-family kernel table
+from HIP events (algorithmic bytes and FLOPs of each launch are the bookkeeping of model/mwt.py).  Launches under ~100 us are dominated
+by the event overhead in this table: take those from `rocprofv3 --kernel-trace --stats -- python tools/mwt_probe.py
+--no-events` instead.
+    python tools/mwt_probe.py [--batches 1 8 32] [--runs 20] [--no-events] [--out profiles/mwt_probe.txt]"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from realpdebench_amd import _lib                         # noqa: E402
+from realpdebench_amd.model.mwt import MWT3d              # noqa: E402
+
+HBM_PEAK, COPY_CEIL = 8.0e12, (5.2e12, 6.0e12)           # B/s: data-sheet peak; the copy ceiling measured in this repository
+SHAPE = (20, 64, 128, 3)
+
+
+def sustained_bf16():
+    """The matrix rate this repository states its convolution fractions against (bench.py mfma_ceiling, random operands), TFLOP/s."""
+    from realpdebench_amd import ops
+    seed, out = torch.randn(4096, device="cuda:0"), torch.empty(256 * 2 * 512, device="cuda:0")
+    ops.mfma_probe(seed, out, 2000)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fl = ops.mfma_probe(seed, out, 40000)
+    e1.record()
+    torch.cuda.synchronize()
+    return fl / (e0.elapsed_time(e1) * 1e9)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--no-events", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/mwt_probe.py measures on an MI355X: no GPU, no number")
+    torch.manual_seed(0)
+    m = MWT3d(k=3, alpha=5, c=4, nCZ=4, L=0, base="legendre", shape_in=SHAPE, shape_out=SHAPE).to("cuda:0").eval()
+    lines = []
+    sustained = sustained_bf16()
+    fl_rate = lambda v: v["flops"] * v["calls"] / (v["total_ms"] * 1e-3) / 1e12
+    lines.append(f"sustained bf16 MFMA rate of this chip (rpb_mfma_probe, random operands): {sustained:.0f} TFLOP/s")
+    for B in a.batches:
+        x = torch.randn(B, *SHAPE, device="cuda:0")
+        with torch.no_grad():
+            for _ in range(3):
+                m(x)
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(a.runs):
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                m(x)
+                e.record()
+                torch.cuda.synchronize()
+                ts.append(s.elapsed_time(e))
+        med = statistics.median(ts)
+        lines.append(f"B={B}: eval forward median {med:.3f} ms over {a.runs} runs (min {min(ts):.3f}, max {max(ts):.3f}); "
+                     f"{B / med * 1e3:.1f} samples/s")
+        if a.no_events:
+            continue
+        _lib.PROFILE = {}
+        with torch.no_grad():
+            m(x)
+        torch.cuda.synchronize()
+        summ = _lib.profile_summary()
+        _lib.PROFILE = None
+        tot = sum(v["total_ms"] for v in summ.values())
+        stream_bytes = sum(v["bytes"] * v["calls"] for v in summ.values())
+        lines.append(f"  HIP-event table (one forward, sum {tot:.3f} ms incl. event overhead; algorithmic bytes {stream_bytes / 1e9:.2f} GB = "
+                     f"{stream_bytes / COPY_CEIL[1] * 1e3:.2f}-{stream_bytes / COPY_CEIL[0] * 1e3:.2f} ms at the 5.2-6.0 TB/s copy ceiling)")
+        lines.append(f"  {'family':<16}{'calls':>6}{'total ms':>10}{'GB':>9}{'of 8 TB/s':>11}{'TFLOP/s':>9}")
+        for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"]):
+            by, fl, t = v["bytes"] * v["calls"], v["flops"] * v["calls"], v["total_ms"] * 1e-3
+            lines.append(f"  {k:<16}{v['calls']:>6}{v['total_ms']:>10.3f}{by / 1e9:>9.3f}{by / t / HBM_PEAK:>11.3f}{fl / t / 1e12:>9.2f}")
+        if "mwt_conv3" in summ:
+            v = summ["mwt_conv3"]
+            # one v_mfma_f32_16x16x4_f32 = 16 * 16 * 4 * 2 FLOP on the 48-row padded tile; issued per 64 cells: 27 * 9 * 12 + 12 * 12
+            cells = v["flops"] * v["calls"] / (2 * (27 * 36 + 36) * 36)
+            mf = cells / 64 * (27 * 9 * 12 + 12 * 12)
+            issued = mf * 2048 / (v["total_ms"] * 1e-3) / 1e12
+            lines.append(f"  mwt_conv3: {mf:.3e} MFMA (16x16x4 f32) = {issued:.1f} TFLOP/s issued = {issued / (sustained / 16):.2f} of the fp32 "
+                         f"MFMA ceiling (sustained bf16 rate {sustained:.0f} TFLOP/s measured here with random operands, / 16); useful rows "
+                         f"36/48.  fp32-grade FLOP/s delivered {fl_rate(v):.1f} TFLOP/s; conv3x's split-bf16 (3 products per fp32-grade product) "
+                         f"at its documented 0.75-0.86 of the sustained rate delivers {0.75 * sustained / 3:.0f}-{0.86 * sustained / 3:.0f}")
+    txt = "\n".join(lines)
+    print(txt)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
