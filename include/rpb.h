@@ -693,6 +693,15 @@ int rpb_mwt_spec_out(const float* S, const float* GT, const float* loT, const fl
 int rpb_mwt_conv3_wprep(const float* w, const float* lo, float* wp, float* lop, void* stream);
 int rpb_mwt_conv3(const float* x, const float* wp, const float* cb48, const float* lop, const float* lb, float* out, int B, int Nx, int Ny,
                   int T, int accumulate, void* stream);
+/*     the same operator on the split-operand arithmetic of csrc/rpb_mma.h (csrc/rpb_mwt3x.hip; MWT3d.set_arith): planes = 3 ("bf16x3":
+ *     operands as three bf16 planes, six products per fp32 product; ea, ew unused, may be NULL) or planes = 2 ("f16x2": two fp16
+ *     planes of the tensor scaled by an exact power of two, three products, dropped term <= 2^-22 |a b|; ew = rpb_amax_exp(w, 36,
+ *     972, 972), ea = rpb_amax_exp(x, cells, 36, 36), both read from device memory: no host synchronisation).  wprep: w
+ *     [36][36][3][3][3] -> wpx [31 K steps][3 row tiles][planes][64 lanes] x 16 bytes (K = 27 * 36 flat, padded to 992).  cb48, lop,
+ *     lb and the shapes as rpb_mwt_conv3 (lop from rpb_mwt_conv3_wprep: Lo stays on the fp32 MFMA). */
+int rpb_mwt_conv3x_wprep(const float* w, void* wpx, int planes, const int* ew, void* stream);
+int rpb_mwt_conv3x(const float* x, const void* wpx, const float* cb48, const float* lop, const float* lb, float* out, int B, int Nx,
+                   int Ny, int T, int accumulate, int planes, const int* ea, const int* ew, void* stream);
 /*     head: Lc0 (w0t [36][128], b0), ReLU, Lc1 (w1 [Cout * r][128], b1) and the output permute: x [B][Nx][Ny][T][36] ->
  *     out [B][T * r][Nx][Ny][Cout] */
 int rpb_mwt_head(const float* x, const float* w0t, const float* b0, const float* w1, const float* b1, float* out, int B, int Nx, int Ny,

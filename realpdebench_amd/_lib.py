@@ -199,6 +199,8 @@ SIGNATURES = {
     "rpb_mwt_spec_out": (_I, "ppppp" + "liii" + "p"),
     "rpb_mwt_conv3_wprep": (_I, "pppp" + "p"),
     "rpb_mwt_conv3": (_I, "pppppp" + "iiiii" + "p"),
+    "rpb_mwt_conv3x_wprep": (_I, "pp" + "i" + "p" + "p"),
+    "rpb_mwt_conv3x": (_I, "pppppp" + "iiiii" + "i" + "pp" + "p"),
     "rpb_mwt_head": (_I, "pppppp" + "iiiiii" + "p"),
 }
 

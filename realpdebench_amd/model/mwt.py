@@ -17,6 +17,8 @@ Pipeline (activations channels-last fp32 ``[B][Nx][Ny][T][36]``, 36 = (c, k^2) =
     coarsest: rpb_mwt_coarse (T0 on the row-major (B, 1, 1, T, 36 * W/H) view)
     level i, upwards: rpb_mwt_reconstruct (x + Us_i, cat Ud_i, rc_*, scatter to the 2 x 2 children; the ReLU between two CZ blocks
               rides in the top level's launch)
+``set_arith("bf16x3" | "f16x2")`` moves the rpb_mwt_conv3 launches (and nothing else) to rpb_mwt_conv3x of ``csrc/rpb_mwt3x.hip``: the
+same operator with its operands as 16-bit planes on the bf16 / fp16 matrix pipe; the default ``"f32"`` is the parity path.
 ``BN`` (one BatchNorm3d per CZ block) exists for ``state_dict`` compatibility and is never computed, as in the reference.
 
 Parameters carry the reference's names, shapes and dtypes (``nn`` modules of the same tree), so ``state_dict`` / ``load_state_dict``
@@ -34,6 +36,9 @@ from numpy.polynomial import legendre as npleg
 from .. import _lib
 from ..dft import _fwd_complex, _fwd_real, _inv_complex, _inv_real
 from .model import _META_KEYS, Model
+
+ARITHS = ("f32", "bf16x3", "f16x2")      # MWT3d.set_arith
+_PLANES = {"bf16x3": 3, "f16x2": 2}      # 16-bit planes per operand of rpb_mwt_conv3x
 
 MWT_TRAIN_MSG = ("the MWT training step is not built yet: MWT3d on MI355X covers the evaluation forward, train_loss as a value under "
                  "torch.no_grad(), the rollout and checkpoint I/O")
@@ -227,6 +232,18 @@ class MWT3d(Model):
             initializer(self.Lc0.weight)
             initializer(self.Lc1.weight)
         self._plans, self._prepped = {}, None
+        self.arith = "f32"
+
+    def set_arith(self, arith):
+        """Arithmetic of the ``sparseKernel3d`` convolutions (kernels B and C of every CZ block and level) in the evaluation / rollout
+        forward: ``"f32"`` (default, the parity path: ``rpb_mwt_conv3`` on the fp32 MFMA), ``"bf16x3"`` (opt-in: operands as three bf16
+        planes, ``hi + mid + lo`` exact, six products per fp32 product, fp32 accumulation) or ``"f16x2"`` (opt-in: operands as two fp16
+        planes of the tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_mwt3x.hip).  Everything else in
+        the forward is unchanged; training stays refused under every mode."""
+        if arith not in ARITHS:
+            raise ValueError(f"arith must be 'f32', 'bf16x3' or 'f16x2', got {arith!r}")
+        self.arith = arith
+        return self
 
     # ------------------------------------------------------------------ checkpoints (models.py:791-844)
     def load_checkpoint(self, checkpoint_path, device="cpu"):
@@ -254,7 +271,7 @@ class MWT3d(Model):
         return self._plans[key]
 
     def _prep(self, device):
-        stamp = (str(device),) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        stamp = (str(device), self.arith) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._prepped is not None and self._prepped[0] == stamp:
             return self._prepped[1]
         f = dict(device=device, dtype=torch.float32)
@@ -269,6 +286,8 @@ class MWT3d(Model):
                 cb = torch.zeros(48, **f)
                 cb[:36] = m.conv[0].bias.detach()
                 d[name] = (wp, cb, lop, m.Lo.bias.detach().contiguous())
+                if self.arith != "f32":           # the A operand as 16-bit planes, only for the selected mode
+                    d[name] += self.k_conv3_wprep(m.conv[0].weight.detach().contiguous(), self.arith)
             A = cz.A
             ws = torch.stack([getattr(A, f"weights{i}").detach() for i in range(1, 5)])          # [4][i][o][x][y][t]
             d["Wt"] = torch.view_as_real(ws.permute(0, 3, 4, 5, 1, 2).contiguous()).contiguous()  # [4][x][y][t][i][o][2]
@@ -318,15 +337,42 @@ class MWT3d(Model):
         return out
 
     @staticmethod
-    def k_conv3(x, pack, out=None):
-        """sparseKernel3d; ``out`` given = accumulate into it."""
-        wp, cb, lop, lb = pack
+    def k_conv3_wprep(w, arith):
+        """Conv3d weight [36][36][3][3][3] -> (wpx, ew): the planes of ``rpb_mwt_conv3x`` for ``arith`` and, for ``"f16x2"``, the
+        weight's power-of-two exponent (int32 on the device; None for ``"bf16x3"``)."""
+        planes = _PLANES[arith]
+        wpx = torch.empty(31 * 3 * planes * 64 * 8, device=w.device, dtype=torch.int16)
+        ew = None
+        if planes == 2:
+            ew = torch.empty(1, device=w.device, dtype=torch.int32)
+            _lib.call("rpb_amax_exp", _p(w), 36, 972, 972, ew.data_ptr(), _stream(), label="amax_exp", nbytes=4 * w.numel())
+        _lib.call("rpb_mwt_conv3x_wprep", _p(w), wpx.data_ptr(), planes, ew.data_ptr() if planes == 2 else None, _stream())
+        return wpx, ew
+
+    @staticmethod
+    def k_conv3(x, pack, out=None, arith="f32"):
+        """sparseKernel3d; ``out`` given = accumulate into it.  ``arith`` other than ``"f32"`` needs the pack extended by
+        ``k_conv3_wprep`` for that mode."""
+        wp, cb, lop, lb = pack[:4]
         B, Nx, Ny, T, _ = x.shape
         acc = out is not None
         if out is None:
             out = torch.empty_like(x)
+        nbytes, flops = 4 * x.numel() * (3 if acc else 2), 2 * x.numel() * (27 * 36 + 36)
+        if arith != "f32":
+            if len(pack) != 6 or pack[4].numel() != 31 * 3 * _PLANES[arith] * 64 * 8:
+                raise _lib.RpbError(f"k_conv3: the weight pack was not prepared for arith={arith!r}")
+            wpx, ew = pack[4:]
+            planes, ea = _PLANES[arith], None
+            if planes == 2:                       # per-tensor exponent of the activations, kept on the device
+                ea = torch.empty(1, device=x.device, dtype=torch.int32)
+                _lib.call("rpb_amax_exp", _p(x), x.numel() // 36, 36, 36, ea.data_ptr(), _stream(), label="mwt_amax_exp", nbytes=4 * x.numel())
+            _lib.call("rpb_mwt_conv3x", _p(x), wpx.data_ptr(), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), planes,
+                      ea.data_ptr() if planes == 2 else None, ew.data_ptr() if planes == 2 else None, _stream(),
+                      label=f"mwt_conv3[{arith}]", nbytes=nbytes, flops=flops)
+            return out
         _lib.call("rpb_mwt_conv3", _p(x), _p(wp), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), _stream(), label="mwt_conv3",
-                  nbytes=4 * x.numel() * (3 if acc else 2), flops=2 * x.numel() * (27 * 36 + 36))
+                  nbytes=nbytes, flops=flops)
         return out
 
     @staticmethod
@@ -375,9 +421,9 @@ class MWT3d(Model):
             d, x = self.k_decompose(x, p["ec_d"], p["ec_s"])
             plan = self._plan(d.shape[1], d.shape[2], d.device)
             ud = self.k_spectral(d, plan, p["Wt"], p["loT"], p["lb"])
-            self.k_conv3(x, p["B"], out=ud)
+            self.k_conv3(x, p["B"], out=ud, arith=self.arith)
             Ud.append(ud)
-            Us.append(self.k_conv3(d, p["C"]))
+            Us.append(self.k_conv3(d, p["C"], arith=self.arith))
             if keep is not None:
                 keep.setdefault("d", []).append(d)
                 keep.setdefault("s", []).append(x)

@@ -2,7 +2,8 @@
 from HIP events (algorithmic bytes and FLOPs of each launch are the bookkeeping of model/mwt.py).  Launches under ~100 us are dominated
 by the event overhead in this table: take those from `rocprofv3 --kernel-trace --stats -- python tools/mwt_probe.py
 --no-events` instead.
-    python tools/mwt_probe.py [--batches 1 8 32] [--runs 20] [--no-events] [--out profiles/mwt_probe.txt]"""
+``--arith`` selects MWT3d.set_arith (f32 = the default path; bf16x3 / f16x2 = the split-operand convolutions).
+    python tools/mwt_probe.py [--arith f32|bf16x3|f16x2] [--batches 1 8 32] [--runs 20] [--no-events] [--out profiles/mwt_probe.txt]"""
 import argparse
 import os
 import statistics
@@ -37,13 +38,15 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--no-events", action="store_true")
+    ap.add_argument("--arith", default="f32", choices=["f32", "bf16x3", "f16x2"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/mwt_probe.py measures on an MI355X: no GPU, no number")
     torch.manual_seed(0)
     m = MWT3d(k=3, alpha=5, c=4, nCZ=4, L=0, base="legendre", shape_in=SHAPE, shape_out=SHAPE).to("cuda:0").eval()
-    lines = []
+    m.set_arith(a.arith)
+    lines = [f"arith = {a.arith}"]
     sustained = sustained_bf16()
     fl_rate = lambda v: v["flops"] * v["calls"] / (v["total_ms"] * 1e-3) / 1e12
     lines.append(f"sustained bf16 MFMA rate of this chip (rpb_mfma_probe, random operands): {sustained:.0f} TFLOP/s")
@@ -80,16 +83,29 @@ def main():
         for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"]):
             by, fl, t = v["bytes"] * v["calls"], v["flops"] * v["calls"], v["total_ms"] * 1e-3
             lines.append(f"  {k:<16}{v['calls']:>6}{v['total_ms']:>10.3f}{by / 1e9:>9.3f}{by / t / HBM_PEAK:>11.3f}{fl / t / 1e12:>9.2f}")
-        if "mwt_conv3" in summ:
-            v = summ["mwt_conv3"]
-            # one v_mfma_f32_16x16x4_f32 = 16 * 16 * 4 * 2 FLOP on the 48-row padded tile; issued per 64 cells: 27 * 9 * 12 + 12 * 12
+        fam = {k: v for k, v in summ.items() if k.startswith("mwt_conv3") or k == "mwt_amax_exp"}
+        if fam:
+            lines.append(f"  mwt_conv3 family ({' + '.join(sorted(fam))}): {sum(v['total_ms'] for v in fam.values()):.3f} ms")
+        label = "mwt_conv3" if a.arith == "f32" else f"mwt_conv3[{a.arith}]"
+        if label in summ:
+            v = summ[label]
             cells = v["flops"] * v["calls"] / (2 * (27 * 36 + 36) * 36)
-            mf = cells / 64 * (27 * 9 * 12 + 12 * 12)
-            issued = mf * 2048 / (v["total_ms"] * 1e-3) / 1e12
-            lines.append(f"  mwt_conv3: {mf:.3e} MFMA (16x16x4 f32) = {issued:.1f} TFLOP/s issued = {issued / (sustained / 16):.2f} of the fp32 "
-                         f"MFMA ceiling (sustained bf16 rate {sustained:.0f} TFLOP/s measured here with random operands, / 16); useful rows "
-                         f"36/48.  fp32-grade FLOP/s delivered {fl_rate(v):.1f} TFLOP/s; conv3x's split-bf16 (3 products per fp32-grade product) "
-                         f"at its documented 0.75-0.86 of the sustained rate delivers {0.75 * sustained / 3:.0f}-{0.86 * sustained / 3:.0f}")
+            # per 64 cells (12 tiles of the 48-row padded output); Lo is 12 * 12 v_mfma_f32_16x16x4_f32 in every mode
+            lo_mf, lo_fl = cells / 64 * 12 * 12, 16 * 16 * 4 * 2
+            if a.arith == "f32":
+                # one v_mfma_f32_16x16x4_f32 = 16 * 16 * 4 * 2 FLOP; 27 taps x 9 steps
+                mf, per, name, ceil_, what = cells / 64 * 27 * 9 * 12, 2048, "16x16x4 f32", sustained / 16, "fp32 MFMA ceiling (sustained bf16 rate / 16)"
+            else:
+                # one v_mfma_f32_16x16x32_{bf16,f16} = 16 * 16 * 32 * 2 FLOP; 31 steps of the flat K = 992, 6 or 3 products each
+                prod = 6 if a.arith == "bf16x3" else 3
+                mf, per, name, ceil_, what = (cells / 64 * 31 * 12 * prod, 16384, "16x16x32 bf16" if prod == 6 else "16x16x32 f16", sustained,
+                                              "sustained bf16 rate")
+            issued = (mf * per + lo_mf * lo_fl) / (v["total_ms"] * 1e-3) / 1e12
+            lines.append(f"  {label}: {mf:.3e} MFMA ({name}) + {lo_mf:.3e} (16x16x4 f32, Lo) = {issued:.1f} TFLOP/s issued; the main product alone "
+                         f"= {mf * per / (v['total_ms'] * 1e-3) / 1e12 / ceil_:.2f} of the {what} ({sustained:.0f} TFLOP/s measured here with random "
+                         f"operands); useful rows 36/48.  fp32-grade FLOP/s delivered {fl_rate(v):.1f} TFLOP/s; conv3x's split-bf16 (3 products per "
+                         f"fp32-grade product) at its documented 0.75-0.86 of the sustained rate delivers {0.75 * sustained / 3:.0f}-"
+                         f"{0.86 * sustained / 3:.0f}")
     txt = "\n".join(lines)
     print(txt)
     if a.out:
