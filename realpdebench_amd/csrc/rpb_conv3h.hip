@@ -11,6 +11,11 @@
 // Layout and tiling are those of conv3x_kernel: a workgroup owns 128 consecutive tokens, stages the 130 rows of each (kt, kh) and
 // 64-channel chunk in LDS (two planes: 2 x 33 KB per stage buffer instead of 2 x 50 KB), the w boundary is applied to the A operand,
 // weights are pre-arranged in MFMA B-operand order Wz[tap][Ci/16][2 planes][N/32][64 lanes][8] fp16.
+// The kernel stays a second text next to conv3x_kernel on purpose.  One body for both plane schemes was tried two ways with hipcc 7.2
+// (profiles/conv3_fwd_unify.txt): as a forced-inline __device__ template it is optimised on its own before it is inlined, without
+// the kernel's launch bounds, and every instance came out differently (other loop duplication, 1.5x the v_accvgpr moves); as one
+// text included into both kernels the bf16x3 instances kept their code and speed, but conv3x_f16x2_kernel<1> went from
+// 368 VGPRs + 128 AGPRs to 496 + 256 and from 1.85 to 2.15 ms at the U-Net 64 -> 64 shape.  Outputs were bit-equal in both forms.
 #include "rpb_mma.h"
 #include <stdlib.h>
 

@@ -73,7 +73,8 @@ def _conv_case(ops, B, mesh, Ci, Co, xs=1.0, ws=None, seed=0):
 
 
 @pytest.mark.parametrize("B,mesh,Ci,Co", [(2, (3, 5, 7), 64, 64), (1, (4, 6, 40), 128, 128), (1, (2, 9, 33), 64, 256),
-                                          (1, (5, 4, 13), 192, 512), (3, (2, 2, 2), 64, 64), (1, (3, 6, 20), 256, 512)])
+                                          (1, (5, 4, 13), 192, 512), (3, (2, 2, 2), 64, 64), (1, (3, 6, 20), 256, 512),
+                                          (1, (3, 4, 11), 128, 64), (1, (2, 5, 9), 64, 128)])
 def test_conv3x_f16x2_forward_vs_fp64(ops, B, mesh, Ci, Co):
     M, x, w, bias = _conv_case(ops, B, mesh, Ci, Co)
     assert ops.conv3_split_ok(Co, Ci)

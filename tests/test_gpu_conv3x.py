@@ -43,7 +43,8 @@ def test_split3_reconstructs_every_significand_bit(ops):
 
 
 @pytest.mark.parametrize("B,mesh,Ci,Co", [(2, (3, 5, 7), 64, 64), (1, (4, 6, 40), 128, 128), (1, (2, 9, 33), 64, 256),
-                                          (1, (5, 4, 13), 192, 512), (3, (2, 2, 2), 64, 64)])
+                                          (1, (5, 4, 13), 192, 512), (3, (2, 2, 2), 64, 64), (1, (3, 4, 11), 128, 64),
+                                          (1, (2, 5, 9), 64, 128)])
 def test_conv3x_forward_vs_fp64(ops, B, mesh, Ci, Co):
     T, H, W = mesh
     M = B * T * H * W
