@@ -199,6 +199,14 @@ __global__ void gn_tokens_fwd_kernel(const float* __restrict__ x, const float* _
     }
 }
 
+// gh = gy * gamma as ONE rounded fp32 product in both passes: contracted into the subtraction of the second pass it would be the
+// unrounded product there and the rounded one under the group mean, and rstd (up to eps^-1/2 = 316 for a constant group) multiplies the
+// difference -- a group whose deviations cancel (one element: gx = gadd exactly) then got rstd * 2^-24 |gh| instead of 0
+__device__ __forceinline__ float gn_gh(float gyv, float ga) {
+#pragma clang fp contract(off)
+    return gyv * ga;
+}
+
 // gx = rstd * (gh - mean_g(gh) - xhat mean_g(gh xhat)) (+ gadd), gh = gy * gamma;  pg[b][c] = sum_p gy xhat, pb[b][c] = sum_p gy
 __global__ void gn_tokens_bwd_kernel(const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ gamma,
                                      const float* __restrict__ stat, const float* __restrict__ gy, const float* __restrict__ gadd,
@@ -222,7 +230,7 @@ __global__ void gn_tokens_bwd_kernel(const float* __restrict__ x, const float* _
             if (x2) v += x2[base + (long)p * C];
             const float xh = (v - mu) * rstd;
             const float gyv = gy[base + (long)p * C];
-            const float gh = gyv * ga;
+            const float gh = gn_gh(gyv, ga);
             s1 += (double)gh;
             s2 += (double)gh * (double)xh;
             dg += gyv * xh;
@@ -251,7 +259,7 @@ __global__ void gn_tokens_bwd_kernel(const float* __restrict__ x, const float* _
             float v = x[base + (long)p * C];
             if (x2) v += x2[base + (long)p * C];
             const float xh = (v - mu) * rstd;
-            const float gh = gy[base + (long)p * C] * ga;
+            const float gh = gn_gh(gy[base + (long)p * C], ga);
             float o = rstd * (gh - m1 - xh * m2);
             if (gadd) o += gadd[base + (long)p * C];
             gx[base + (long)p * C] = o;
