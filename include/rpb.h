@@ -707,6 +707,26 @@ int rpb_mwt_conv3x(const float* x, const void* wpx, const float* cb48, const flo
 int rpb_mwt_head(const float* x, const float* w0t, const float* b0, const float* w1, const float* b1, float* out, int B, int Nx, int Ny,
                  int T, int Cout, int r, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * DeepONet (realpdebench/model/deeponet.py) -- evaluation forward (additions do not change RPB_ABI_VERSION).  The branch CNN's
+ * convolutions and Linear layers are rpb_im2col / rpb_gemm3x / rpb_split3 / rpb_conv3x; DESIGN.md section 16.
+ *     eval BatchNorm + ReLU + pooling on channels-last rows: x [B][T][H][W][ldx], channels 0..C-1 live; y = relu(x * sc[c] + sh[c])
+ *     (sc = gamma / sqrt(running_var + eps), sh = beta - running_mean * sc).  mode 0: MaxPool3d(2), floor -> out [B][T/2][H/2][W/2][ldo];
+ *     mode 1: AdaptiveAvgPool3d((1, 4, 4)), bins [floor(i In / Out), ceil((i + 1) In / Out)) -> out [B][4][4][ldo].  Output channels
+ *     C..ldo-1 are written as zeros.  C, ldx, ldo multiples of 4. */
+int rpb_don_bn_relu_pool(const float* x, const float* sc, const float* sh, float* out, int B, int T, int H, int W, int C, int ldx,
+                         int ldo, int mode, void* stream);
+/*     trunk MLP over the N = T H W grid points (gt [T], gh [H], gw [W]: the axes' coordinates): Linear(3, 64) ReLU Linear(64, 128) ReLU
+ *     Linear(128, p), weights TRANSPOSED (w1t [3][64], w2t [64][128], w3t [128][p]) -> t [N][p].  p in {64, 128, 256}. */
+int rpb_don_trunk(const float* gt, const float* gh, const float* gw, const float* w1t, const float* b1, const float* w2t,
+                  const float* b2, const float* w3t, const float* b3, float* t, int T, int H, int W, int p, void* stream);
+/*     output net per (sample, point) in one launch: out [B][N][Cout] = W3 relu(W2 relu(W1 (b[b] (.) t[n]) + b1) + b2) + b3 on the bf16
+ *     MFMA from three-plane split operands (six products, fp32 grade); the 512- and 128-wide activations stay in registers.  t [N][p],
+ *     b [B][p]; w1z / w2z / w3z: the weights as bf16 planes in MFMA lane order and b1z / b2z: the biases in accumulator-register order
+ *     (model/deeponet.py point_weights); b3 [Cout].  p in {64, 128, 256}, Cout <= 16, any N > 0 (the tail tile is masked).  No atomics. */
+int rpb_don_point_mlp(const float* t, const float* b, const void* w1z, const float* b1z, const void* w2z, const float* b2z,
+                      const void* w3z, const float* b3, float* out, int B, long N, int p, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,9 @@ SIGNATURES = {
     "rpb_mwt_conv3x_wprep": (_I, "pp" + "i" + "p" + "p"),
     "rpb_mwt_conv3x": (_I, "pppppp" + "iiiii" + "i" + "pp" + "p"),
     "rpb_mwt_head": (_I, "pppppp" + "iiiiii" + "p"),
+    "rpb_don_bn_relu_pool": (_I, "pppp" + "iiiiiiii" + "p"),
+    "rpb_don_trunk": (_I, "pppppppppp" + "iiii" + "p"),
+    "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),
 }
 
 _lib = None

@@ -53,7 +53,11 @@ def load_model(train_dataset, device="cpu", **kwargs):
         kwargs["shape_out"] = output_shape
         kwargs.pop("config", None)
         model = MWT3d(**kwargs).to(device)
+    elif model_name == "deeponet":
+        from .deeponet import DeepONet
+        model = DeepONet(shape_in=input_shape, shape_out=output_shape, input_channels=input_shape[-1],       # load_model.py:132-143
+                         output_channels=output_shape[-1], p=kwargs["p"], dropout_rate=kwargs["dropout_rate"], device=device).to(device)
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
-                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt)")
+                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet)")
     return model
