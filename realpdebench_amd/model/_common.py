@@ -1,0 +1,144 @@
+"""Plumbing the models share between their parameter trees and the C ABI: the autograd glue (``HipFunction``), the weight-gradient
+finish (``wgrad``, ``colsum``, ``sum_rows``), the cache of kernel-side layouts (``LayoutCache``) and the base of the models whose
+training step is not built (``EvalOnly``)."""
+import torch
+
+from .. import ops
+
+# checkpoint key -> meta-data key handed back to the caller (train.py:299-301 uses the returned dict)
+META_KEYS = {
+    "train_losses": "all_train_losses",
+    "val_losses": "all_val_losses",
+    "iteration": "iteration",
+    "best_iteration": "best_iteration",
+    "best_val_loss": "best_val_loss",
+}
+
+
+class HipFunction(torch.autograd.Function):
+    """Autograd glue of every ``nn.Parameter`` model: one forward / backward call into its HIP pipelines.
+
+    The model provides ``_new_state()`` (what the forward records into: a dict, U-Net's tape), ``_forward_hip(x, state)`` and
+    ``_backward_hip(state, g_out, need_gx=...) -> {parameter: gradient}``, with the input gradient under ``"__x__"`` where the model
+    computes one (DPOT's sliding windows)."""
+
+    @staticmethod
+    def forward(ctx, x, model, *params):
+        state = model._new_state()
+        out = model._forward_hip(x, state)
+        ctx.model, ctx.state, ctx.params = model, state, params
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        grads = ctx.model._backward_hip(ctx.state, g_out.contiguous().float(), need_gx=ctx.needs_input_grad[0])
+        ctx.state = None               # the saved activations go now, not when autograd drops the graph
+        return (grads.get("__x__"), None) + tuple(grads.get(p) for p in ctx.params)
+
+
+def wgrad(G, A, M, N, K, ldg=None, lda=None, conv=None, conv_mode=1, one_reduction=False):
+    """(dW [N,K], db [N]) = (G^T A(im2col), colsum G): TN GEMM (``ops.conv3_wgrad_parts`` for the 3x3x3 convolution) into split-token
+    partials, then the fp64 reduction.  ``one_reduction``: a single launch over ``[dW | db]`` whose results are views of one buffer and
+    which may wait for the end of a ``deferred_reductions`` block; otherwise two launches into separate tensors.  The reduction kernel
+    is chosen by row length and the two kernels add rows in a different order, so the forms differ in the low bits of ``db``: a call
+    site keeps the form it has."""
+    dev = (G.t if isinstance(G, ops.Sub) else G).device
+    taps_rev = False
+    if conv is not None and conv_mode == 1:
+        part, taps_rev = ops.conv3_wgrad_parts(G, A, M, N, K // 27, conv, ldg=ldg, ldx=lda)
+    else:
+        part = torch.empty(ops.gemm_tn_splits(M, N, K, conv is not None, conv_mode, ldg=ldg, lda=lda), N * K + N, device=dev,
+                           dtype=torch.float32)
+        ops.gemm_tn(G, A, part, M, N, K, ldg=ldg, lda=lda, conv=conv, conv_mode=conv_mode)
+    splits, L = part.shape
+    if one_reduction:
+        tot = torch.empty(L, device=dev, dtype=torch.float32)
+        ops.reduce_partials(part, splits, L, out_f32=tot, deferrable=not taps_rev)       # (the tap restore below reads dW at once)
+        dW, db = tot[:N * K].view(N, K), tot[N * K:]
+    else:
+        dW, db = torch.empty(N, K, device=dev, dtype=torch.float32), torch.empty(N, device=dev, dtype=torch.float32)
+        ops.reduce_partials(part, splits, N * K, out_f32=dW.view(-1), row_stride=L)
+        ops.reduce_partials(part, splits, N, out_f32=db, row_stride=L, col0=N * K)
+    if taps_rev:
+        dW = ops.conv3_taps_restore(dW, N, K // 27)
+    return dW, db
+
+
+def sum_rows(part, rows, L, f64=False, deferrable=False):
+    """sum_r part[r][:L] in fp64, returned as fp32 (or as the fp64 sums themselves)."""
+    out = torch.empty(L, device=part.device, dtype=torch.float64 if f64 else torch.float32)
+    ops.reduce_partials(part, rows, L, out_f64=out if f64 else None, out_f32=None if f64 else out, deferrable=deferrable)
+    return out
+
+
+def colsum(x, M, N, deferrable=False):
+    """Column sums of x [M][N] (bias gradients) in column chunks the reduction kernel takes (a power of two <= 1024)."""
+    rows = ops.colsum_rows()
+    chunk = 1024
+    while N % chunk:
+        chunk //= 2
+    out = torch.empty(N, device=x.device, dtype=torch.float32)
+    for c0 in range(0, N, chunk):
+        part = torch.empty(rows, chunk, device=x.device, dtype=torch.float32)      # one per chunk: the reduction may be deferred
+        ops.colsum(ops.Sub(x, c0), part, M, chunk, ld=N)
+        ops.reduce_partials(part, rows, chunk, out_f32=ops.Sub(out, c0), deferrable=deferrable)
+    return out
+
+
+class LayoutCache:
+    """Kernel-side layouts derived from parameters and buffers (re-laid-out, concatenated or split weights), one entry per key.
+
+    An entry is served only while every source tensor still has the address, in-place version and device it was built from, the
+    caller's ``extra`` key is the same, and ``invalidate()`` has not been called since.  ``_version`` alone is not enough:
+    ``p.data = other`` rebinds a parameter without touching it.  The entry therefore holds the (detached) tensors it was built from,
+    so that their storage cannot be freed and handed to a new tensor that would stamp the same.  Kernels that write weights through
+    raw pointers report it with ``torch.autograd.graph.increment_version`` (``trainer.ArenaTrainer.step``)."""
+
+    def __init__(self):
+        self._entries, self._token = {}, 0
+
+    def invalidate(self):
+        """``Model`` calls this from ``load_state_dict`` and ``_apply`` (``.to``, ``.float`` ...)."""
+        self._token += 1
+
+    def get(self, key, sources, build, extra=None):
+        """``build()``'s value for ``key``; ``sources``: the tensors it reads."""
+        sources = tuple(sources)
+        stamp = (self._token, extra, tuple((t.data_ptr(), t._version, t.device) for t in sources))
+        hit = self._entries.get(key)
+        if hit is None or hit[0] != stamp:
+            hit = self._entries[key] = (stamp, build(), tuple(t.detach() for t in sources))
+        return hit[1]
+
+
+class EvalOnly:
+    """Mixin in front of ``Model`` for the models whose training step is not built (MWT3d, DeepONet): evaluation forward,
+    ``train_loss`` as a value, rollout and checkpoint I/O.  Every attempt to backpropagate raises ``NotImplementedError`` with
+    ``training_unavailable`` instead of returning tensors without a graph; ``trainer.make_trainer`` refuses at construction."""
+    TRAIN_MSG = ("the {} training step is not built yet: {} on MI355X covers the evaluation forward, train_loss as a value under "
+                 "torch.no_grad(), the rollout and checkpoint I/O")
+    training_unavailable = None        # subclasses: TRAIN_MSG.format(family, class name)
+
+    def _require_eval(self, x):
+        """First thing in ``forward``: never hand back a tensor that silently carries no graph.  Under grad mode anything that asks for
+        a gradient is refused (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with
+        requires_grad off)."""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(self.training_unavailable)
+
+    def _require_hip(self, x):
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} runs on MI355X only: there is no CPU fallback (move the model and its input to "
+                               "'cuda')")
+
+    def train_loss(self, input, target):
+        """Elementwise MSE (the reference's ``mse_loss(pred, target)``), as a value: under grad mode it raises."""
+        if torch.is_grad_enabled():
+            raise NotImplementedError(self.training_unavailable)
+        return super().train_loss(input, target)
+
+    @staticmethod
+    def _bookkeeping(book):
+        """The meta data of a checkpoint dict; a bare weights file (``book = {}``) gives the entries of an untrained run."""
+        blank = {"train_losses": [], "val_losses": {}, "iteration": 0, "best_iteration": 0, "best_val_loss": float("inf")}
+        return {meta: book.get(key, blank[key]) for key, meta in META_KEYS.items()}

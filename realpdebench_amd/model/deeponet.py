@@ -2,7 +2,7 @@
 ``load_model`` like model/load_model.py:132-143) for the reference's ``configs/*/deeponet.yaml`` (p = 64 / 128 / 256).
 
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training step is not built: every
-attempt to backpropagate raises ``NotImplementedError`` (``DEEPONET_TRAIN_MSG``) instead of returning tensors without a graph, and
+attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph, and
 ``trainer.make_trainer`` refuses the model at construction.  Dropout is the identity and BatchNorm3d uses its running statistics in
 every mode (no batch-statistics path exists).
 
@@ -26,23 +26,13 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .model import _META_KEYS, Model
+from ..ops import _p, _stream
+from ._common import EvalOnly
+from .model import Model
 
-DEEPONET_TRAIN_MSG = ("the DeepONet training step is not built yet: DeepONet on MI355X covers the evaluation forward, train_loss as a "
-                      "value under torch.no_grad(), the rollout and checkpoint I/O")
+I16 = torch.int16
 P_SUPPORTED = (64, 128, 256)
 _COL_FLOATS = 1 << 28          # stage-1 im2col buffer bound (1 GiB): larger batches run the first stage in chunks of samples
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    if not t.is_cuda:
-        raise _lib.RpbError("realpdebench_amd ops need tensors on a HIP device (no CPU fallback exists)")
-    assert t.is_contiguous() and t.dtype in (torch.float32, torch.int16)
-    return t.data_ptr()
 
 
 # ----------------------------------------------------------------------------------------------------------- layouts (plain torch)
@@ -115,16 +105,9 @@ class _Trunk(nn.Module):
         self.fc = nn.Sequential(nn.Linear(3, 64), nn.ReLU(), nn.Linear(64, 128), nn.ReLU(), nn.Linear(128, p))
 
 
-def _stamp(tensors):
-    """(address, in-place version) per tensor.  The caches also keep the tensors they were built from alive (``held``), so a parameter
-    rebound to a fresh tensor (``p.data = new``) cannot land on a stamped address, and DeepONet adds a token that ``load_state_dict``
-    and ``_apply`` (``.to``, ``.float`` ...) bump."""
-    return tuple((t.data_ptr(), t._version) for t in tensors)
-
-
-class DeepONet(Model):
+class DeepONet(EvalOnly, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
-    training_unavailable = DEEPONET_TRAIN_MSG       # trainer.make_trainer refuses at construction
+    training_unavailable = EvalOnly.TRAIN_MSG.format("DeepONet", "DeepONet")
 
     def __init__(self, shape_in, shape_out, input_channels, output_channels, p, dropout_rate=0.1, device="cuda"):
         super().__init__()
@@ -147,16 +130,6 @@ class DeepONet(Model):
         self.trunk = _Trunk(self.p)
         self.output_net = nn.Sequential(nn.Linear(self.p, 512), nn.ReLU(), nn.Dropout(dropout_rate), nn.Linear(512, 128), nn.ReLU(),
                                         nn.Dropout(dropout_rate), nn.Linear(128, self.output_channels))
-        self._prepped, self._t, self._token = None, None, 0
-
-    # ------------------------------------------------------------------ cache invalidation
-    def _apply(self, fn, *args, **kwargs):
-        self._token = getattr(self, "_token", 0) + 1
-        return super()._apply(fn, *args, **kwargs)
-
-    def load_state_dict(self, *args, **kwargs):
-        self._token += 1
-        return super().load_state_dict(*args, **kwargs)
 
     # ------------------------------------------------------------------ checkpoints
     def load_checkpoint(self, checkpoint_path, device="cpu"):
@@ -167,17 +140,16 @@ class DeepONet(Model):
             meta = super().load_checkpoint(checkpoint_path, "cpu")
         else:
             self.load_state_dict(ck)
-            blank = {"train_losses": [], "val_losses": {}, "iteration": 0, "best_iteration": 0, "best_val_loss": float("inf")}
-            meta = {m: blank[k] for k, m in _META_KEYS.items()}
+            meta = self._bookkeeping({})
         self.to(device)
         return meta
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _prep(self, device):
         tensors = list(self.branch.parameters()) + list(self.branch.buffers()) + list(self.output_net.parameters())
-        stamp = (str(device), self._token) + _stamp(tensors)
-        if self._prepped is not None and self._prepped[0] == stamp:
-            return self._prepped[1]
+        return self._layouts.get("prep", tensors, lambda: self._build_prep(device))
+
+    def _build_prep(self, device):
         f = dict(device=device, dtype=torch.float32)
         prep = {}
         for i in range(4):
@@ -199,7 +171,7 @@ class DeepONet(Model):
                 wm[:Co, :, :Ci] = wt.reshape(Co, 27, Ci)
                 wm = wm.reshape(N, 27 * K)
                 wz = torch.empty(3 * N * 27 * K, device=device, dtype=torch.int16)
-                _lib.call("rpb_conv3x_wprep", _p(wm), _p(wz), N, K, _stream(), label="conv3x_wprep", nbytes=10 * N * 27 * K)
+                _lib.call("rpb_conv3x_wprep", _p(wm), _p(wz, I16), N, K, _stream(), label="conv3x_wprep", nbytes=10 * N * 27 * K)
             sc64 = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
             sh64 = bn.bias.detach().double() - bn.running_mean.detach().double() * sc64
             prep[f"s{i + 1}"] = dict(wz=wz, bias=bias, N=N, K=K, C=Co, sc=sc64.float().contiguous(), sh=sh64.float().contiguous())
@@ -209,33 +181,32 @@ class DeepONet(Model):
         prep["fc3"] = (self.k_gemm_wprep(fc3.weight.detach().contiguous()), fc3.bias.detach().contiguous())
         o = self.output_net
         prep["point"] = point_weights(*(t.detach() for t in (o[0].weight, o[0].bias, o[3].weight, o[3].bias, o[6].weight, o[6].bias)))
-        self._prepped = (stamp, prep, [t.detach() for t in tensors])       # held: see _stamp
         return prep
 
     def _trunk(self, T, H, W, device):
         """t [N][p] of the (T, H, W) grid.  ONE grid is kept (84 MB at the cylinder shape): it is recomputed when the grid, the device or a
         trunk weight changed."""
-        stamp = (T, H, W, str(device), self._token) + _stamp(self.trunk.parameters())
-        if self._t is None or self._t[0] != stamp:
+        def build():
             fc = self.trunk.fc
             wt = [fc[i].weight.detach().t().contiguous() for i in (0, 2, 4)]
             bs = [fc[i].bias.detach().contiguous() for i in (0, 2, 4)]
-            self._t = (stamp, self.k_trunk(T, H, W, wt, bs, device), [q.detach() for q in self.trunk.parameters()])       # held: see _stamp
-        return self._t[1]
+            return self.k_trunk(T, H, W, wt, bs, device)
+
+        return self._layouts.get("trunk", self.trunk.parameters(), build, extra=(T, H, W))
 
     # ------------------------------------------------------------------ the kernels, one method per family (tests call these)
     @staticmethod
     def k_gemm_wprep(w):
         N, K = w.shape
         wz = torch.empty(3 * N * K, device=w.device, dtype=torch.int16)
-        _lib.call("rpb_gemm3x_wprep", _p(w), _p(wz), N, K, _stream(), label="gemm3x_wprep", nbytes=10 * N * K)
+        _lib.call("rpb_gemm3x_wprep", _p(w), _p(wz, I16), N, K, _stream(), label="gemm3x_wprep", nbytes=10 * N * K)
         return wz
 
     @staticmethod
     def k_gemm(a, wz, bias, N, relu):
         M, K = a.shape
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-        _lib.call("rpb_gemm3x", _p(a), _p(wz), _p(bias), None, None, _p(out), M, N, K, K, N, 3 if relu else 0, None, None, None, 0, 0.0,
+        _lib.call("rpb_gemm3x", _p(a), _p(wz, I16), _p(bias), None, None, _p(out), M, N, K, K, N, 3 if relu else 0, None, None, None, 0, 0.0,
                   _stream(), label=f"don_gemm3x[N{N},K{K}]", nbytes=4 * (M * K + M * N) + 6 * N * K, flops=2 * M * N * K)
         return out
 
@@ -254,9 +225,9 @@ class DeepONet(Model):
         M, Ci = x.shape
         N = s["N"]
         planes = torch.empty(3 * M * Ci, device=x.device, dtype=torch.int16)
-        _lib.call("rpb_split3", _p(x), _p(planes), M, Ci, Ci, _stream(), label="don_split3", nbytes=10 * M * Ci)
+        _lib.call("rpb_split3", _p(x), _p(planes, I16), M, Ci, Ci, _stream(), label="don_split3", nbytes=10 * M * Ci)
         out = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _lib.call("rpb_conv3x", _p(planes), _p(s["wz"]), _p(s["bias"]), _p(out), M, N, Ci, N, *mesh, _stream(),
+        _lib.call("rpb_conv3x", _p(planes, I16), _p(s["wz"], I16), _p(s["bias"]), _p(out), M, N, Ci, N, *mesh, _stream(),
                   label=f"don_conv3x[N{N},Ci{Ci}]", nbytes=6 * M * Ci + 4 * M * N, flops=2 * M * N * 27 * Ci)
         return out
 
@@ -285,7 +256,7 @@ class DeepONet(Model):
         N, p = t.shape
         B, Cout = b.shape[0], b3.shape[0]
         out = torch.empty(B, N, Cout, device=t.device, dtype=torch.float32)
-        _lib.call("rpb_don_point_mlp", _p(t), _p(b), _p(w1z), _p(b1z), _p(w2z), _p(b2z), _p(w3z), _p(b3), _p(out), B, N, p, Cout, _stream(),
+        _lib.call("rpb_don_point_mlp", _p(t), _p(b), _p(w1z, I16), _p(b1z), _p(w2z, I16), _p(b2z), _p(w3z, I16), _p(b3), _p(out), B, N, p, Cout, _stream(),
                   label="don_point_mlp", nbytes=4 * (B * N * Cout + N * p + B * p) + 6 * (512 * p + 128 * 512 + 32 * 128),
                   flops=2 * B * N * (p * 512 + 512 * 128 + 128 * Cout))
         return out
@@ -315,12 +286,8 @@ class DeepONet(Model):
         return self.k_gemm(z, *prep["fc3"], self.p, relu=False)
 
     def forward(self, x):
-        # never hand back a tensor that silently carries no graph: under grad mode anything that asks for a gradient is refused
-        # (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with requires_grad off)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(DEEPONET_TRAIN_MSG)
-        if not x.is_cuda:
-            raise RuntimeError("DeepONet runs on MI355X only: there is no CPU fallback (move the model and its input to 'cuda')")
+        self._require_eval(x)
+        self._require_hip(x)
         if x.dim() != 5 or x.shape[1] != self.shape_in[0] or x.shape[-1] != self.input_channels:
             raise ValueError(f"DeepONet was built for inputs [B, {self.shape_in[0]}, H, W, {self.input_channels}], got {tuple(x.shape)}")
         if min(pooled_extents(*x.shape[1:4])[3]) < 1:
@@ -333,10 +300,3 @@ class DeepONet(Model):
             b = self.branch_forward(x, prep)
             t = self._trunk(T_out, H, W, x.device)
             return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
-
-    def train_loss(self, input, target):
-        """Elementwise MSE (the reference's ``mse_loss(pred, target)``), as a value: under grad mode it raises, see the module docstring."""
-        if torch.is_grad_enabled():
-            raise NotImplementedError(DEEPONET_TRAIN_MSG)
-        pred = self.forward(input)
-        return (pred - target) ** 2

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .galerkin_transformer import _wgrad
+from ._common import HipFunction, colsum, sum_rows, wgrad
 from .model import Model as _ModelBase
 
 
@@ -438,7 +438,7 @@ class DPOT(_ModelBase):
         gU = new(Mt, NU)
         ops.gemm_nt(gV, Tr(ol2.weight.data.view(OD, OD)), gU, Mp, OD, OD, act=2, aux=sv["Upre"])
         del gV
-        dWt, dbt = _wgrad(gU, sv["Xlast"], Mt, NU, E)
+        dWt, dbt = wgrad(gU, sv["Xlast"], Mt, NU, E, one_reduction=True)
         grads[ol0.weight] = dWt.view(ps, ps, OD, E).permute(3, 2, 0, 1).contiguous()
         grads[ol0.bias] = dbt.view(ps * ps, OD).sum(0)
         g = new(Mt, E)
@@ -455,11 +455,11 @@ class DPOT(_ModelBase):
         with defer:
             for blk, tp in zip(reversed(list(net.blocks)), reversed(sv["tapes"])):
                 fl, m0, m2 = blk.filter, blk.mlp[0], blk.mlp[2]
-                dWm2, dbm2 = _wgrad(g, tp["Hh"], Mt, E, hid)
+                dWm2, dbm2 = wgrad(g, tp["Hh"], Mt, E, hid, one_reduction=True)
                 grads[m2.weight], grads[m2.bias] = dWm2.reshape(m2.weight.shape), dbm2
                 gH = new(Mt, hid)
                 ops.gemm_nt(g, Tr(m2.weight.data.view(E, hid)), gH, Mt, hid, E, act=2, aux=tp["Hpre"])
-                dWm0, dbm0 = _wgrad(gH, tp["Y2"], Mt, hid, E)
+                dWm0, dbm0 = wgrad(gH, tp["Y2"], Mt, hid, E, one_reduction=True)
                 grads[m0.weight], grads[m0.bias] = dWm0.reshape(m0.weight.shape), dbm0
                 gY2 = new(Mt, E)
                 ops.gemm_nt(gH, Tr(m0.weight.data.view(hid, E)), gY2, Mt, E, hid)
@@ -467,7 +467,8 @@ class DPOT(_ModelBase):
                 pg, pb = new(B, E), new(B, E)
                 gz = new(Mt, E)
                 ops.gn_tokens_bwd(tp["Fo"], tp["Y1"], blk.norm2.weight.data, tp["st2"], gY2, None, gz, pg, pb, B, n * n, E, 8)
-                grads[blk.norm2.weight], grads[blk.norm2.bias] = self._sum_rows(pg, B, E), self._sum_rows(pb, B, E)
+                grads[blk.norm2.weight] = sum_rows(pg, B, E, deferrable=True)
+                grads[blk.norm2.bias] = sum_rows(pb, B, E, deferrable=True)
                 # AFNO: z = irfft2(mlp_c(rfft2(y1))) + y1
                 gO2 = new(ntok, 2 * E)
                 self._irfft2(gO2, A1, gz, B, pl, E, fwd=False)
@@ -480,15 +481,16 @@ class DPOT(_ModelBase):
                 ops.afno_wgrad(tp["Hs"], gO2, wpart, dw2, ntok, nb, bs, True)
                 ops.afno_wgrad(tp["S"], gHs, wpart, dw1, ntok, nb, bs, False)
                 grads[fl.w2], grads[fl.w1] = dw2, dw1
-                grads[fl.b2] = self._colsum(gO2, ntok, 2 * E).view(fl.b2.shape)
-                grads[fl.b1] = self._colsum(gHs, ntok, 2 * E).view(fl.b1.shape)
+                grads[fl.b2] = colsum(gO2, ntok, 2 * E, deferrable=True).view(fl.b2.shape)
+                grads[fl.b1] = colsum(gHs, ntok, 2 * E, deferrable=True).view(fl.b1.shape)
                 gY1 = new(Mt, E)
                 self._rfft2(gY1, A1, gS, B, pl, E, fwd=False)
                 gY1 = ops.add(gY1, gz)
                 gX = new(Mt, E)
                 pg, pb = new(B, E), new(B, E)                  # (fresh partial rows: norm2's are still waiting for the grouped reduction)
                 ops.gn_tokens_bwd(tp["X"], None, blk.norm1.weight.data, tp["st1"], gY1, g, gX, pg, pb, B, n * n, E, 8)
-                grads[blk.norm1.weight], grads[blk.norm1.bias] = self._sum_rows(pg, B, E), self._sum_rows(pb, B, E)
+                grads[blk.norm1.weight] = sum_rows(pg, B, E, deferrable=True)
+                grads[blk.norm1.bias] = sum_rows(pb, B, E, deferrable=True)
                 g = gX
         # ---- TimeAggregator
         ta = net.time_agg_layer
@@ -506,14 +508,14 @@ class DPOT(_ModelBase):
         dposb = new(n * n, E)
         ops.gemm_nt(GP, Wsum, dposb, n * n, E, E)
         grads[net.pos_embed] = dposb.view(n, n, E).permute(2, 0, 1).unsqueeze(0).contiguous()
-        grads[pe2.bias] = self._colsum(dposb, n * n, E)
-        dWsum, _ = _wgrad(sv["posb"], GP, n * n, E, E)                      # [i][j]
-        dWcT, _ = _wgrad(g, Hb, Mt, E, KT, ldg=E, lda=KT)                   # [j][(t, k)]
+        grads[pe2.bias] = colsum(dposb, n * n, E, deferrable=True)
+        dWsum, _ = wgrad(sv["posb"], GP, n * n, E, E, one_reduction=True)          # [i][j]
+        dWcT, _ = wgrad(g, Hb, Mt, E, KT, ldg=E, lda=KT, one_reduction=True)       # [j][(t, k)]
         gH1 = new(M1, E1p)
         ops.gemm_nt(g, Tr(WcT), gH1, Mt, KT, E, act=2, aux=sv["H1pre"])      # d hidden pre-activation, rows [B n^2][T * 64]
         dWf = new(E, T * E)                                                 # [j][(t, i)] = sum_k dWcT[j][(t, k)] W2[i][k]: rows (j, t)
         ops.gemm_nt(dWcT, W2p, dWf, E * T, E, E1p)
-        dW2p, _ = _wgrad(sv["Wf"], dWcT, E * T, E, E1p, ldg=E, lda=E1p)     # [i][k] = sum_(j,t) Wf[(j,t)][i] dWcT[(j,t)][k]
+        dW2p, _ = wgrad(sv["Wf"], dWcT, E * T, E, E1p, ldg=E, lda=E1p, one_reduction=True)     # [i][k] = sum_(j,t) Wf[(j,t)][i] dWcT[(j,t)][k]
         dWb = dWf.view(E, T, E).permute(1, 2, 0).contiguous()               # parameter-sized re-layout to [(t, i)][j]
         ops.dpot_tagg_finish(dWb, ta.w.data, sv["gamma"], pl["tt"], dw, dgamma, T, E, dWsum=dWsum)
         del dWb, dWf
@@ -521,7 +523,7 @@ class DPOT(_ModelBase):
         grads[ta.w] = dw
         if self.time_agg == "exp_mlp":
             grads[ta.gamma] = dgamma.view(1, E)
-        dW1, db1 = _wgrad(gH1, sv["P"], M1, E1, Kp, ldg=E1p, lda=Kp)
+        dW1, db1 = wgrad(gH1, sv["P"], M1, E1, Kp, ldg=E1p, lda=Kp, one_reduction=True)
         grads[pe0.weight], grads[pe0.bias] = dW1.reshape(pe0.weight.shape), db1
         if need_gx:
             # gradient of the token rows, then the inverse of the patch gather (patches do not overlap) and of the input resize
@@ -545,7 +547,7 @@ class DPOT(_ModelBase):
         the FNO path (both operands read once in MFMA layout) instead of the split-token TN GEMM, which is launch-bound at these widths."""
         CI = CO if CI is None else CI
         if (CO, CI) not in ((32, 32), (64, 64), (128, 128), (128, 32), (128, 64), (64, 32)):      # instances of csrc/rpb_cell.hip
-            return _wgrad(G, A, M, CO, CI)
+            return wgrad(G, A, M, CO, CI, one_reduction=True)
         slots = ops.cell_wgrad_slots(M, CO, CI)
         part = torch.empty(slots, CO * CI + CO, device=G.device, dtype=torch.float32)
         ops.cell_wgrad(G, A, part, M, CO, CI)
@@ -553,35 +555,14 @@ class DPOT(_ModelBase):
         ops.reduce_partials(part, slots, CO * CI + CO, out_f32=tot, deferrable=True)
         return tot[:CO * CI].view(CO, CI), tot[CO * CI:]
 
-    @staticmethod
-    def _sum_rows(part, rows, L):
-        out = torch.empty(L, device=part.device, dtype=torch.float32)
-        ops.reduce_partials(part, rows, L, out_f32=out, deferrable=True)
-        return out
-
-    @staticmethod
-    def _colsum(x, M, N):
-        """Column sums of x [M][N] (bias gradients) in column chunks the reduction kernel takes (a power of two <= 1024)."""
-        rows = ops.colsum_rows()
-        chunk = 1024
-        while N % chunk:
-            chunk //= 2
-        out = torch.empty(N, device=x.device, dtype=torch.float32)
-        for c0 in range(0, N, chunk):
-            part = torch.empty(rows, chunk, device=x.device, dtype=torch.float32)      # one per chunk: the reduction may be deferred
-            ops.colsum(ops.Sub(x, c0), part, M, chunk, ld=N)
-            ops.reduce_partials(part, rows, chunk, out_f32=ops.Sub(out, c0), deferrable=True)
-        return out
-
     # ------------------------------------------------------------------ Model protocol
     def _window(self, x):
         """model/dpot.py:180-237 at native resolution: one DPOTNet call on ``in_timesteps`` frames."""
-        if not x.is_cuda:
-            raise RuntimeError("realpdebench_amd.DPOT runs on MI355X only: there is no CPU fallback")
+        self._require_hip(x)
         x = x.contiguous().float()
         params = [p for p in self.parameters()]
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in params):
-            return _DPOTFunction.apply(x, self, *params)
+            return HipFunction.apply(x, self, *params)
         return self._forward_hip(x, save=None)
 
     def forward(self, x):
@@ -608,7 +589,7 @@ class DPOT(_ModelBase):
     def train_loss(self, input, target):
         """model/dpot.py:239-309.  out_timesteps == T_out (every reference YAML): the scalar mean squared error of one window.
         out_timesteps < T_out: sliding windows -- each window's prediction is appended to the input of the next one, so the loss
-        back-propagates through the fed-back predictions (``_DPOTFunction`` returns the window's input gradient); a last partial window
+        back-propagates through the fed-back predictions (``HipFunction`` returns the window's input gradient); a last partial window
         with at least out_timesteps // 2 frames counts with weight remaining / out_timesteps.  The reference returns the ELEMENT-WISE
         sum there (its callers take ``.mean()``), and a partial window's ``[B, remaining, ...]`` loss is added to the full windows'
         ``[B, out_timesteps, ...]`` tensor by broadcasting, which only type-checks for remaining == 1 (or no partial window);
@@ -645,20 +626,3 @@ class DPOT(_ModelBase):
             raise ValueError(f"DPOT: the single-window path takes exactly in_timesteps = {self.in_timesteps} input frames, got {x.shape[1]} "
                              "(the reference's TimeAggregator fails on any other count)")
         return x
-
-
-class _DPOTFunction(torch.autograd.Function):
-    """Autograd glue: one forward / backward call into the HIP pipelines above."""
-
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        sv = {}
-        out = model._forward_hip(x, save=sv)
-        ctx.model, ctx.sv, ctx.params = model, sv, params
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        grads = ctx.model._backward_hip(ctx.sv, g_out.contiguous().float(), need_gx=ctx.needs_input_grad[0])
-        ctx.sv = None
-        return (grads.get("__x__"), None) + tuple(grads.get(p) for p in ctx.params)

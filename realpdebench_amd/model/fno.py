@@ -784,8 +784,3 @@ class FNO3d(Model):
             self._params_settled()
         out = self._forward_impl(x, ws, training=self.training)
         return self._shape_output(out.clone(), x.shape[0])
-
-    def train_loss(self, input, target):
-        """fno.py:131-133: elementwise ``mse_loss(pred, target)`` (callers take ``.mean()``)."""
-        pred = self.forward(input)
-        return (pred - target) ** 2

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ._common import HipFunction, wgrad
 from .fno import FNO3d
 from .model import Model as _ModelBase
 
@@ -128,21 +129,10 @@ class _RegressorCore(FNO3d):
         dWg = torch.empty(C, 3, device=g.device, dtype=torch.float32)
         self._reduce_cols(partl, 0, C * 3, dWg)
         self._reduce_cols(partl, C * 3, C, self.pview("fc0.bias", gflat))
-        dWx, _ = _wgrad(ws.gU, x, d.ncrop, C, Ch)
+        dWx, _ = wgrad(ws.gU, x, d.ncrop, C, Ch, one_reduction=True)
         gw[:, :Ch].copy_(dWx)
         gw[:, Ch:].copy_(dWg)
         ops.gemm_nt(ws.gU, Wx.t().contiguous(), ws.gx, d.ncrop, Ch, C)
-
-
-def _wgrad(G, A, M, N, K, ldg=None, lda=None):
-    """(dW [N,K], db [N]) = (G^T A, colsum G): TN GEMM with split-token partials + fp64 reduction."""
-    base = G.t if isinstance(G, ops.Sub) else G
-    splits = ops.gemm_tn_splits(M, N, K, ldg=ldg, lda=lda)
-    part = torch.empty(splits, N * K + N, device=base.device, dtype=torch.float32)
-    ops.gemm_tn(G, A, part, M, N, K, ldg=ldg, lda=lda)
-    tot = torch.empty(N * K + N, device=base.device, dtype=torch.float32)       # one reduction launch for [dW | db]
-    ops.reduce_partials(part, splits, N * K + N, out_f32=tot, deferrable=True)      # (queued only inside DPOT's deferred_reductions block)
-    return tot[:N * K].view(N, K), tot[N * K:]
 
 
 _REG_RENAME = (("regressor.fc0.", "regressor.fc."), ("regressor.spectral_convs.", "regressor.spectral_conv."),
@@ -352,7 +342,7 @@ class GalerkinTransformer3d(_ModelBase):
 
     # ------------------------------------------------------------------ backward
     @torch.no_grad()
-    def _backward_hip(self, sv, g_out):
+    def _backward_hip(self, sv, g_out, need_gx=False):
         """Gradients of every parameter given dLoss/d(out): autograd of galerkin_transformer.py:20-63."""
         C, Fh, Cin = self.n_hidden, self.dim_ff, self.node_feats
         B, n, M, mk = sv["B"], sv["n"], sv["M"], sv["mk"]
@@ -370,11 +360,11 @@ class GalerkinTransformer3d(_ModelBase):
         g = ws.gx                                                     # dLoss/dX2
         # ---- FeedForward
         g2 = self._through_dropout(g, self._site(mk, "d2"), M * C)
-        grads[enc.ff.lr2.weight], grads[enc.ff.lr2.bias] = _wgrad(g2, sv["Hh"], M, C, Fh)
+        grads[enc.ff.lr2.weight], grads[enc.ff.lr2.bias] = wgrad(g2, sv["Hh"], M, C, Fh, one_reduction=True)
         gH = new(M, Fh)
         mf, drf = self._site(mk, "ffn")
         ops.gemm_nt(g2, T_(enc.ff.lr2.weight), gH, M, Fh, C, act=4, aux=sv["Hh"], mask=mf, drop=drf)
-        grads[enc.ff.lr1.weight], grads[enc.ff.lr1.bias] = _wgrad(gH, sv["X1"], M, Fh, C)
+        grads[enc.ff.lr1.weight], grads[enc.ff.lr1.bias] = wgrad(gH, sv["X1"], M, Fh, C, one_reduction=True)
         gX1 = new(M, C)
         ops.gemm_nt(gH, T_(enc.ff.lr1.weight), gX1, M, C, Fh, residual=g)
         del gH
@@ -398,7 +388,7 @@ class GalerkinTransformer3d(_ModelBase):
                 grads[m.weight] = dgb[h * _DK:(h + 1) * _DK].clone()
                 grads[m.bias] = dgb[C + h * _DK:C + (h + 1) * _DK].clone()
         del gKVn
-        dW, db = _wgrad(gQKV, sv["X0"], M, 3 * C, C)
+        dW, db = wgrad(gQKV, sv["X0"], M, 3 * C, C, one_reduction=True)
         for i, lin in enumerate(at.linears):
             grads[lin.weight], grads[lin.bias] = dW[i * C:(i + 1) * C].clone(), db[i * C:(i + 1) * C].clone()
         gX0 = new(M, C)
@@ -422,8 +412,7 @@ class GalerkinTransformer3d(_ModelBase):
     def forward(self, node, pos=None, grid=None, weight=None, boundary_value=None):
         if pos is not None or grid is not None or weight is not None:
             raise NotImplementedError("pos / grid / weight inputs are never used by the reference's train/eval loops")
-        if not node.is_cuda:
-            raise RuntimeError("realpdebench_amd.GalerkinTransformer3d runs on MI355X only: there is no CPU fallback")
+        self._require_hip(node)
         if tuple(node.shape[1:]) != self.shape_in:
             raise ValueError(f"expected input [B,{','.join(map(str, self.shape_in))}], got {tuple(node.shape)}")
         x = node.contiguous().float()
@@ -432,27 +421,5 @@ class GalerkinTransformer3d(_ModelBase):
             if not self.training:
                 raise NotImplementedError("gradients through eval-mode BatchNorm are not implemented; wrap evaluation in "
                                           "torch.no_grad() as the reference does (train.py:345-361)")
-            return _GalerkinFunction.apply(x, self, *params)
+            return HipFunction.apply(x, self, *params)
         return self._forward_hip(x, save={} if self.training else None)
-
-    def train_loss(self, input, target):
-        """galerkin_transformer.py:65-67: elementwise mse_loss(pred, target) (callers take .mean())."""
-        pred = self.forward(input)
-        return (pred - target) ** 2
-
-
-class _GalerkinFunction(torch.autograd.Function):
-    """Autograd glue: one forward / backward call into the HIP pipelines above."""
-
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        sv = {}
-        out = model._forward_hip(x, save=sv)
-        ctx.model, ctx.sv, ctx.params = model, sv, params
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        grads = ctx.model._backward_hip(ctx.sv, g_out.contiguous().float())
-        ctx.sv = None
-        return (None, None) + tuple(grads.get(p) for p in ctx.params)

@@ -3,7 +3,7 @@ realpdebench/model/MWT_libs/models.py:498-790, built by ``load_model`` like mode
 the reference's ``configs/*/mwt.yaml``: ``k: 3, alpha: 5, c: 4, nCZ: 4, L: 0, base: legendre``.
 
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training backward is not built:
-every attempt to backpropagate raises ``NotImplementedError`` (``MWT_TRAIN_MSG``) instead of returning tensors without a graph.
+every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph.
 
 Pipeline (activations channels-last fp32 ``[B][Nx][Ny][T][36]``, 36 = (c, k^2) = (4, 9); every product runs in a HIP kernel of
 ``csrc/rpb_mwt.hip``; no reference permute survives):
@@ -23,7 +23,7 @@ same operator with its operands as 16-bit planes on the bf16 / fp16 matrix pipe;
 
 Parameters carry the reference's names, shapes and dtypes (``nn`` modules of the same tree), so ``state_dict`` / ``load_state_dict``
 are the reference's; the kernel layouts (lane-ordered convolution weights, mode-major spectral weights, transposed linears) are
-derived tensors rebuilt when a parameter changed (``_prep``).
+derived tensors rebuilt when a parameter changed (``_prep``, through the model's ``LayoutCache``).
 """
 import math
 
@@ -35,13 +35,14 @@ from numpy.polynomial import legendre as npleg
 
 from .. import _lib
 from ..dft import _fwd_complex, _fwd_real, _inv_complex, _inv_real
-from .model import _META_KEYS, Model
+from ..ops import _p, _stream
+from ._common import EvalOnly
+from .model import Model
+
+I16, I32 = torch.int16, torch.int32
 
 ARITHS = ("f32", "bf16x3", "f16x2")      # MWT3d.set_arith
 _PLANES = {"bf16x3": 3, "f16x2": 2}      # 16-bit planes per operand of rpb_mwt_conv3x
-
-MWT_TRAIN_MSG = ("the MWT training step is not built yet: MWT3d on MI355X covers the evaluation forward, train_loss as a value under "
-                 "torch.no_grad(), the rollout and checkpoint I/O")
 
 
 # ----------------------------------------------------------------------------------------------------------- filter bank (numpy only)
@@ -180,20 +181,9 @@ class _CZ(nn.Module):
             self.register_buffer(name, t)
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    if not t.is_cuda:
-        raise _lib.RpbError("realpdebench_amd ops need tensors on a HIP device (no CPU fallback exists)")
-    assert t.is_contiguous() and t.dtype in (torch.float32, torch.int32)
-    return t.data_ptr()
-
-
-class MWT3d(Model):
+class MWT3d(EvalOnly, Model):
     batch_independent = True      # no batch statistics are ever computed (BN is never called)
-    training_unavailable = MWT_TRAIN_MSG      # trainer.make_trainer refuses at construction
+    training_unavailable = EvalOnly.TRAIN_MSG.format("MWT", "MWT3d")
 
     def __init__(self, k=3, alpha=2, c=1, nCZ=3, L=0, base="legendre", initializer=None, shape_in=None, shape_out=None, **kwargs):
         super().__init__()
@@ -231,7 +221,7 @@ class MWT3d(Model):
         if initializer is not None:
             initializer(self.Lc0.weight)
             initializer(self.Lc1.weight)
-        self._plans, self._prepped = {}, None
+        self._plans = {}
         self.arith = "f32"
 
     def set_arith(self, arith):
@@ -259,9 +249,7 @@ class MWT3d(Model):
         logging.info(f"MWT3d.load_checkpoint: {len(ok)}/{len(sd)} entries match" + (f"; skipped {skipped[:5]}" if skipped else ""))
         self.load_state_dict(ok, strict=False)
         self.to(device)
-        blank = {"train_losses": [], "val_losses": {}, "iteration": 0, "best_iteration": 0, "best_val_loss": float("inf")}
-        book = ck if sd is not ck else {}
-        return {meta: book.get(key, blank[key]) for key, meta in _META_KEYS.items()}
+        return self._bookkeeping(ck if sd is not ck else {})
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _plan(self, Nx, Ny, device):
@@ -271,9 +259,11 @@ class MWT3d(Model):
         return self._plans[key]
 
     def _prep(self, device):
-        stamp = (str(device), self.arith) + tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._prepped is not None and self._prepped[0] == stamp:
-            return self._prepped[1]
+        """The kernel-side layouts; the 16-bit planes of the convolution weights only for the selected arithmetic."""
+        return self._layouts.get("prep", list(self.parameters()) + list(self.buffers()), lambda: self._build_prep(device),
+                                 extra=self.arith)
+
+    def _build_prep(self, device):
         f = dict(device=device, dtype=torch.float32)
         czs = []
         for cz in self.MWT_CZ:
@@ -296,11 +286,9 @@ class MWT3d(Model):
             d["rc"] = torch.stack([cz.rc_ee, cz.rc_eo, cz.rc_oe, cz.rc_oo]).contiguous()
             d["ec_d"], d["ec_s"] = cz.ec_d.contiguous(), cz.ec_s.contiguous()
             czs.append(d)
-        prep = dict(cz=czs, Lkw=self.Lk.weight.detach().contiguous(), Lkb=self.Lk.bias.detach().contiguous(),
+        return dict(cz=czs, Lkw=self.Lk.weight.detach().contiguous(), Lkb=self.Lk.bias.detach().contiguous(),
                     w0t=self.Lc0.weight.detach().t().contiguous(), b0=self.Lc0.bias.detach().contiguous(),
                     w1=self.Lc1.weight.detach().contiguous(), b1=self.Lc1.bias.detach().contiguous())
-        self._prepped = (stamp, prep)
-        return prep
 
     # ------------------------------------------------------------------ the kernels, one method per family (tests call these)
     @staticmethod
@@ -345,8 +333,8 @@ class MWT3d(Model):
         ew = None
         if planes == 2:
             ew = torch.empty(1, device=w.device, dtype=torch.int32)
-            _lib.call("rpb_amax_exp", _p(w), 36, 972, 972, ew.data_ptr(), _stream(), label="amax_exp", nbytes=4 * w.numel())
-        _lib.call("rpb_mwt_conv3x_wprep", _p(w), wpx.data_ptr(), planes, ew.data_ptr() if planes == 2 else None, _stream())
+            _lib.call("rpb_amax_exp", _p(w), 36, 972, 972, _p(ew, I32), _stream(), label="amax_exp", nbytes=4 * w.numel())
+        _lib.call("rpb_mwt_conv3x_wprep", _p(w), _p(wpx, I16), planes, _p(ew, I32), _stream())
         return wpx, ew
 
     @staticmethod
@@ -366,9 +354,9 @@ class MWT3d(Model):
             planes, ea = _PLANES[arith], None
             if planes == 2:                       # per-tensor exponent of the activations, kept on the device
                 ea = torch.empty(1, device=x.device, dtype=torch.int32)
-                _lib.call("rpb_amax_exp", _p(x), x.numel() // 36, 36, 36, ea.data_ptr(), _stream(), label="mwt_amax_exp", nbytes=4 * x.numel())
-            _lib.call("rpb_mwt_conv3x", _p(x), wpx.data_ptr(), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), planes,
-                      ea.data_ptr() if planes == 2 else None, ew.data_ptr() if planes == 2 else None, _stream(),
+                _lib.call("rpb_amax_exp", _p(x), x.numel() // 36, 36, 36, _p(ea, I32), _stream(), label="mwt_amax_exp", nbytes=4 * x.numel())
+            _lib.call("rpb_mwt_conv3x", _p(x), _p(wpx, I16), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), planes,
+                      _p(ea, I32), _p(ew, I32), _stream(),
                       label=f"mwt_conv3[{arith}]", nbytes=nbytes, flops=flops)
             return out
         _lib.call("rpb_mwt_conv3", _p(x), _p(wp), _p(cb), _p(lop), _p(lb), _p(out), B, Nx, Ny, T, int(acc), _stream(), label="mwt_conv3",
@@ -393,7 +381,7 @@ class MWT3d(Model):
         X = MWT3d.k_axis(y, plan.FX, B, KY * m * C)                         # [B][(ri, kx)][ky][kt][36]
         NB = KX * KY * m
         Y = torch.empty_like(X)
-        _lib.call("rpb_mwt_modes", _p(X), _p(Wt), _p(plan.tab), _p(Y), B, NB, _stream(), label="mwt_modes",
+        _lib.call("rpb_mwt_modes", _p(X), _p(Wt), _p(plan.tab, I32), _p(Y), B, NB, _stream(), label="mwt_modes",
                   nbytes=16 * B * NB * C + 8 * NB * C * C, flops=8 * B * NB * C * C)
         z = MWT3d.k_axis(Y, plan.GX, B, KY * m * C)                         # [B][(x, ri)][ky][kt][36]
         z = MWT3d.k_axis(z, plan.GY, B * Nx, m * C)                         # [B][Nx][(y, ri)][kt][36]
@@ -435,12 +423,8 @@ class MWT3d(Model):
         return x
 
     def forward(self, x):
-        # never hand back a tensor that silently carries no graph: under grad mode anything that asks for a gradient is refused
-        # (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with requires_grad off)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(MWT_TRAIN_MSG)
-        if not x.is_cuda:
-            raise RuntimeError("MWT3d runs on MI355X only: there is no CPU fallback (move the model and its input to 'cuda')")
+        self._require_eval(x)
+        self._require_hip(x)
         if tuple(x.shape[1:]) != self.shape_in:
             raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(x.shape)}")
         with torch.no_grad():
@@ -450,10 +434,3 @@ class MWT3d(Model):
             for i, cz in enumerate(p["cz"]):
                 h = self._cz_forward(h, cz, relu=i < self.nCZ - 1)
             return self.k_head(h, p["w0t"], p["b0"], p["w1"], p["b1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])
-
-    def train_loss(self, input, target):
-        """Elementwise MSE (the reference's ``mse_loss(pred, target)``), as a value: under grad mode it raises, see the module docstring."""
-        if torch.is_grad_enabled():
-            raise NotImplementedError(MWT_TRAIN_MSG)
-        pred = self.forward(input)
-        return (pred - target) ** 2

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ._common import HipFunction, wgrad
 from .model import Model as _ModelBase
 
 
@@ -94,8 +95,6 @@ class Transolver(_ModelBase):
         self.blocks = nn.ModuleList([_Block(n_hidden, n_head, mlp_ratio, slice_num, i == n_layers - 1, out_dim)
                                      for i in range(n_layers)])
         self.placeholder = nn.Parameter((1.0 / n_hidden) * torch.rand(n_hidden))
-        self._wcat = {}
-        self._wh = {}                   # block -> (key, f16x2 weight planes of _conv_cat) for the f16x2 eval forward
         self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
         self._mask_override = None      # tests: list of (attn_mask [B,h,G,G], out_mask [M,C]) per block, already scaled
 
@@ -103,23 +102,21 @@ class Transolver(_ModelBase):
     # column = ((kh*3+kw)*3+kd)*Ci + ci  (what rpb_gemm_nt's implicit-GEMM loader walks)
     def _conv_cat(self, i):
         a = self.blocks[i].Attn
-        key = (i, a.in_project_fx.weight._version, a.in_project_x.weight._version, a.in_project_fx.bias._version,
-               a.in_project_x.bias._version, str(a.in_project_x.weight.device))
-        if self._wcat.get(i, (None,))[0] != key:
+        src = (a.in_project_fx.weight, a.in_project_x.weight, a.in_project_fx.bias, a.in_project_x.bias)
+
+        def build():
             C = self.n_hidden
             w = torch.cat([a.in_project_fx.weight.detach(), a.in_project_x.weight.detach()], dim=0)     # [2C,Ci,3,3,3]
             w = w.permute(0, 2, 3, 4, 1).reshape(2 * C, 27 * C).contiguous()
-            b = torch.cat([a.in_project_fx.bias.detach(), a.in_project_x.bias.detach()]).contiguous()
-            self._wcat[i] = (key, w, b)
-        return self._wcat[i][1], self._wcat[i][2]
+            return w, torch.cat([a.in_project_fx.bias.detach(), a.in_project_x.bias.detach()]).contiguous()
+
+        return self._layouts.get(("conv_cat", i), src, build)
 
     def _conv_cat_f16x2(self, i):
-        """_conv_cat's weight as ops.conv3_f16x2_weights planes, cached under the same key."""
-        wcat, _ = self._conv_cat(i)
-        key = self._wcat[i][0]
-        if self._wh.get(i, (None,))[0] != key:
-            self._wh[i] = (key, ops.conv3_f16x2_weights(wcat, 2 * self.n_hidden, self.n_hidden))
-        return self._wh[i][1]
+        """_conv_cat's weight as ops.conv3_f16x2_weights planes, cached under the same rule."""
+        a = self.blocks[i].Attn
+        return self._layouts.get(("conv_cat_f16x2", i), (a.in_project_fx.weight, a.in_project_x.weight),
+                                 lambda: ops.conv3_f16x2_weights(self._conv_cat(i)[0], 2 * self.n_hidden, self.n_hidden))
 
     def set_arith(self, arith):
         """Arithmetic of the evaluation / rollout forward's 3x3x3 convolutions: ``"f32"`` (default, the parity path: operands as three
@@ -228,24 +225,6 @@ class Transolver(_ModelBase):
         return out.reshape(*x.shape[:-1], self.out_dim)
 
     # ------------------------------------------------------------------ backward
-    def _wgrad(self, G, A, M, N, K, ldg=None, lda=None, conv=None):
-        """(dW [N,K], db [N]) = (G^T A, colsum G) through the TN GEMM + fp64 partial reduction."""
-        taps_rev = False
-        if conv is not None:
-            part, taps_rev = ops.conv3_wgrad_parts(G, A, M, N, K // 27, conv, ldg=ldg, ldx=lda)
-            splits = part.shape[0]
-        else:
-            splits = ops.gemm_tn_splits(M, N, K, False, ldg=ldg, lda=lda)
-            part = torch.empty(splits, N * K + N, device=G.device, dtype=torch.float32)
-            ops.gemm_tn(G, A, part, M, N, K, ldg=ldg, lda=lda)
-        dW = torch.empty(N, K, device=G.device, dtype=torch.float32)
-        db = torch.empty(N, device=G.device, dtype=torch.float32)
-        ops.reduce_partials(part, splits, N * K, out_f32=dW.view(-1), row_stride=N * K + N)
-        ops.reduce_partials(part, splits, N, out_f32=db, row_stride=N * K + N, col0=N * K)
-        if taps_rev:
-            dW = ops.conv3_taps_restore(dW, N, K // 27)
-        return dW, db
-
     def _ln_bwd(self, x, ln, gy, gadd, M, C):
         rows = ops.layernorm_bwd_rows(M)
         part = torch.empty(rows, 2 * C, device=x.device, dtype=torch.float32)
@@ -256,7 +235,7 @@ class Transolver(_ModelBase):
         return gx, dgb[:C].clone(), dgb[C:].clone()
 
     @torch.no_grad()
-    def _backward_hip(self, sv, g_out):
+    def _backward_hip(self, sv, g_out, need_gx=False):
         """Gradients of every parameter given dLoss/d(out) -- autograd of Transolver_Structured_Mesh_3D.py:170-196.
         Returns {parameter: gradient}."""
         C, heads, G, M, B, ntok = self.n_hidden, self.n_head, self.slice_num, sv["M"], sv["B"], sv["ntok"]
@@ -274,15 +253,15 @@ class Transolver(_ModelBase):
                 go = g_out.reshape(M, od).contiguous()
                 gpad = torch.zeros(M, (od + 3) // 4 * 4, **f)               # even leading dimension for float2 loads
                 gpad[:, :od] = go
-                grads[blk.mlp2.weight], grads[blk.mlp2.bias] = self._wgrad(gpad, st["a3"], M, od, C, ldg=gpad.shape[1])
+                grads[blk.mlp2.weight], grads[blk.mlp2.bias] = wgrad(gpad, st["a3"], M, od, C, ldg=gpad.shape[1])
                 ga3 = new(M, C)
                 ops.tokens_lift(go, T(blk.mlp2.weight), torch.zeros(C, **f), ga3, M, od, C, False)   # g_out @ W2
                 g, grads[blk.ln_3.weight], grads[blk.ln_3.bias] = self._ln_bwd(st["fx2"], blk.ln_3, ga3, None, M, C)
             # ---- MLP (fx2 = fx1 + post(gelu(pre(LN2(fx1)))))
-            grads[blk.mlp.linear_post.weight], grads[blk.mlp.linear_post.bias] = self._wgrad(g, st["hid"], M, C, Hm)
+            grads[blk.mlp.linear_post.weight], grads[blk.mlp.linear_post.bias] = wgrad(g, st["hid"], M, C, Hm)
             ghp = new(M, Hm)
             ops.gemm_nt(g, T(blk.mlp.linear_post.weight), ghp, M, Hm, C, act=2, aux=st["hpre"])
-            grads[blk.mlp.linear_pre[0].weight], grads[blk.mlp.linear_pre[0].bias] = self._wgrad(ghp, st["a2"], M, Hm, C)
+            grads[blk.mlp.linear_pre[0].weight], grads[blk.mlp.linear_pre[0].bias] = wgrad(ghp, st["a2"], M, Hm, C)
             ga2 = new(M, C)
             ops.gemm_nt(ghp, T(blk.mlp.linear_pre[0].weight), ga2, M, C, Hm)
             del ghp
@@ -295,7 +274,7 @@ class Transolver(_ModelBase):
                     ops.dropout_mul(g1, g1m, M * C, *st["omask"])
                 else:
                     ops.mul(g1, st["omask"], g1m, M * C)
-            grads[at.to_out[0].weight], grads[at.to_out[0].bias] = self._wgrad(g1m, st["ox"], M, C, C)
+            grads[at.to_out[0].weight], grads[at.to_out[0].bias] = wgrad(g1m, st["ox"], M, C, C)
             gox = new(M, C)
             ops.gemm_nt(g1m, T(at.to_out[0].weight), gox, M, C, C)
             # ---- deslice backward w.r.t. the attended slice tokens: g_tok2 = sum_n w * g_ox
@@ -326,7 +305,7 @@ class Transolver(_ModelBase):
             inside = ((temp >= 0.1) & (temp <= 5.0)).float()                    # torch.clamp passes the gradient inside
             grads[at.temperature] = (tot[G * 32 + G:] * inside).view(1, heads, 1, 1)
             # ---- the two convolutions: weight gradient (TN implicit GEMM) and data gradient (flipped-tap implicit GEMM)
-            dWc, dbc = self._wgrad(gxf, st["a1"], M, 2 * C, 27 * C, conv=(self.H, self.W, self.D))
+            dWc, dbc = wgrad(gxf, st["a1"], M, 2 * C, 27 * C, conv=(self.H, self.W, self.D))
             dWc = dWc.view(2 * C, 3, 3, 3, C).permute(0, 4, 1, 2, 3).contiguous()
             grads[at.in_project_fx.weight], grads[at.in_project_x.weight] = dWc[:C].clone(), dWc[C:].clone()
             grads[at.in_project_fx.bias], grads[at.in_project_x.bias] = dbc[:C].clone(), dbc[C:].clone()
@@ -338,7 +317,7 @@ class Transolver(_ModelBase):
             g, grads[blk.ln_1.weight], grads[blk.ln_1.bias] = self._ln_bwd(st["fx0"], blk.ln_1, ga1, g1, M, C)
         # ---- preprocess MLP (+ placeholder): fx0 = post(gelu(pre(x))) + placeholder
         pre = self.preprocess
-        dW, db = self._wgrad(g, sv["h1"], M, C, 2 * C)
+        dW, db = wgrad(g, sv["h1"], M, C, 2 * C)
         grads[pre.linear_post.weight], grads[pre.linear_post.bias], grads[self.placeholder] = dW, db, db.clone()
         Cin = self.in_dim
         h1pre = new(M, 2 * C)
@@ -347,39 +326,15 @@ class Transolver(_ModelBase):
         ops.gemm_nt(g, T(pre.linear_post.weight), gh1, M, 2 * C, C, act=2, aux=h1pre)
         xpad = torch.zeros(M, (Cin + 3) // 4 * 4, **f)
         xpad[:, :Cin] = sv["x2"]
-        grads[pre.linear_pre[0].weight], grads[pre.linear_pre[0].bias] = self._wgrad(gh1, xpad, M, 2 * C, Cin,
-                                                                                     lda=xpad.shape[1])
+        grads[pre.linear_pre[0].weight], grads[pre.linear_pre[0].bias] = wgrad(gh1, xpad, M, 2 * C, Cin, lda=xpad.shape[1])
         return grads
 
     def forward(self, x, fx=None, T=None):
         if fx is not None or T is not None:
             raise NotImplementedError("fx / T inputs are never used by the reference's train/eval loops")
-        if not x.is_cuda:
-            raise RuntimeError("realpdebench_amd.Transolver runs on MI355X only: there is no CPU fallback")
+        self._require_hip(x)
         x = x.contiguous().float()
         params = [p for p in self.parameters()]
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _TransolverFunction.apply(x, self, *params)
+            return HipFunction.apply(x, self, *params)
         return self._forward_hip(x)
-
-    def train_loss(self, input, target):
-        """Transolver_Structured_Mesh_3D.py:198-201: elementwise (pred - target)**2 (callers take .mean())."""
-        pred = self.forward(input)
-        return (pred - target) ** 2
-
-
-class _TransolverFunction(torch.autograd.Function):
-    """Autograd glue: one forward / backward call into the HIP pipelines above."""
-
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        sv = {}
-        out = model._forward_hip(x, save=sv)
-        ctx.model, ctx.sv, ctx.params = model, sv, params
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        grads = ctx.model._backward_hip(ctx.sv, g_out.contiguous().float())
-        ctx.sv = None
-        return (None, None) + tuple(grads.get(p) for p in ctx.params)

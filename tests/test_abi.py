@@ -5,10 +5,28 @@ import re
 from conftest import ROOT
 
 
-def declared_symbols():
+def _header():
     txt = open(os.path.join(ROOT, "include", "rpb.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rpb_[a-z0-9_]+)\s*\(", txt)))
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def declared_symbols():
+    return sorted(set(re.findall(r"\b(rpb_[a-z0-9_]+)\s*\(", _header())))
+
+
+def declared_signatures():
+    """name -> (return type, argument codes of ``_lib.SIGNATURES``) parsed from the declarations of include/rpb.h."""
+    def code(param):
+        if "*" in param or "hipStream_t" in param:
+            return "p"
+        words = [w for w in param.split()[:-1] if w not in ("const", "unsigned", "signed")]      # the last word is the name
+        return {"int": "i", "long": "l", "float": "f", "double": "d"}[" ".join(words)]
+
+    out = {}
+    for ret, name, params in re.findall(r"\b([a-z][a-z ]*?\*?)\s*\b(rpb_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header()):
+        params = params.strip()
+        out[name] = (" ".join(ret.split()), "" if params == "void" else "".join(code(q.strip()) for q in params.split(",")))
+    return out
 
 
 def test_header_symbols_exported_and_bound():
@@ -20,6 +38,14 @@ def test_header_symbols_exported_and_bound():
         assert hasattr(lib, n), f"{n} declared in include/rpb.h but not exported by librpb_hip.so"
         assert n in _lib.SIGNATURES, f"{n} has no ctypes signature in realpdebench_amd/_lib.py"
     assert set(_lib.SIGNATURES) == set(names)
+    # every hand-typed row against the declaration: callers pass bare Python ints, so a wrong l / i would truncate silently
+    import ctypes
+    restypes = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+    decl = declared_signatures()
+    assert set(decl) == set(names)
+    for n in names:
+        ret, codes = decl[n]
+        assert _lib.SIGNATURES[n] == (restypes[ret], codes), f"{n}: include/rpb.h declares {ret} ({codes}), _lib.SIGNATURES has {_lib.SIGNATURES[n]}"
     hdr = open(os.path.join(ROOT, "include", "rpb.h")).read()
     assert lib.rpb_abi_version() == int(re.search(r"#define RPB_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION
 
