@@ -8,7 +8,7 @@
 #define TS_THREADS 256
 
 // ---------------------------------------------------------------------------------- tiny-K linear (+GELU)
-// out[m][n] = act(sum_{k<K} x[m][k] W[n][k] + b[n]),  K <= 8  (preprocess.linear_pre: C_in = 3 -> 512, GELU)
+// out[m][n] = act(sum_{k<K} x[m][k] W[n][k] + b[n]),  K <= 32, (K + 1) N floats of LDS  (preprocess.linear_pre: C_in = 3 -> 512, GELU)
 __global__ __launch_bounds__(TS_THREADS) void tokens_lift_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                  const float* __restrict__ b, float* __restrict__ out,
                                                                  long M, int K, int N, int act) {
@@ -43,6 +43,9 @@ extern "C" int rpb_tokens_lift(const float* x, const float* W, const float* b, f
                                void* stream) {
     RPB_REQUIRE(x && W && b && out && M > 0 && K > 0 && K <= 32 && N % 4 == 0, "tokens_lift: bad arguments (K=%d N=%d)", K, N);
     const size_t lds = (size_t)(K + 1) * N * 4;
+    RPB_REQUIRE(lds <= 160 * 1024, "tokens_lift: LDS (K=%d N=%d)", K, N);
+    if (lds > 64 * 1024)        // past the default limit only (K = 32 at N = 512); the lift layers of the configs (K = 3) stay below
+        (void)hipFuncSetAttribute((const void*)tokens_lift_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     long grid = (M * (N / 4) + TS_THREADS - 1) / TS_THREADS;
     const long cap = (long)rpb_num_cus() * 8;
     if (grid > cap) grid = cap;
