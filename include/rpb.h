@@ -727,6 +727,21 @@ int rpb_don_trunk(const float* gt, const float* gh, const float* gw, const float
 int rpb_don_point_mlp(const float* t, const float* b, const void* w1z, const float* b1z, const void* w2z, const float* b2z,
                       const void* w3z, const float* b3, float* out, int B, long N, int p, int Cout, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * CNO3d (realpdebench/model/cno.py, activation = 'LeakyReLU') -- evaluation forward (additions do not change RPB_ABI_VERSION).
+ * Every layer is Conv3d(3, padding=1) + eval BatchNorm + LeakyReLU(0.2) / residual add / channel concat; DESIGN.md section 17.
+ *     rpb_cno_conv3x: the implicit GEMM of rpb_conv3x (same planes P[3][M][Ci], same rpb_conv3x_wprep weights, same six products) with
+ *     the epilogue  v = acc * sc[n] + sh[n];  if (act) v = v > 0 ? v : 0.2 v;  if (res) v += res[m * ldr + n]  (sc, sh: [N]).
+ *     The first nvalid channels leave as fp32 rows out[m * ldo + n] (out may be null) and / or as the three bf16 planes of v at
+ *     out_planes[pl * M * ldp + m * ldp + n] (may be null; bit-equal to rpb_split3 of the fp32 v).  out, out_planes and res point at the
+ *     first column the launch owns, so producers of disjoint column ranges fill one buffer (the concat).  Ci % 64 == 0, N in {64, 128},
+ *     1 <= nvalid <= N, act in {0, 1}; plane output: first column 16-byte aligned, ldp % 8 == 0, nvalid % 8 == 0.  Pad columns of a plane
+ *     buffer a convolution reads must be zero (zero weights do not cancel NaN): the caller owns that. */
+int rpb_cno_conv3x(const void* planes, const void* Wz, const float* sc, const float* sh, const float* res, float* out, void* out_planes,
+                   long M, int N, int Ci, int nvalid, int act, int ldr, int ldo, int ldp, int Hc, int Wc, int Dc, void* stream);
+/*     the first layer's input: x [M][Cin] fp32 (1 <= Cin <= 64) -> planes P[3][M][64] with columns Cin..63 zero */
+int rpb_cno_pack(const float* x, void* planes, long M, int Cin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

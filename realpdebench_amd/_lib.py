@@ -205,6 +205,8 @@ SIGNATURES = {
     "rpb_don_bn_relu_pool": (_I, "pppp" + "iiiiiiii" + "p"),
     "rpb_don_trunk": (_I, "pppppppppp" + "iiii" + "p"),
     "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),
+    "rpb_cno_conv3x": (_I, "ppppppp" + "l" + "iiiiiii" + "iii" + "p"),
+    "rpb_cno_pack": (_I, "pp" + "li" + "p"),
 }
 
 _lib = None

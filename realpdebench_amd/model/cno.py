@@ -1,0 +1,320 @@
+"""CNO3d on MI355X -- drop-in for ``realpdebench.model.cno.CNO3d`` (reference realpdebench/model/cno.py, built by ``load_model`` like
+model/load_model.py:60-75) for the reference's ``configs/*/cno.yaml``.
+
+``load_model`` passes only ``in_dim``, ``out_dim``, ``out_dim_mult``, ``in_size`` and ``N_layers``, so every shipped config runs with
+``activation='LeakyReLU'`` (cno.py:256), a six-block neck and no up- or down-sampling: the model is 35 ``Conv3d(3, padding=1)`` layers
+at full resolution, each followed by an eval BatchNorm3d, LeakyReLU(0.2), a residual add or a channel concat.
+
+Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training step is not built: every
+attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) and ``trainer.make_trainer`` refuses the model at
+construction.  BatchNorm3d uses its running statistics in every mode (no batch-statistics path exists).
+
+Pipeline (activations channels-last rows ``[B * T * H * W][C]``, mesh (T, H, W)):
+  rpb_cno_pack      x [M][in_dim] -> bf16 planes P[3][M][64], columns in_dim..63 zero
+  rpb_cno_conv3x    x 35: implicit GEMM on the planes + ``v = acc * sc + sh``, LeakyReLU, residual; the result leaves as bf16 planes for the
+                    next convolution (and as fp32 rows only where a residual add reads it later, and at the end)
+Layers narrower than 64 channels run padded to 64 with zero weight rows / columns and ``sc = sh = 0``; the pad columns of every plane
+buffer a convolution reads are zeroed here (zero weights do not cancel NaN).  A concat is two producers writing disjoint column ranges
+of one plane buffer.
+
+Parameters carry the reference's names, shapes and dtypes (the same ``nn`` module tree, ``decoder_inv.3`` -- constructed, never used in
+``forward`` -- included), so ``state_dict`` / ``load_state_dict`` are the reference's; kernel layouts are derived tensors rebuilt when a
+parameter changed.
+"""
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from ..ops import Sub, _p, _stream
+from ._common import EvalOnly
+from .model import Model
+
+I16 = torch.int16
+N_LAYERS = 3
+MAX_CH = 64                    # widest first-layer input / last-layer output: one 64-channel tile
+# reference defaults of every keyword load_model never passes (cno.py:240-256)
+DEFAULTS = dict(N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001, filter_size=6, lrelu_upsampling=2,
+                half_width_mult=0.8, radial=False, batch_norm=True, out_size=1, expand_input=False, latent_lift_proj_dim=64, add_inv=True)
+
+
+# ----------------------------------------------------------------------------------------------------------- parameter tree
+class CNOBlock3d(nn.Module):
+    """conv -> BatchNorm3d (optional) -> LeakyReLU(0.2) (cno.py:28-100)."""
+
+    def __init__(self, in_channels, out_channels, batch_norm=True):
+        super().__init__()
+        self.convolution = nn.Conv3d(in_channels, out_channels, kernel_size=3, padding=1)
+        self.batch_norm = nn.BatchNorm3d(out_channels) if batch_norm else False
+        self.activation = nn.LeakyReLU(negative_slope=0.2)
+
+
+class LiftProjectBlock3d(nn.Module):
+    """CNOBlock (no BatchNorm) -> conv (cno.py:106-152; lift and project are built with batch_norm=False)."""
+
+    def __init__(self, in_channels, out_channels, latent_dim=64):
+        super().__init__()
+        self.inter_CNOBlock = CNOBlock3d(in_channels, latent_dim, batch_norm=False)
+        self.convolution = nn.Conv3d(latent_dim, out_channels, kernel_size=3, stride=1, padding=1)
+        self.batch_norm = False
+
+
+class ResidualBlock3d(nn.Module):
+    """x + BN(conv(L(BN(conv x)))) (cno.py:159-231): the residual is added after the second BatchNorm, no activation follows."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.convolution1 = nn.Conv3d(channels, channels, kernel_size=3, stride=1, padding=1)
+        self.convolution2 = nn.Conv3d(channels, channels, kernel_size=3, stride=1, padding=1)
+        self.batch_norm1 = nn.BatchNorm3d(channels)
+        self.batch_norm2 = nn.BatchNorm3d(channels)
+        self.activation = nn.LeakyReLU(negative_slope=0.2)
+
+
+def fold_affine(conv, bn, N):
+    """(sc, sh) [N] of ``v = acc * sc + sh``: sc = gamma / sqrt(var + eps), sh = beta + (bias - mean) * sc, formed in float64 and rounded
+    once; without BatchNorm sc = 1, sh = bias.  Pad channels get sc = sh = 0."""
+    bias = conv.bias.detach().double()
+    Co = bias.numel()
+    if isinstance(bn, nn.BatchNorm3d):
+        sc64 = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        sh64 = bn.bias.detach().double() + (bias - bn.running_mean.detach().double()) * sc64
+    else:
+        sc64, sh64 = torch.ones_like(bias), bias
+    sc, sh = torch.zeros(N, dtype=torch.float32, device=bias.device), torch.zeros(N, dtype=torch.float32, device=bias.device)
+    sc[:Co], sh[:Co] = sc64.float(), sh64.float()
+    return sc, sh
+
+
+def padded_weight(conv, N, K):
+    """Conv3d weight [Co][Ci][3][3][3] -> [N][27 * K] fp32, tap-major and channel-minor rows, zero rows / columns on the pad channels."""
+    w = conv.weight.detach()
+    Co, Ci = w.shape[:2]
+    wm = torch.zeros(N, 27, K, dtype=torch.float32, device=w.device)
+    wm[:Co, :, :Ci] = w.permute(0, 2, 3, 4, 1).reshape(Co, 27, Ci)
+    return wm.reshape(N, 27 * K)
+
+
+class _Planes:
+    """bf16 plane buffer P[3][M][ld] (int16 bit patterns).  ``zero``: the producers leave columns unwritten that a convolution reads."""
+
+    def __init__(self, M, ld, device, zero):
+        self.t = (torch.zeros if zero else torch.empty)(3 * M * ld, dtype=I16, device=device)
+        self.ld = ld
+
+    def ptr(self, col=0):
+        return _p(self.t, I16) + 2 * col
+
+
+def _ptr(t, dtype=torch.float32):
+    """address of a tensor of ``dtype``, of an ``ops.Sub`` (a block of an fp32 allocation, whatever it holds), or the address itself"""
+    if t is None or isinstance(t, int):
+        return t
+    return _p(t) if isinstance(t, Sub) else _p(t, dtype)
+
+
+class CNO3d(EvalOnly, Model):
+    batch_independent = True                        # BatchNorm runs on its running statistics only
+    training_unavailable = EvalOnly.TRAIN_MSG.format("CNO", "CNO3d")
+
+    def __init__(self, in_dim, in_size, N_layers, N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001,
+                 filter_size=6, lrelu_upsampling=2, half_width_mult=0.8, radial=False, batch_norm=True, out_dim=1, out_dim_mult=1,
+                 out_size=1, expand_input=False, latent_lift_proj_dim=64, add_inv=True, activation="LeakyReLU"):
+        super().__init__()
+        given = dict(N_res=N_res, N_res_neck=N_res_neck, channel_multiplier=channel_multiplier, conv_kernel=conv_kernel,
+                     cutoff_den=cutoff_den, filter_size=filter_size, lrelu_upsampling=lrelu_upsampling, half_width_mult=half_width_mult,
+                     radial=radial, batch_norm=batch_norm, out_size=out_size, expand_input=expand_input,
+                     latent_lift_proj_dim=latent_lift_proj_dim, add_inv=add_inv)
+        unsupported = []
+        if int(N_layers) != N_LAYERS:
+            unsupported.append(f"N_layers={N_layers} (every cno.yaml has 3)")
+        if activation != "LeakyReLU":
+            unsupported.append(f"activation={activation!r} (only 'LeakyReLU': the filtered activations are not built)")
+        for k, v in given.items():
+            if v != DEFAULTS[k]:
+                unsupported.append(f"{k}={v!r} (only the reference default {DEFAULTS[k]!r}: load_model never passes it)")
+        if int(out_dim) * int(out_dim_mult) > MAX_CH or int(out_dim) * int(out_dim_mult) < 1:
+            unsupported.append(f"out_dim * out_dim_mult = {int(out_dim) * int(out_dim_mult)} (1..{MAX_CH})")
+        if not 1 <= int(in_dim) <= MAX_CH:
+            unsupported.append(f"in_dim={in_dim} (1..{MAX_CH})")
+        if unsupported:
+            raise NotImplementedError("MI355X CNO3d covers the configuration family of the reference's configs/*/cno.yaml; unsupported: "
+                                      + "; ".join(unsupported))
+        self.in_dim, self.in_size, self.N_layers = int(in_dim), in_size, N_LAYERS
+        self.out_dim_mult, self.out_dim = int(out_dim_mult), int(out_dim) * int(out_dim_mult)     # out_dim: the total, as in cno.py:270
+        self.N_res, self.N_res_neck, self.add_inv = 1, 6, True
+        self.lift_dim = channel_multiplier // 2
+        self.encoder_features = ef = [self.lift_dim] + [2 ** i * channel_multiplier for i in range(N_LAYERS)]        # 16, 32, 64, 128
+        dec_in = [ef[3], 2 * ef[2], 2 * ef[1]]                                                                       # 128, 128, 64
+        dec_out = [ef[2], ef[1], ef[0]]                                                                              # 64, 32, 16
+        inv = dec_in + [ef[0] + dec_out[-1]]                                                                         # 128, 128, 64, 32
+        self.lift = LiftProjectBlock3d(self.in_dim, ef[0], latent_lift_proj_dim)
+        self.project = LiftProjectBlock3d(ef[0] + dec_out[-1], self.out_dim, latent_lift_proj_dim)
+        self.encoder = nn.ModuleList([CNOBlock3d(ef[i], ef[i + 1]) for i in range(N_LAYERS)])
+        self.ED_expansion = nn.ModuleList([CNOBlock3d(ef[i], ef[i]) for i in range(N_LAYERS + 1)])
+        self.decoder = nn.ModuleList([CNOBlock3d(dec_in[i], dec_out[i]) for i in range(N_LAYERS)])
+        self.decoder_inv = nn.ModuleList([CNOBlock3d(inv[i], inv[i]) for i in range(N_LAYERS + 1)])                  # [3] is never used
+        self.res_nets = nn.Sequential(*([ResidualBlock3d(ef[l]) for l in range(N_LAYERS)] + [ResidualBlock3d(ef[N_LAYERS]) for _ in range(6)]))
+
+    # ------------------------------------------------------------------ checkpoints
+    def load_checkpoint(self, checkpoint_path, device="cpu"):
+        """The base class's loader (``model_state_dict`` + bookkeeping, realpdebench/model/model.py); a bare weights file gives the
+        bookkeeping entries of an untrained run (iteration 0, no losses), as MWT3d and DeepONet do."""
+        ck = torch.load(checkpoint_path, map_location="cpu")
+        if "model_state_dict" in ck:
+            meta = super().load_checkpoint(checkpoint_path, "cpu")
+        else:
+            self.load_state_dict(ck)
+            meta = self._bookkeeping({})
+        self.to(device)
+        return meta
+
+    # ------------------------------------------------------------------ kernel-side layouts
+    def _convs(self):
+        """name -> (conv, BatchNorm3d or False) of the 35 convolutions ``forward`` runs."""
+        out = {"lift.0": (self.lift.inter_CNOBlock.convolution, False), "lift.1": (self.lift.convolution, False),
+               "project.0": (self.project.inter_CNOBlock.convolution, False), "project.1": (self.project.convolution, False)}
+        for i in range(N_LAYERS):
+            out[f"encoder.{i}"] = (self.encoder[i].convolution, self.encoder[i].batch_norm)
+            out[f"decoder.{i}"] = (self.decoder[i].convolution, self.decoder[i].batch_norm)
+            out[f"decoder_inv.{i}"] = (self.decoder_inv[i].convolution, self.decoder_inv[i].batch_norm)
+        for i in range(N_LAYERS + 1):
+            out[f"ED_expansion.{i}"] = (self.ED_expansion[i].convolution, self.ED_expansion[i].batch_norm)
+        for i, r in enumerate(self.res_nets):
+            out[f"res_nets.{i}.1"] = (r.convolution1, r.batch_norm1)
+            out[f"res_nets.{i}.2"] = (r.convolution2, r.batch_norm2)
+        return out
+
+    def _prep(self, device):
+        tensors = list(self.parameters()) + list(self.buffers())
+        return self._layouts.get("prep", tensors, lambda: self._build_prep(device))
+
+    def _build_prep(self, device):
+        prep = {}
+        for name, (conv, bn) in self._convs().items():
+            Co, Ci = conv.weight.shape[:2]
+            N, K = max(Co, 64), max(Ci, 64)
+            wz = self.k_wprep(padded_weight(conv, N, K).to(device), N, K)
+            sc, sh = fold_affine(conv, bn, N)
+            prep[name] = dict(wz=wz, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
+        return prep
+
+    # ------------------------------------------------------------------ the kernels, one method per family (tests call these)
+    @staticmethod
+    def k_wprep(wm, N, K):
+        wz = torch.empty(3 * N * 27 * K, device=wm.device, dtype=I16)
+        _lib.call("rpb_conv3x_wprep", _p(wm), _p(wz, I16), N, K, _stream(), label="conv3x_wprep", nbytes=10 * N * 27 * K)
+        return wz
+
+    @staticmethod
+    def k_pack(x, planes, M, Cin):
+        """x [M][Cin] fp32 -> planes P[3][M][64], columns Cin..63 zero."""
+        _lib.call("rpb_cno_pack", _ptr(x), _ptr(planes, I16), M, Cin, _stream(), label="cno_pack", nbytes=4 * M * Cin + 6 * M * 64)
+
+    @staticmethod
+    def k_conv(planes, wz, sc, sh, M, N, Ci, mesh, nvalid, act, res=None, ldr=0, out=None, ldo=0, out_planes=None, ldp=0):
+        """One CNO layer (rpb_cno_conv3x).  ``planes`` / ``out_planes``: int16 tensors or raw addresses (already at the first column);
+        ``res`` / ``out``: fp32 tensors, ``ops.Sub`` or raw addresses."""
+        _lib.call("rpb_cno_conv3x", _ptr(planes, I16), _ptr(wz, I16), _ptr(sc), _ptr(sh), _ptr(res), _ptr(out), _ptr(out_planes, I16), M, N, Ci,
+                  nvalid, int(act), ldr, ldo, ldp, *mesh, _stream(), label=f"cno_conv3x[N{N},Ci{Ci}]",
+                  nbytes=6 * M * Ci + (4 * M * nvalid if out is not None else 0) + (6 * M * nvalid if out_planes is not None else 0)
+                  + (4 * M * nvalid if res is not None else 0), flops=2 * M * N * 27 * Ci)
+
+    # ------------------------------------------------------------------ forward
+    def _forward_rows(self, x, B, mesh, keep=None):
+        """x [M][in_dim] fp32 -> [M][out_dim] fp32.  ``keep`` (a dict) receives the fp32 rows of the lift output, ``skip[0..2]`` and the
+        neck output (tests); the extra fp32 stores do not change any value."""
+        dev = x.device
+        M = x.shape[0]
+        prep = self._prep(dev)
+        want = keep is not None
+
+        def layer(name, src, dst=None, col=0, act=True, res=None, f32=False, nvalid=None):
+            """src: _Planes read whole; dst: _Planes written at column ``col``; returns the fp32 rows [M][nvalid] when asked for"""
+            s = prep[name]
+            assert src.ld == s["K"], name
+            nv = s["Co"] if nvalid is None else nvalid
+            out = torch.empty(M, nv, device=dev, dtype=torch.float32) if f32 else None
+            self.k_conv(src.ptr(), s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, nv, act, res=res, ldr=0 if res is None else res.shape[1],
+                        out=out, ldo=nv, out_planes=None if dst is None else dst.ptr(col), ldp=0 if dst is None else dst.ld)
+            return out
+
+        def planes(ld, written):
+            return _Planes(M, ld, dev, zero=written < ld)
+
+        def res_block(i, xp, xf, width, f32=False):
+            """res_nets[i] on (planes, fp32 rows) of its input -> (planes, fp32 rows or None) of x + BN(conv(L(BN(conv x))))"""
+            ld = max(width, 64)
+            hp, yp = planes(ld, width), planes(ld, width)
+            layer(f"res_nets.{i}.1", xp, hp)
+            yf = layer(f"res_nets.{i}.2", hp, yp, act=False, res=xf, f32=f32)
+            return yp, yf
+
+        ef = self.encoder_features
+        p0 = planes(64, 64)                                           # (the pack kernel writes the zero pad itself)
+        self.k_pack(x, p0.t, M, self.in_dim)
+        p1 = planes(64, 64)
+        layer("lift.0", p0, p1)
+        xp = planes(64, ef[0])
+        xf = layer("lift.1", p1, xp, act=False, f32=True)
+        if want:
+            keep["lift"] = xf
+        skip = []
+        for i in range(N_LAYERS):
+            sp, sf = res_block(i, xp, xf, ef[i], f32=want)
+            if want:
+                keep[f"skip{i}"] = sf
+            skip.append(sp)
+            nxt = planes(max(ef[i + 1], 64), ef[i + 1])
+            xf = layer(f"encoder.{i}", xp, nxt, f32=True)
+            xp = nxt
+        n_res = len(self.res_nets)
+        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
+            last = j == 5
+            xp, xf = res_block(n_res - 1 - j, xp, xf, ef[3], f32=not last or want)
+        if want:
+            keep["neck"] = xf
+        # decoder: cat(x, ED_expansion(skip)) is two producers of one plane buffer
+        a = planes(128, 128)
+        layer("ED_expansion.3", xp, a)
+        b = planes(128, 128)
+        layer("decoder_inv.0", a, b)
+        c1 = planes(128, 128)
+        layer("decoder.0", b, c1, col=0)                              # 64 channels -> columns 0..63
+        layer("ED_expansion.2", skip[2], c1, col=64)                  # 64 channels -> columns 64..127
+        b = planes(128, 128)
+        layer("decoder_inv.1", c1, b)
+        c2 = planes(64, 64)
+        layer("decoder.1", b, c2, col=0)                              # 32 -> columns 0..31
+        layer("ED_expansion.1", skip[1], c2, col=32)                  # 32 -> columns 32..63
+        b = planes(64, 64)
+        layer("decoder_inv.2", c2, b)
+        c3 = planes(64, 32)
+        layer("decoder.2", b, c3, col=0)                              # 16 -> columns 0..15
+        layer("ED_expansion.0", skip[0], c3, col=16)                  # 16 -> columns 16..31; 32..63 stay zero
+        d = planes(64, 64)
+        layer("project.0", c3, d)
+        return layer("project.1", d, act=False, f32=True)
+
+    def check_input(self, shape):
+        """The shapes ``forward`` takes: [B, T, H, W, in_dim] with in_dim < T."""
+        if len(shape) != 5 or shape[-1] != self.in_dim:
+            raise ValueError(f"CNO3d was built for inputs [B, T, H, W, {self.in_dim}], got {tuple(shape)}")
+        if not shape[-1] < shape[1]:
+            raise ValueError(f"CNO3d: input {tuple(shape)} has C >= T.  The reference permutes to channels-first only when C < T "
+                             "(cno.py:467) and otherwise convolves with T as the channel axis; this port requires C < T")
+
+    def forward(self, x, keep=None):
+        self._require_eval(x)
+        self._require_hip(x)
+        self.check_input(tuple(x.shape))
+        with torch.no_grad():
+            x = x.contiguous().float()
+            B, T, H, W, C = x.shape
+            out = self._forward_rows(x.view(B * T * H * W, C), B, (T, H, W), keep=keep)
+            if keep is not None:
+                for k in keep:
+                    keep[k] = keep[k].view(B, T, H, W, -1)
+            out = out.view(B, T, H, W, self.out_dim)
+            if self.out_dim_mult > 1:                                 # cno.py:519-520 on channels-last memory: a view, not a time-major split
+                out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
+            return out

@@ -57,7 +57,17 @@ def load_model(train_dataset, device="cpu", **kwargs):
         from .deeponet import DeepONet
         model = DeepONet(shape_in=input_shape, shape_out=output_shape, input_channels=input_shape[-1],       # load_model.py:132-143
                          output_channels=output_shape[-1], p=kwargs["p"], dropout_rate=kwargs["dropout_rate"], device=device).to(device)
+    elif model_name == "cno":
+        from .cno import CNO3d
+        if output_shape[0] > input_shape[0] and output_shape[0] % input_shape[0] == 0:                       # load_model.py:60-75
+            out_dim_mult = output_shape[0] // input_shape[0]
+        elif output_shape[0] == input_shape[0]:
+            out_dim_mult = 1
+        else:
+            raise ValueError(f"Output shape {output_shape[1]} is not a multiple of input shape {input_shape[1]}")
+        model = CNO3d(in_dim=input_shape[-1], out_dim=output_shape[-1], out_dim_mult=out_dim_mult, in_size=input_shape[2],
+                      N_layers=kwargs["N_layers"]).to(device)
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
-                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet)")
+                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno)")
     return model

@@ -1,0 +1,182 @@
+"""CNO3d host side (no GPU): the plain-torch fp64 restatement of the kernel-side pipeline (tests/cno_restatement.py) against the
+reference's vectors and intermediates (tests/golden/cno_small.npz, written by tests/golden/make_golden_cno.py), state_dict
+compatibility, the YAMLs and every refusal.
+
+The tolerance rule is in tests/cno_helpers.py."""
+import os
+import sys
+
+import pytest
+import torch
+import yaml
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cno_common as CC                           # noqa: E402
+import cno_restatement as R                       # noqa: E402
+from cno_helpers import CFG, GOLD, SCENARIOS, TRAIN_MSG, One, host_tol, new_model, rel, sd_of          # noqa: E402
+from realpdebench_amd.model import cno as M       # noqa: E402
+
+
+@pytest.mark.parametrize("case", list(CC.CASES))
+def test_restatement_matches_reference(case):
+    shape_in, shape_out, _ = CC.CASES[case]
+    x, y = CC.case_inputs(case)
+    keep = {}
+    with torch.no_grad():
+        out = R.forward(sd_of(case), x.double(), shape_out, keep=keep)
+    e = rel(out, GOLD[f"{case}_out"])
+    loss = float(((out - y) ** 2).mean())
+    el = abs(loss - float(GOLD[f"{case}_loss"])) / float(GOLD[f"{case}_loss"])
+    print(f"case {case}: out Rel-L2 {e:.2e} (tol {host_tol(case + '_out'):.1e}); loss rel {el:.2e} (tol {host_tol(case + '_loss'):.1e})")
+    assert tuple(out.shape[1:]) == shape_out
+    if case == "a":
+        for k in CC.INTERMEDIATES:
+            ei = rel(CC.inter_stored(keep[k]), GOLD[f"a_{k}"])
+            print(f"  {k}: {ei:.2e} (tol {host_tol('a_' + k):.1e})")
+            assert ei < host_tol(f"a_{k}"), k
+    assert e < host_tol(case + "_out")
+    assert el < host_tol(case + "_loss")
+
+
+@pytest.mark.parametrize("case", CC.ROLLOUT_CASES)
+def test_restatement_rollout_matches_reference(case):
+    """The 3-step rollout with the Gaussian normaliser (eval.py:305-321), restated: normalise, predict, de-normalise, append the
+    control channels of the raw input, normalise again."""
+    shape_in, shape_out, _ = CC.CASES[case]
+    sd = sd_of(case)
+    x = CC.case_inputs(case)[0].double()
+    mi, mt, si, st = (t.double() for t in CC.normalizer_stats(case))
+    co = shape_out[-1]
+    cur, preds = (x - mi) / si, []
+    with torch.no_grad():
+        for _ in range(CC.ROLLOUT_STEPS):
+            pr = R.forward(sd, cur, shape_out) * st + mt
+            if shape_in[-1] != co:
+                pr = torch.cat([pr, x[..., co:]], -1)
+            cur = (pr - mi) / si
+            preds.append(cur)
+    e = rel(torch.cat(preds, 1), GOLD[f"{case}_roll"])
+    print(f"case {case}: rollout Rel-L2 {e:.2e} (tol {host_tol(case + '_roll'):.1e})")
+    assert e < host_tol(case + "_roll")
+
+
+def test_folded_affine_and_padded_weights_are_the_restatements():
+    """``fold_affine`` (float64, rounded once) and ``padded_weight`` of the model against ``fold`` of the restatement, for a layer with
+    BatchNorm and pad channels (16 -> 16) and one without BatchNorm (64 -> 3)."""
+    m = new_model("a")
+    sd = sd_of("a")
+    m.load_state_dict(sd)
+    for name, (conv, bn) in (("res_nets.0.convolution1", (m.res_nets[0].convolution1, m.res_nets[0].batch_norm1)),
+                             ("project.convolution", (m.project.convolution, False))):
+        wp, sc, sh, Co = R.fold(sd, name, name.replace("convolution", "batch_norm") if bn else None, 64)
+        gsc, gsh = M.fold_affine(conv, bn, 64)
+        assert torch.equal(gsc, sc.float()) and torch.equal(gsh, sh.float()), name
+        assert not bool(gsc[Co:].any()) and not bool(gsh[Co:].any())
+        gw = M.padded_weight(conv, 64, 64)
+        assert torch.equal(gw.view(64, 3, 3, 3, 64).permute(0, 4, 1, 2, 3).double(), wp), name
+
+
+@pytest.mark.parametrize("case", list(CC.CASES))
+def test_state_dict_is_the_references(case):
+    sd = new_model(case).state_dict()
+    assert len(sd) == 232
+    assert [[k, list(v.shape), str(v.dtype)] for k, v in sd.items()] == CFG["state_dict"][case]
+    assert list(sd) == list(CC.state_shapes(*CC.CASES[case][:2]))
+    assert "decoder_inv.3.convolution.weight" in sd and "res_nets.8.batch_norm2.num_batches_tracked" in sd
+
+
+def test_reference_layout_round_trip():
+    m = new_model("c")
+    new = sd_of("c")
+    m.load_state_dict(new)
+    back = m.state_dict()
+    assert list(back) == list(new)
+    for k, v in new.items():
+        assert back[k].dtype == v.dtype and torch.equal(back[k], v), k
+
+
+@pytest.mark.parametrize("scenario", SCENARIOS)
+def test_yaml_builds_through_load_model(scenario):
+    from realpdebench_amd.model import load_model
+    with open(os.path.join(ROOT, "realpdebench_amd", "configs", scenario, "cno.yaml")) as fh:
+        cfg = yaml.safe_load(fh)
+    for k, v in CFG["model_keys"][scenario].items():
+        assert cfg[k] == v, (scenario, k)
+    shape_in, shape_out = tuple(cfg["shape_in"]), tuple(cfg["shape_out"])
+    assert list(shape_in) == CFG["native_shapes"][scenario]["shape_in"] and list(shape_out) == CFG["native_shapes"][scenario]["shape_out"]
+    m = load_model(One(shape_in, shape_out), **cfg)
+    assert isinstance(m, M.CNO3d) and m.in_dim == shape_in[-1] and m.out_dim == shape_out[-1] and m.out_dim_mult == 1
+    assert len(m.res_nets) == 9                      # the YAML's "N_res_neck: 8," is a string nobody reads: six neck blocks
+    assert len(m.state_dict()) == 232
+
+
+def test_load_model_out_dim_mult_rule():
+    from realpdebench_amd.model import load_model
+    m = load_model(One((4, 9, 7, 3), (8, 9, 7, 2)), model_name="cno", N_layers=3)
+    assert m.out_dim_mult == 2 and m.out_dim == 4 and m.project.convolution.out_channels == 4
+    with pytest.raises(ValueError, match="is not a multiple of input shape"):
+        load_model(One((4, 9, 7, 3), (6, 9, 7, 2)), model_name="cno", N_layers=3)
+    with pytest.raises(ValueError, match="cno"):
+        load_model(One((4, 9, 7, 3), (4, 9, 7, 3)), model_name="no_such_model")
+
+
+@pytest.mark.parametrize("kwargs,match", [
+    (dict(N_layers=2), "N_layers=2"),
+    (dict(activation="lrelu"), "activation='lrelu'"),
+    (dict(N_res_neck=8), "N_res_neck=8"),
+    (dict(batch_norm=False), "batch_norm=False"),
+    (dict(add_inv=False), "add_inv=False"),
+    (dict(channel_multiplier=16), "channel_multiplier=16"),
+    (dict(out_dim=33, out_dim_mult=2), "out_dim \\* out_dim_mult = 66"),
+    (dict(in_dim=65), "in_dim=65"),
+    (dict(N_layers=4, activation="lrelu", out_size=32), "N_layers=4.*activation='lrelu'.*out_size=32"),
+])
+def test_unsupported_configurations_are_refused_loudly(kwargs, match):
+    args = dict(in_dim=3, in_size=10, N_layers=3, out_dim=3)
+    args.update(kwargs)
+    with pytest.raises(NotImplementedError, match=match):
+        M.CNO3d(**args)
+
+
+def test_input_shape_rule():
+    m = new_model("a")
+    m.check_input((2, 6, 10, 12, 3))
+    with pytest.raises(ValueError, match="C >= T"):
+        m.check_input((2, 3, 10, 12, 3))
+    with pytest.raises(ValueError, match="built for inputs"):
+        m.check_input((2, 6, 10, 12, 4))
+    with pytest.raises(ValueError, match="built for inputs"):
+        m.check_input((6, 10, 12, 3))
+
+
+def test_backward_is_refused_without_a_gpu_too():
+    m = new_model("a")
+    x = torch.zeros(1, *CC.CASES["a"][0])
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        m.train_loss(x, x)
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        m(x.requires_grad_())
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        m.eval()(x.detach())                       # eval mode under grad mode with trainable parameters: no graph-less tensor comes back
+    from realpdebench_amd.trainer import make_trainer
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        make_trainer(m, lr=1e-3, num_update=10)
+    with torch.no_grad(), pytest.raises(RuntimeError, match="no CPU fallback"):
+        m(x.detach())
+
+
+def test_checkpoint_formats(tmp_path):
+    m = new_model("a")
+    m.load_state_dict(sd_of("a"))
+    torch.save(m.state_dict(), str(tmp_path / "w.pth"))
+    torch.save({"model_state_dict": m.state_dict(), "train_losses": [2.0], "val_losses": {}, "iteration": 3, "best_iteration": 2,
+                "best_val_loss": 0.25}, str(tmp_path / "full.pth"))
+    m2 = new_model("a")
+    meta = m2.load_checkpoint(str(tmp_path / "w.pth"), "cpu")
+    assert meta["iteration"] == 0 and meta["all_train_losses"] == []
+    assert torch.equal(m2.lift.convolution.weight, m.lift.convolution.weight)
+    meta = new_model("a").load_checkpoint(str(tmp_path / "full.pth"), "cpu")
+    assert meta["iteration"] == 3 and meta["best_val_loss"] == 0.25 and meta["all_train_losses"] == [2.0]
