@@ -741,6 +741,34 @@ int rpb_cno_conv3x(const void* planes, const void* Wz, const float* sc, const fl
                    long M, int N, int Ci, int nvalid, int act, int ldr, int ldo, int ldp, int Hc, int Wc, int Dc, void* stream);
 /*     the first layer's input: x [M][Cin] fp32 (1 <= Cin <= 64) -> planes P[3][M][64] with columns Cin..63 zero */
 int rpb_cno_pack(const float* x, void* planes, long M, int Cin, void* stream);
+/*     rpb_cno_conv3x: `res` may alias `out` element for element (same address, ldr == ldo): a lane reads res[m][n] and then writes
+ *     out[m][n], nobody else touches that element.  The training step accumulates data gradients into one buffer that way.
+ *
+ * CNO3d training step (opt-in: CNO3d.enable_training()) -- batch-statistics BatchNorm3d + LeakyReLU(0.2) + residual on rows [M][C],
+ * forward and backward (csrc/rpb_cno_train.hip; additions do not change RPB_ABI_VERSION).  C in {16, 32, 64, 128}; every row pointer arrives
+ * at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed summation order (two calls are bit-equal).
+ *     rpb_cno_bn_stats: part[rpb_cno_bn_rows()][2 C] (fp64) = per-workgroup (sum y, sum y^2) per channel of y [M][ld].
+ *     rpb_cno_bn_finish: the partials -> mean, rstd = 1 / sqrt(var + eps) (biased var), a = gamma rstd, b = beta - mean a, formed in fp64 and
+ *     rounded once; running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var M / (M - 1), in place.
+ *     rpb_cno_bn_act_fwd: v = fmaf(y, a, b); if (act) v = v > 0 ? v : 0.2 v; if (res) v += res[m * ldr + c] -> fp32 rows out[m * ldo + c]
+ *     and / or the three bf16 planes out_planes[pl * M * ldp + m * ldp + c] (bit-equal to rpb_split3 of v; ldp % 8 == 0).
+ *     rpb_cno_bn_act_bwd_stats: fp64 partials (as rpb_cno_bn_stats) of (sum dz, sum dz xhat), dz = gv (z > 0 ? 1 : 0.2) (gv without act),
+ *     z = fmaf(y, a, b) recomputed, xhat = (y - mean) rstd.  rpb_cno_sum64: sums[2 C] = the partials' rows added in a fixed order.
+ *     rpb_cno_bn_act_bwd_apply: dy = a (dz - sums[c] / M - xhat sums[C + c] / M) as fp32 rows dy[m * ldd + c] and / or bf16 planes, columns
+ *     C..Cpad-1 written as zero; dbeta[c] = sums[c], dgamma[c] = sums[C + c] (may be null).  has_bn = 0: dy = dz with the gate taken from the
+ *     sign of y itself (the saved LeakyReLU output); a, b, mean, rstd, sums unused. */
+int rpb_cno_bn_rows(void);
+int rpb_cno_bn_stats(const float* y, int ld, long M, int C, double* part, void* stream);
+int rpb_cno_bn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd, void* stream);
+int rpb_cno_bn_act_fwd(const float* y, int ldy, const float* a, const float* b, const float* res, int ldr, float* out, int ldo,
+                       void* out_planes, int ldp, long M, int C, int act, void* stream);
+int rpb_cno_bn_act_bwd_stats(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                             const float* rstd, long M, int C, int act, double* part, void* stream);
+int rpb_cno_sum64(const double* part, int rows, int C, double* sums, void* stream);
+int rpb_cno_bn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                             const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy, int ldd,
+                             void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
 
 #ifdef __cplusplus
 }

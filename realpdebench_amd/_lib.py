@@ -207,6 +207,13 @@ SIGNATURES = {
     "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),
     "rpb_cno_conv3x": (_I, "ppppppp" + "l" + "iiiiiii" + "iii" + "p"),
     "rpb_cno_pack": (_I, "pp" + "li" + "p"),
+    "rpb_cno_bn_rows": (_I, ""),
+    "rpb_cno_bn_stats": (_I, "p" + "ili" + "p" + "p"),
+    "rpb_cno_bn_finish": (_I, "p" + "ili" + "pppp" + "dd" + "pppp" + "p"),
+    "rpb_cno_bn_act_fwd": (_I, "pi" + "pp" + "pi" + "pi" + "pi" + "lii" + "p"),
+    "rpb_cno_bn_act_bwd_stats": (_I, "pi" + "pi" + "pppp" + "lii" + "p" + "p"),
+    "rpb_cno_sum64": (_I, "p" + "ii" + "p" + "p"),
+    "rpb_cno_bn_act_bwd_apply": (_I, "pi" + "pi" + "pppp" + "p" + "liiii" + "pi" + "pi" + "pp" + "p"),
 }
 
 _lib = None

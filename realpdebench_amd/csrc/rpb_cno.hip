@@ -7,6 +7,8 @@
 // out_planes[pl * M * ldp + m * ldp + n] -- bit-equal to rpb_split3 of the fp32 v.  Both pointers arrive at the first column the launch
 // owns: two producers write disjoint column ranges of one plane buffer and the next convolution reads it directly, so neither a
 // torch.cat nor an rpb_split3 pass exists in the model.  rpb_cno_pack writes the first layer's planes from the raw input.
+// `res` may alias `out` element for element (same address, ldr == ldo): the lane that reads res[m][n] is the one that writes out[m][n]
+// afterwards and no other lane touches that element -- the training step accumulates data gradients into one buffer that way.
 // The kernel is a second text next to conv3x_kernel on purpose (csrc/rpb_conv3h.hip:14-18 records what one shared body did to the
 // register counts); the main loop below is conv3x_kernel's, statement for statement.
 #include "rpb_mma.h"

@@ -5,9 +5,13 @@ model/load_model.py:60-75) for the reference's ``configs/*/cno.yaml``.
 ``activation='LeakyReLU'`` (cno.py:256), a six-block neck and no up- or down-sampling: the model is 35 ``Conv3d(3, padding=1)`` layers
 at full resolution, each followed by an eval BatchNorm3d, LeakyReLU(0.2), a residual add or a channel concat.
 
-Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training step is not built: every
-attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) and ``trainer.make_trainer`` refuses the model at
-construction.  BatchNorm3d uses its running statistics in every mode (no batch-statistics path exists).
+Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
+every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``), ``trainer.make_trainer`` refuses the model at
+construction and BatchNorm3d uses its running statistics in every mode.  ``enable_training()`` (``hip_training: true`` through
+``load_model``) opts an instance in: in ``train()`` mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction`` with
+batch-statistics BatchNorm (csrc/rpb_cno_train.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
+implicit GEMM for the seven ``EXACT_DGRAD`` layers) and the weight gradient is ``_common.wgrad``; ``eval()`` mode stays the code below,
+untouched.
 
 Pipeline (activations channels-last rows ``[B * T * H * W][C]``, mesh (T, H, W)):
   rpb_cno_pack      x [M][in_dim] -> bf16 planes P[3][M][64], columns in_dim..63 zero
@@ -25,13 +29,20 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import Sub, _p, _stream
-from ._common import EvalOnly
+from ..ops import Sub, _p, _stream, gemm_nt, split3
+from ..ops import add as ops_add
+from ._common import EvalOnly, HipFunction, wgrad
 from .model import Model
 
 I16 = torch.int16
 N_LAYERS = 3
 MAX_CH = 64                    # widest first-layer input / last-layer output: one 64-channel tile
+# Layers whose data gradient runs on the exact-fp32 implicit GEMM (rpb_gemm_nt) instead of the bf16x3 kernel: the ones that add into the
+# gradient of the neck's residual chain.  A BatchNorm shift gradient is a column sum of that gradient, which sees a per-channel bias of
+# the error sqrt(M) times stronger than its unbiased part; the bf16x3 kernel's error as a data gradient has such a bias (column mean 3-4
+# times the unbiased expectation, tests/test_gpu_cno_train_kernels.py prints it) and along the chain's identity path it adds up block by
+# block, where every other path goes through a BatchNorm backward that removes it.
+EXACT_DGRAD = frozenset(["ED_expansion.3"] + [f"res_nets.{i}.1" for i in range(3, 9)])
 # reference defaults of every keyword load_model never passes (cno.py:240-256)
 DEFAULTS = dict(N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001, filter_size=6, lrelu_upsampling=2,
                 half_width_mult=0.8, radial=False, batch_norm=True, out_size=1, expand_input=False, latent_lift_proj_dim=64, add_inv=True)
@@ -94,6 +105,22 @@ def padded_weight(conv, N, K):
     return wm.reshape(N, 27 * K)
 
 
+def flipped_weight(conv, N, K):
+    """Data-gradient weights of a Conv3d(Ci, Co, 3, padding=1): the same convolution run from the Co side with flipped, transposed taps,
+    Wd[ci][(kt, kh, kw)][co] = W[co][ci][2 - kt][2 - kh][2 - kw] -> [K][27 * N] fp32 (K >= Ci output rows, N >= Co input channels, zero on
+    the pad channels): what ``padded_weight`` is to the forward convolution."""
+    w = conv.weight.detach()
+    Co, Ci = w.shape[:2]
+    wd = torch.zeros(K, 27, N, dtype=torch.float32, device=w.device)
+    wd[:Ci, :, :Co] = w.flip(2, 3, 4).permute(1, 2, 3, 4, 0).reshape(Ci, 27, Co)
+    return wd.reshape(K, 27 * N)
+
+
+def weight_grad_view(dW, Co, Ci, N, K):
+    """dW [N][27 * K] (tap-major rows, the layout of ``padded_weight``) -> the parameter's [Co][Ci][3][3][3]."""
+    return dW.view(N, 3, 3, 3, K)[:Co, :, :, :, :Ci].permute(0, 4, 1, 2, 3).contiguous()
+
+
 class _Planes:
     """bf16 plane buffer P[3][M][ld] (int16 bit patterns).  ``zero``: the producers leave columns unwritten that a convolution reads."""
 
@@ -103,6 +130,19 @@ class _Planes:
 
     def ptr(self, col=0):
         return _p(self.t, I16) + 2 * col
+
+
+class _Act:
+    """One activation buffer of the training forward: fp32 rows [M][ld] (what a weight gradient reads) next to the bf16 planes (what the
+    next convolution reads).  ``zero``: as ``_Planes``."""
+
+    def __init__(self, M, ld, device, zero):
+        self.rows = (torch.zeros if zero else torch.empty)(M, ld, dtype=torch.float32, device=device)
+        self.planes = _Planes(M, ld, device, zero)
+        self.ld = ld
+
+    def at(self, col=0):
+        return Sub(self.rows, col)
 
 
 def _ptr(t, dtype=torch.float32):
@@ -115,6 +155,8 @@ def _ptr(t, dtype=torch.float32):
 class CNO3d(EvalOnly, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
     training_unavailable = EvalOnly.TRAIN_MSG.format("CNO", "CNO3d")
+    hip_training = False                            # enable_training() sets it on the instance
+    dp_unavailable = None                           # (enabled instances: why trainer.make_trainer refuses more than one rank)
 
     def __init__(self, in_dim, in_size, N_layers, N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001,
                  filter_size=6, lrelu_upsampling=2, half_width_mult=0.8, radial=False, batch_norm=True, out_dim=1, out_dim_mult=1,
@@ -154,6 +196,22 @@ class CNO3d(EvalOnly, Model):
         self.decoder = nn.ModuleList([CNOBlock3d(dec_in[i], dec_out[i]) for i in range(N_LAYERS)])
         self.decoder_inv = nn.ModuleList([CNOBlock3d(inv[i], inv[i]) for i in range(N_LAYERS + 1)])                  # [3] is never used
         self.res_nets = nn.Sequential(*([ResidualBlock3d(ef[l]) for l in range(N_LAYERS)] + [ResidualBlock3d(ef[N_LAYERS]) for _ in range(6)]))
+
+    # ------------------------------------------------------------------ the opt-in training step
+    def enable_training(self):
+        """Opt this instance into the HIP training step (batch-statistics BatchNorm; ``hip_training: true`` in a config).  Batch statistics
+        couple the samples of a step, so the instance stops declaring ``batch_independent`` (no micro-batching) and refuses more than one
+        rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for CNO is not built)."""
+        self.hip_training = True
+        self.training_unavailable = None
+        self.batch_independent = False
+        self.dp_unavailable = ("CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, "
+                               "run it on one rank")
+        return self
+
+    def _require_eval(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(type(self).training_unavailable)
 
     # ------------------------------------------------------------------ checkpoints
     def load_checkpoint(self, checkpoint_path, device="cpu"):
@@ -198,6 +256,25 @@ class CNO3d(EvalOnly, Model):
             prep[name] = dict(wz=wz, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
         return prep
 
+    def _prep_train(self, device):
+        """The training step's layouts: they depend on the convolutions alone (BatchNorm enters through the statistics kernels)."""
+        tensors = [t for conv, _ in self._convs().values() for t in (conv.weight, conv.bias)]
+        return self._layouts.get("prep_train", tensors, lambda: self._build_prep_train(device))
+
+    def _build_prep_train(self, device):
+        """Per layer: ``wz`` / ``sc`` = 1 / ``sh`` = bias of the forward convolution and ``wd``, the flipped, transposed taps of its data
+        gradient (``lift.0`` has none; fp32 rows [K][27 N] for the ``EXACT_DGRAD`` layers, rpb_conv3x_wprep planes otherwise); ``unit[n]``: the
+        (1, 0) affine of the bf16x3 data-gradient launches."""
+        prep = {"unit": {n: (torch.ones(n, device=device), torch.zeros(n, device=device)) for n in (64, 128)}}
+        for name, (conv, _) in self._convs().items():
+            Co, Ci = conv.weight.shape[:2]
+            N, K = max(Co, 64), max(Ci, 64)
+            sc, sh = fold_affine(conv, False, N)
+            wd = None if name == "lift.0" else flipped_weight(conv, N, K).to(device)
+            prep[name] = dict(wz=self.k_wprep(padded_weight(conv, N, K).to(device), N, K), sc=sc.to(device), sh=sh.to(device),
+                              wd=wd if wd is None or name in EXACT_DGRAD else self.k_wprep(wd, K, N), N=N, K=K, Co=Co, Ci=Ci)
+        return prep
+
     # ------------------------------------------------------------------ the kernels, one method per family (tests call these)
     @staticmethod
     def k_wprep(wm, N, K):
@@ -218,6 +295,207 @@ class CNO3d(EvalOnly, Model):
                   nvalid, int(act), ldr, ldo, ldp, *mesh, _stream(), label=f"cno_conv3x[N{N},Ci{Ci}]",
                   nbytes=6 * M * Ci + (4 * M * nvalid if out is not None else 0) + (6 * M * nvalid if out_planes is not None else 0)
                   + (4 * M * nvalid if res is not None else 0), flops=2 * M * N * 27 * Ci)
+
+    # the row passes of the training step (csrc/rpb_cno_train.hip); row operands: fp32 tensors, ``ops.Sub`` or raw addresses at the first column
+    @staticmethod
+    def k_bn_rows():
+        return _lib.query("rpb_cno_bn_rows")
+
+    @staticmethod
+    def k_bn_stats(y, ld, M, C, part):
+        _lib.call("rpb_cno_bn_stats", _ptr(y), ld, M, C, _ptr(part, torch.float64), _stream(), label="cno_bn_stats", nbytes=4 * M * C)
+
+    @staticmethod
+    def k_bn_finish(part, rows, M, C, gamma, beta, rmean, rvar, eps, momentum, a, b, mean, rstd):
+        _lib.call("rpb_cno_bn_finish", _ptr(part, torch.float64), rows, M, C, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
+                  float(momentum), _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _stream(), label="cno_bn_finish", nbytes=16 * rows * C)
+
+    @staticmethod
+    def k_bn_act_fwd(y, ldy, a, b, M, C, act, res=None, ldr=0, out=None, ldo=0, out_planes=None, ldp=0):
+        _lib.call("rpb_cno_bn_act_fwd", _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(res), ldr, _ptr(out), ldo, _ptr(out_planes, I16), ldp, M, C,
+                  int(act), _stream(), label="cno_bn_act_fwd",
+                  nbytes=M * C * (4 + (4 if res is not None else 0) + (4 if out is not None else 0) + (6 if out_planes is not None else 0)))
+
+    @staticmethod
+    def k_bn_act_bwd_stats(gv, ldg, y, ldy, a, b, mean, rstd, M, C, act, part):
+        _lib.call("rpb_cno_bn_act_bwd_stats", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), M, C, int(act),
+                  _ptr(part, torch.float64), _stream(), label="cno_bn_act_bwd_stats", nbytes=8 * M * C)
+
+    @staticmethod
+    def k_sum64(part, rows, C, sums):
+        _lib.call("rpb_cno_sum64", _ptr(part, torch.float64), rows, C, _ptr(sums, torch.float64), _stream(), label="cno_sum64",
+                  nbytes=16 * rows * C)
+
+    @staticmethod
+    def k_bn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=None, ldy=0, a=None, b=None, mean=None, rstd=None, sums=None, dy=None, ldd=0,
+                           dy_planes=None, ldp=0, dgamma=None, dbeta=None):
+        """``sums`` given: the BatchNorm form; otherwise the gate-only form (``y``: the saved LeakyReLU output)."""
+        _lib.call("rpb_cno_bn_act_bwd_apply", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(sums, torch.float64),
+                  M, C, Cpad, int(act), int(sums is not None), _ptr(dy), ldd, _ptr(dy_planes, I16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(),
+                  label="cno_bn_act_bwd_apply",
+                  nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))
+
+    # ------------------------------------------------------------------ the training step
+    def _train_rows(self, x, B, mesh, state):
+        """x [M][in_dim] fp32 -> [M][out_dim] fp32 with batch-statistics BatchNorm (the running statistics are updated).  The data flow is
+        ``_forward_rows``'s; a BatchNorm layer is the raw convolution (fp32 rows ``y``), the statistics and one row pass that writes fp32
+        rows and planes of ``v``.  ``state`` (a dict, or None) receives the tape the backward pass walks: per layer the buffers it read and
+        wrote, ``y`` and (a, b, mean, rstd)."""
+        dev, M = x.device, x.shape[0]
+        prep, convs, rows = self._prep_train(dev), self._convs(), self.k_bn_rows()
+        tape, touched, counters = [], [], []
+
+        def buf(ld, written):
+            return _Act(M, ld, dev, zero=written < ld)
+
+        def layer(name, src, dst=None, col=0, act=True, res=None):
+            s, (conv, bn) = prep[name], convs[name]
+            N, K, Co = s["N"], s["K"], s["Co"]
+            assert src.ld == K, name
+            rec = dict(name=name, src=src, dst=dst, col=col, act=act, res=res, y=None, ab=None, out=None)
+            tape.append(rec)
+            if bn is False:                                           # lift / project: today's fused launch
+                if dst is None:
+                    rec["out"] = torch.empty(M, Co, device=dev, dtype=torch.float32)
+                self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, Co, act, out=rec["out"] if dst is None else dst.at(col),
+                            ldo=Co if dst is None else dst.ld, out_planes=None if dst is None else dst.planes.ptr(col),
+                            ldp=0 if dst is None else dst.ld)
+                return rec["out"]
+            y = torch.empty(M, N, device=dev, dtype=torch.float32)
+            self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, N, 0, out=y, ldo=N)
+            part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
+            ab = torch.empty(4, Co, device=dev, dtype=torch.float32)  # a, b, mean, rstd
+            self.k_bn_stats(y, N, M, Co, part)
+            self.k_bn_finish(part, rows, M, Co, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, *ab)
+            self.k_bn_act_fwd(y, N, ab[0], ab[1], M, Co, act, res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
+                              out=dst.at(col), ldo=dst.ld, out_planes=dst.planes.ptr(col), ldp=dst.ld)
+            rec["y"], rec["ab"] = y, ab
+            touched.extend((bn.running_mean, bn.running_var))
+            counters.append(bn.num_batches_tracked)
+
+        def res_block(i, xa, width):
+            """res_nets[i]: x + BN(conv(L(BN(conv x))))"""
+            ld = max(width, 64)
+            h, ya = buf(ld, width), buf(ld, width)
+            layer(f"res_nets.{i}.1", xa, h)
+            layer(f"res_nets.{i}.2", h, ya, act=False, res=xa)
+            return ya
+
+        ef = self.encoder_features
+        p0 = buf(64, self.in_dim)
+        p0.rows[:, :self.in_dim] = x
+        self.k_pack(x, p0.planes.t, M, self.in_dim)
+        p1 = buf(64, 64)
+        layer("lift.0", p0, p1)
+        xa = buf(64, ef[0])
+        layer("lift.1", p1, xa, act=False)
+        skip = []
+        for i in range(N_LAYERS):
+            skip.append(res_block(i, xa, ef[i]))
+            nxt = buf(max(ef[i + 1], 64), ef[i + 1])
+            layer(f"encoder.{i}", xa, nxt)
+            xa = nxt
+        n_res = len(self.res_nets)
+        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
+            xa = res_block(n_res - 1 - j, xa, ef[3])
+        a = buf(128, 128)
+        layer("ED_expansion.3", xa, a)
+        b = buf(128, 128)
+        layer("decoder_inv.0", a, b)
+        c1 = buf(128, 128)
+        layer("decoder.0", b, c1, col=0)
+        layer("ED_expansion.2", skip[2], c1, col=64)
+        b = buf(128, 128)
+        layer("decoder_inv.1", c1, b)
+        c2 = buf(64, 64)
+        layer("decoder.1", b, c2, col=0)
+        layer("ED_expansion.1", skip[1], c2, col=32)
+        b = buf(64, 64)
+        layer("decoder_inv.2", c2, b)
+        c3 = buf(64, 32)
+        layer("decoder.2", b, c3, col=0)
+        layer("ED_expansion.0", skip[0], c3, col=16)
+        d = buf(64, 64)
+        layer("project.0", c3, d)
+        out = layer("project.1", d, act=False)
+        # the kernels wrote the running statistics through raw pointers: the layout cache is keyed on the version counters
+        for t in touched:
+            torch.autograd.graph.increment_version(t)
+        torch._foreach_add_(counters, 1)
+        if state is not None:
+            for rec in tape:                                          # the backward pass reads fp32 rows only
+                rec["src"].planes = None
+            state.update(tape=tape, M=M, mesh=mesh)
+        return out
+
+    @torch.no_grad()
+    def _forward_hip(self, x, state):
+        x = x.contiguous().float()
+        B, T, H, W, C = x.shape
+        out = self._train_rows(x.view(B * T * H * W, C), B, (T, H, W), state).view(B, T, H, W, self.out_dim)
+        if self.out_dim_mult > 1:                                     # (as in ``forward``: a view of the channels-last rows)
+            out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
+        return out
+
+    @torch.no_grad()
+    def _backward_hip(self, state, g_out, need_gx=False):
+        """{parameter: gradient} from dLoss/d(out): the tape in reverse.  Per layer: the BatchNorm + LeakyReLU backward row passes give
+        ``dy`` (fp32 rows for ``wgrad``, planes for the data gradient), ``wgrad`` gives (dW, db), rpb_cno_conv3x on the flipped taps adds
+        the data gradient into the gradient buffer of the layer's input (the first consumer writes it, later ones pass it as ``res``);
+        the ``EXACT_DGRAD`` layers take the exact-fp32 implicit GEMM on the fp32 rows instead.
+        A residual hands its gradient to the block input unchanged; a concat is two layers reading column ranges of one buffer.
+        ``state`` is only read: a second call gives bit-equal gradients."""
+        if need_gx:
+            raise NotImplementedError("CNO3d training computes no input gradient (no trainer asks for one)")
+        tape, M, mesh = state["tape"], state["M"], state["mesh"]
+        dev = g_out.device
+        prep, convs, rows = self._prep_train(dev), self._convs(), self.k_bn_rows()
+        g, grads = {}, {}                                             # id(_Act) -> fp32 [M][ld] gradient of that buffer
+        gpad = torch.zeros(M, 64, device=dev, dtype=torch.float32)
+        gpad[:, :self.out_dim] = g_out.reshape(M, self.out_dim)
+        for rec in reversed(tape):
+            name, src, dst, col, act = rec["name"], rec["src"], rec["dst"], rec["col"], rec["act"]
+            s, (conv, bn) = prep[name], convs[name]
+            N, K, Co, Ci = s["N"], s["K"], s["Co"], s["Ci"]
+            gt, ldg = (gpad, 64) if dst is None else (g[id(dst)], dst.ld)
+            gv = Sub(gt, col)
+            if rec["res"] is not None:                                # the residual passes gv on to the block input
+                k = id(rec["res"])
+                g[k] = ops_add(g[k], gt) if k in g else gt
+            need_dx, exact = s["wd"] is not None, name in EXACT_DGRAD
+            dyp = torch.empty(3 * M * N, device=dev, dtype=I16) if need_dx and not exact else None
+            if bn is not False:
+                y, (a, b, mean, rstd) = rec["y"], rec["ab"]
+                part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
+                sums = torch.empty(2 * Co, device=dev, dtype=torch.float64)
+                dgb = torch.empty(2, Co, device=dev, dtype=torch.float32)
+                dy = torch.empty(M, N, device=dev, dtype=torch.float32)
+                self.k_bn_act_bwd_stats(gv, ldg, y, N, a, b, mean, rstd, M, Co, act, part)
+                self.k_sum64(part, rows, Co, sums)
+                self.k_bn_act_bwd_apply(gv, ldg, M, Co, N, act, y=y, ldy=N, a=a, b=b, mean=mean, rstd=rstd, sums=sums, dy=dy, ldd=N,
+                                        dy_planes=dyp, ldp=N, dgamma=dgb[0], dbeta=dgb[1])
+                grads[bn.weight], grads[bn.bias] = dgb[0], dgb[1]
+            elif act:                                                 # lift.0 / project.0: the gate from the sign of the saved v
+                dy = torch.empty(M, N, device=dev, dtype=torch.float32)
+                self.k_bn_act_bwd_apply(gv, ldg, M, Co, N, 1, y=dst.rows, ldy=dst.ld, dy=dy, ldd=N, dy_planes=dyp, ldp=N)
+            else:                                                     # lift.1 / project.1: dy = gv, a 64-wide buffer with zero pad columns
+                assert col == 0 and ldg == N, name
+                dy = gt
+                split3(dy, dyp, M, N)
+            dW, db = wgrad(dy, src.rows, M, N, 27 * K, ldg=N, lda=K, conv=mesh)
+            grads[conv.weight], grads[conv.bias] = weight_grad_view(dW, Co, Ci, N, K), db[:Co]
+            k = id(src)
+            if need_dx and exact:                                     # exact-fp32 implicit GEMM on the fp32 rows; a new buffer (no aliasing)
+                gs = torch.empty(M, K, device=dev, dtype=torch.float32)
+                gemm_nt(dy, s["wd"], gs, M, K, 27 * N, conv=mesh, residual=g.get(k))
+                g[k] = gs
+            elif need_dx:
+                one, zero = prep["unit"][K]
+                first = k not in g
+                gs = torch.empty(M, K, device=dev, dtype=torch.float32) if first else g[k]
+                self.k_conv(dyp, s["wd"], one, zero, M, K, N, mesh, K, 0, res=None if first else gs, ldr=K, out=gs, ldo=K)
+                g[k] = gs
+        return grads
 
     # ------------------------------------------------------------------ forward
     def _forward_rows(self, x, B, mesh, keep=None):
@@ -304,6 +582,16 @@ class CNO3d(EvalOnly, Model):
                              "(cno.py:467) and otherwise convolves with T as the channel axis; this port requires C < T")
 
     def forward(self, x, keep=None):
+        if self.hip_training and self.training:                       # the opt-in training step: batch statistics, through HipFunction
+            if keep is not None:
+                raise ValueError("keep= belongs to the evaluation forward")
+            self._require_hip(x)
+            self.check_input(tuple(x.shape))
+            if not torch.is_grad_enabled():
+                return self._forward_hip(x, None)
+            if x.requires_grad:
+                raise NotImplementedError("CNO3d training computes no input gradient (no trainer asks for one)")
+            return HipFunction.apply(x, self, *self.parameters())
         self._require_eval(x)
         self._require_hip(x)
         self.check_input(tuple(x.shape))
@@ -318,3 +606,11 @@ class CNO3d(EvalOnly, Model):
             if self.out_dim_mult > 1:                                 # cno.py:519-520 on channels-last memory: a view, not a time-major split
                 out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
             return out
+
+    def train_loss(self, input, target):
+        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
+        if self.hip_training and self.training:
+            return Model.train_loss(self, input, target)
+        if torch.is_grad_enabled():
+            raise NotImplementedError(type(self).training_unavailable)
+        return Model.train_loss(self, input, target)

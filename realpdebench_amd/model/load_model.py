@@ -67,6 +67,8 @@ def load_model(train_dataset, device="cpu", **kwargs):
             raise ValueError(f"Output shape {output_shape[1]} is not a multiple of input shape {input_shape[1]}")
         model = CNO3d(in_dim=input_shape[-1], out_dim=output_shape[-1], out_dim_mult=out_dim_mult, in_size=input_shape[2],
                       N_layers=kwargs["N_layers"]).to(device)
+        if kwargs.get("hip_training"):                        # opt-in: the HIP training step with batch-statistics BatchNorm
+            model.enable_training()
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
                          "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno)")

@@ -361,6 +361,9 @@ def make_trainer(model, lr, num_update, scheduler="cosine", step_size=1000, clip
     """Fused trainer for FNO3d (one flat arena built into the model), ArenaTrainer for the nn.Parameter models."""
     if getattr(model, "training_unavailable", None):          # eval-only models (MWT3d) stop here, not inside a step
         raise NotImplementedError(model.training_unavailable)
+    if (getattr(model, "dp_unavailable", None) and torch.distributed.is_available() and torch.distributed.is_initialized()
+            and torch.distributed.get_world_size() > 1):      # per-rank batch statistics would break "N ranks == 1 rank"
+        raise NotImplementedError(model.dp_unavailable)
     if hasattr(model, "flat"):
         if torch.distributed.is_available() and torch.distributed.is_initialized() and model.dp is None:
             from .dp import DataParallel
