@@ -20,12 +20,14 @@ Guard contents.
   that the kernel forms with a select, a load into a register that is never used) leaves no trace; only the bounds of reads whose value
   reaches an output are tested.  Out-of-range WRITES are always seen.
 * Output operands and their guards hold the sentinel bit pattern of the DPOT kernel tests (``-3.0e30``).
+* In/out operands (``inout``: preloaded, then written -- the ``accumulate`` paths) hold the given tensor; their guards hold the sentinel.
 
 ``check()`` -- after the call and a synchronise -- asserts that
 1. every guard, and every input operand, is bit-identical to what was written;
 2. no output element still holds the sentinel, except the elements the test named (``unwritten=``: elements the kernel is documented not to
    write, e.g. the other columns of a column-range output) -- and those still hold exactly the sentinel;
-3. no output element is a NaN.
+3. no output element is a NaN;
+4. for an in/out operand: its guards are intact and it holds no NaN (it was preloaded, so "never written" cannot be asked of it).
 
 The arena works on CPU tensors as well; there ``Operand.op`` is the view itself, so that plain torch code can stand in for a kernel
 (tests/test_unet_kernels_host.py proves with such fakes that each of the assertions above trips).
@@ -103,6 +105,17 @@ class Arena:
         self.items.append(o)
         return o
 
+    def inout(self, t, name=None, ld=None, guard=None):
+        """an operand the kernel reads AND writes (``out += ...``): the body holds ``t``, the guards the sentinel, as for an output.
+        ``check()`` asserts that the guards are intact and that the body holds no NaN.  It can make no never-written assertion, and
+        needs none: a cell the kernel skips keeps its preloaded value, so its error against ``reference + t`` is the size of the
+        result itself, which the max-error measure of the verdict catches (tests/test_mwt_kernels_host.py proves that with a fake)."""
+        assert self.flat is None, "operands are declared before the first .op"
+        assert self.dtype.is_floating_point, "in/out operands are floating point (the sentinel is a float)"
+        o = Operand(self, name or f"inout{len(self.items)}", "inout", t.shape, ld, guard, t.detach().to("cpu", self.dtype).reshape(-1), None)
+        self.items.append(o)
+        return o
+
     def _seal(self):
         if self.flat is None:
             pos, spans = 0, []
@@ -116,7 +129,7 @@ class Arena:
             for o in spans:                                        # guard | operand | (round-up) | guard, in the operand's own colour
                 end = _up4(o.off + o.n) + o.guard
                 host[pos:end] = self.fill if o.kind == "in" else SENTINEL
-                if o.kind == "in":
+                if o.kind != "out":
                     host[o.off:o.off + o.n] = o.data
                     o.data = None
                 pos = end
@@ -150,6 +163,10 @@ class Arena:
                 bad = (body != ebody).nonzero()
                 assert not bad.numel(), (f"input operand '{o.name}' {o.shape} was written: {bad.numel()} element(s), the first at flat "
                                          f"index {int(bad[0])}")
+            elif o.kind == "inout":
+                nan = torch.isnan(h[o.off:o.off + o.n]).nonzero()
+                assert not nan.numel(), (f"in/out operand '{o.name}' {o.shape}: {nan.numel()} NaN(s) -- a read outside an input operand "
+                                         f"reached the result (first at flat index {int(nan[0])})")
             else:
                 val = h[o.off:o.off + o.n]
                 still = body == ebody                               # the interior started as all-sentinel

@@ -64,6 +64,56 @@ def spectral(d, weights, low, lob, plan):
     return F.linear(F.relu(v), low, lob)
 
 
+# ---- ``spectral`` once more, one function per launch of MWT3d.k_spectral (rpb_mwt_axis x 3, rpb_mwt_modes, rpb_mwt_axis x 2,
+#      rpb_mwt_spec_out) on the flat buffers the kernels exchange; tests/test_mwt_kernels_host.py asserts that they compose to it
+def axis(inp, M, outer, inner):
+    """out[outer][o][inner] = sum_k M[o][k] in[outer][k][inner]"""
+    O, K = M.shape
+    return torch.einsum("ok,ukn->uon", M.to(inp.dtype), inp.reshape(outer, K, inner)).reshape(-1)
+
+
+def modes(X, Wt, tab, B, NB):
+    """X [B][2 (re|im)][NB][36] planar, Wt [weight bins][36 in][36 out][2], tab [NB] -> Y like X"""
+    X = X.reshape(B, 2, NB, 36)
+    W = Wt.to(X.dtype)[tab.long()]                                # [NB][in][out][2]
+    a, b, wr, wi = X[:, 0], X[:, 1], W[..., 0], W[..., 1]
+    yr = torch.einsum("bni,nio->bno", a, wr) - torch.einsum("bni,nio->bno", b, wi)
+    yi = torch.einsum("bni,nio->bno", a, wi) + torch.einsum("bni,nio->bno", b, wr)
+    return torch.stack([yr, yi], 1).reshape(-1)
+
+
+def spec_out(S, GT, loT, lb, lines, T):
+    """S [lines][K2][36], GT [T][K2], loT [36 in][36 out] -> [lines * T][36]"""
+    dt = S.dtype
+    v = torch.einsum("tk,lkc->ltc", GT.to(dt), S.reshape(lines, GT.shape[1], 36))
+    return (F.relu(v) @ loT.to(dt) + lb.to(dt)).reshape(lines * T, 36)
+
+
+def spectral_stage_calls(B, plan):
+    """(matrix name, outer, inner) of the five rpb_mwt_axis launches of MWT3d.k_spectral, in order (rpb_mwt_modes runs after the third)"""
+    Nx, Ny, m, KY, C = plan.Nx, plan.Ny, plan.modes, plan.KY, 36
+    return [("FT", B * Nx * Ny, C), ("FY", B * Nx, m * C), ("FX", B, KY * m * C), ("GX", B, KY * m * C), ("GY", B * Nx, m * C)]
+
+
+def spectral_by_stages(d, Wt, loT, lb, plan, keep=None):
+    """``spectral`` as the composition of the stage functions; ``keep`` (a list) receives every stage's output"""
+    B, Nx, Ny, T, _ = d.shape
+    calls = spectral_stage_calls(B, plan)
+    y = d.reshape(-1)
+    for i, (name, outer, inner) in enumerate(calls):
+        if i == 3:
+            y = modes(y, Wt, plan.tab, B, plan.KX * plan.KY * plan.modes)
+            if keep is not None:
+                keep.append(y)
+        y = axis(y, getattr(plan, name), outer, inner)
+        if keep is not None:
+            keep.append(y)
+    out = spec_out(y, plan.GT, loT, lb, B * Nx * Ny, T).reshape(B, Nx, Ny, T, 36)
+    if keep is not None:
+        keep.append(out)
+    return out
+
+
 def head(x, w0, b0, w1, b1, shape_in, shape_out):
     B, Nx, Ny, T, _ = x.shape
     y = F.linear(F.relu(F.linear(x, w0, b0)), w1, b1)

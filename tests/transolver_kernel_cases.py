@@ -12,6 +12,7 @@ The temperatures put one head below the clamp (0.05), one above it (7.0) and the
 import torch
 
 import transolver_restatement as R
+from kernel_verdict import verdict
 from unet_kernel_cases import (BADLY_CONDITIONED, F32, F64, MEASURES, MI355X_CUS, Case, _gen, _rn,      # noqa: F401
                                bound_of, measures)
 
@@ -149,11 +150,4 @@ def judge_dtau(name, got, r64, r32, existing=None):
 
 
 def _verdict(name, figures, existing):
-    rows = []
-    for kind, e32, ek in figures:
-        bound = existing if existing is not None else bound_of(e32)
-        print(f"[transolver-kernels] {name} {kind}: e32 {e32:.3e} kernel {ek:.3e} bound {bound:.3e}")
-        rows.append((kind, e32, ek, bound))
-    for kind, e32, ek, bound in rows:
-        assert 8 * e32 <= BADLY_CONDITIONED, f"{name}: badly conditioned inputs, the fp32 restatement itself is off by {e32:.3e} ({kind})"
-        assert ek <= bound, f"{name} {kind}: kernel error {ek:.3e} > {bound:.3e} (fp32 restatement: {e32:.3e})"
+    verdict("transolver-kernels", name, figures, existing)          # tests/kernel_verdict.py, shared with the MWT kernel tests
