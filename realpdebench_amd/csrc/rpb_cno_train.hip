@@ -20,37 +20,6 @@
 
 #define CT_THREADS 256
 
-// the split of rpb_split3 (csrc/rpb_conv3x.hip): round to nearest even at every level, hi + mid + lo == x exactly
-__device__ __forceinline__ unsigned ct_bf16_rne(float x) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void ct_split3(float x, unsigned& h, unsigned& m, unsigned& l) {
-    h = ct_bf16_rne(x);
-    const float r1 = x - __builtin_bit_cast(float, h << 16);          // exact
-    m = ct_bf16_rne(r1);
-    const float r2 = r1 - __builtin_bit_cast(float, m << 16);         // exact
-    l = ct_bf16_rne(r2);
-}
-// 8 consecutive channels of one token -> 16 B per plane at P + o, P + o + pstride, P + o + 2 pstride
-__device__ __forceinline__ void ct_store_planes(uint16_t* P, long o, long pstride, f32x4 v0, f32x4 v1) {
-    unsigned h[8], md[8], lo[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        ct_split3(v0[i], h[i], md[i], lo[i]);
-        ct_split3(v1[i], h[4 + i], md[4 + i], lo[4 + i]);
-    }
-    u32x4 oh, om, ol;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        oh[q] = h[2 * q] | (h[2 * q + 1] << 16);
-        om[q] = md[2 * q] | (md[2 * q + 1] << 16);
-        ol[q] = lo[2 * q] | (lo[2 * q + 1] << 16);
-    }
-    *reinterpret_cast<u32x4*>(P + o) = oh;
-    *reinterpret_cast<u32x4*>(P + o + pstride) = om;
-    *reinterpret_cast<u32x4*>(P + o + 2 * pstride) = ol;
-}
 __device__ __forceinline__ float ct_lrelu(float z) { return z > 0.f ? z : 0.2f * z; }
 
 // ---------------------------------------------------------------------------------- per-channel fp64 partial sums
@@ -239,7 +208,7 @@ __global__ __launch_bounds__(CT_THREADS) void ct_act_fwd_kernel(const float* __r
             *reinterpret_cast<f32x4*>(out + m * ldo + c0) = v0;
             *reinterpret_cast<f32x4*>(out + m * ldo + c0 + 4) = v1;
         }
-        if (op) ct_store_planes(op, m * ldp + c0, pstride, v0, v1);
+        if (op) split3_store(op, m * ldp + c0, pstride, v0, v1);
     }
 }
 
@@ -319,7 +288,7 @@ __global__ __launch_bounds__(CT_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) {
             *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c0) = d[0];
             *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c0 + 4) = d[1];
         }
-        if (p.dp) ct_store_planes(p.dp, m * p.ldp + c0, pstride, d[0], d[1]);
+        if (p.dp) split3_store(p.dp, m * p.ldp + c0, pstride, d[0], d[1]);
     }
 }
 

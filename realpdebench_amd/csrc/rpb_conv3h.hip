@@ -16,13 +16,9 @@
 // the kernel's launch bounds, and every instance came out differently (other loop duplication, 1.5x the v_accvgpr moves); as one
 // text included into both kernels the bf16x3 instances kept their code and speed, but conv3x_f16x2_kernel<1> went from
 // 368 VGPRs + 128 AGPRs to 496 + 256 and from 1.85 to 2.15 ms at the U-Net 64 -> 64 shape.  Outputs were bit-equal in both forms.
+// The bf16x3 loop is shared in that second form since: csrc/rpb_conv3x_loop.h is the one text of conv3x_kernel and cno_conv3x_kernel.
 #include "rpb_mma.h"
 #include <stdlib.h>
-
-template <int V>
-struct ICh {
-    static constexpr int value = V;
-};
 
 #define CH_BM 128
 #define CH_ROWS (CH_BM + 2)
@@ -308,7 +304,7 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     };
     auto stage_store = [&](u32x4* dst) __attribute__((always_inline)) { CH_FOR9(CH_STORE) };
     bload(wbase + (long)kp * wchunk, bc);                               // (g 0, c 0, s = kp, kw 0)
-    stage_load(0, 0, ICh<0>{}, ICh<NLD>{});
+    stage_load(0, 0, IC<0>{}, IC<NLD>{});
     stage_store(lds4h);
     __syncthreads();
     int buf = 0;
@@ -327,19 +323,19 @@ __global__ __launch_bounds__(256, 1) void conv3x_f16x2_kernel(Conv3hArgs a) {
     if constexpr (SI < SPS) {                                                                                  \
         const int s = kp + SI * KS;                                                                            \
         const uint16_t* w0 = wbase + (long)(g * 3) * wtap + (long)(c * 4 + s) * wchunk;                        \
-        bload(w0 + wtap, bsel(ICh<(SI * 3 + 1) & 1>{}));                                                       \
-        if (more) stage_load(gn, cn, ICh<(SI * 3 + 0) * NLD / NST>{}, ICh<(SI * 3 + 1) * NLD / NST>{});        \
+        bload(w0 + wtap, bsel(IC<(SI * 3 + 1) & 1>{}));                                                        \
+        if (more) stage_load(gn, cn, IC<(SI * 3 + 0) * NLD / NST>{}, IC<(SI * 3 + 1) * NLD / NST>{});          \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
-        tap_step(s, 0, true, bsel(ICh<(SI * 3 + 0) & 1>{}));                                                   \
-        bload(w0 + 2 * wtap, bsel(ICh<(SI * 3 + 2) & 1>{}));                                                   \
-        if (more) stage_load(gn, cn, ICh<(SI * 3 + 1) * NLD / NST>{}, ICh<(SI * 3 + 2) * NLD / NST>{});        \
+        tap_step(s, 0, true, bsel(IC<(SI * 3 + 0) & 1>{}));                                                    \
+        bload(w0 + 2 * wtap, bsel(IC<(SI * 3 + 2) & 1>{}));                                                    \
+        if (more) stage_load(gn, cn, IC<(SI * 3 + 1) * NLD / NST>{}, IC<(SI * 3 + 2) * NLD / NST>{});          \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
-        tap_step(s, 1, true, bsel(ICh<(SI * 3 + 1) & 1>{}));                                                   \
-        if (SI + 1 < SPS) bload(w0 + (long)KS * wchunk, bsel(ICh<(SI * 3 + 3) & 1>{}));                        \
-        else if (more) bload(wbase + (long)(gn * 3) * wtap + (long)(cn * 4 + kp) * wchunk, bsel(ICh<(SI * 3 + 3) & 1>{})); \
-        if (more) stage_load(gn, cn, ICh<(SI * 3 + 2) * NLD / NST>{}, ICh<(SI * 3 + 3) * NLD / NST>{});        \
+        tap_step(s, 1, true, bsel(IC<(SI * 3 + 1) & 1>{}));                                                    \
+        if (SI + 1 < SPS) bload(w0 + (long)KS * wchunk, bsel(IC<(SI * 3 + 3) & 1>{}));                         \
+        else if (more) bload(wbase + (long)(gn * 3) * wtap + (long)(cn * 4 + kp) * wchunk, bsel(IC<(SI * 3 + 3) & 1>{}));  \
+        if (more) stage_load(gn, cn, IC<(SI * 3 + 2) * NLD / NST>{}, IC<(SI * 3 + 3) * NLD / NST>{});          \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
-        tap_step(s, 2, SI + 1 < SPS, bsel(ICh<(SI * 3 + 2) & 1>{}));                                           \
+        tap_step(s, 2, SI + 1 < SPS, bsel(IC<(SI * 3 + 2) & 1>{}));                                            \
     }
             CH_SI_BLOCK(0) CH_SI_BLOCK(1) CH_SI_BLOCK(2) CH_SI_BLOCK(3)
             if constexpr (NST & 1) {                                    // odd step count (N = 64): the next stage's first B set is in bn

@@ -9,8 +9,12 @@
 //   two fp16 planes    x = hi + lo to one fp32 unit in the last place (11 + 11 significand bits and the sign of lo), three products
 //                      hi*lo + lo*hi + hi*hi, dropped term <= 2^-22 |a b| -- the grade of "3xTF32", the opt-in "f16x2" eval arithmetic
 //                      (split8h, mfma16h / mfma32h).
-// (Not here, because they only look similar: split3 / bf16_rne of rpb_conv3x.hip -- integer rounding of single values in a memory-bound
-// pass -- and split2h of rpb_conv3h.hip -- scalar, scaled by ldexpf.)
+//   the stored planes  of the 3x3x3 convolutions (rpb_split3, rpb_conv3x_wprep, rpb_split3t, the CNO plane outputs): bf16_rne / split3 /
+//                      split3_store below round single values to nearest even in INTEGER arithmetic.  It is a separate primitive from
+//                      rpb_split_pair_rne / split8_rne on purpose: the hardware conversion of those keeps a NaN a NaN where the integer form
+//                      rounds its payload like any other bit pattern, and every producer of a plane buffer has to give the same bits
+//                      (rpb_cno_conv3x promises the planes rpb_split3 would have written).  One definition enforces that.
+// (Not here, because it only looks similar: split2h of rpb_conv3h.hip -- scalar, scaled by ldexpf.)
 #pragma once
 #include "rpb_common.h"
 
@@ -21,6 +25,16 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector: selects stay in registers (HIP's uint4 struct did not)
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// a compile-time integer as a value: the argument through which a lambda of a hand-pipelined loop selects a NAMED register
+template <int V>
+struct IC {
+    static constexpr int value = V;
+};
+// the token tile of the bf16x3 3x3x3 convolutions (csrc/rpb_conv3x_loop.h and the launchers of its two kernels): 128 output tokens and the
+// rows of their w neighbours
+#define CX_BM 128
+#define CX_ROWS (CX_BM + 2)
 
 // ---------------------------------------------------------------------------------- 128-bit (64-bit) buffer accesses
 // AUX: the cache policy of the access (the aux operand of raw_buffer_load / _store: RPB_STREAM_AUX for a streamed tensor, 0 = default for
@@ -135,6 +149,40 @@ __device__ __forceinline__ void split8_rne(f32x4 v0, f32x4 v1, u32x4& h, u32x4& 
     h = u32x4{hh[0], hh[1], hh[2], hh[3]};
     m = u32x4{mm[0], mm[1], mm[2], mm[3]};
     l = u32x4{ll[0], ll[1], ll[2], ll[3]};
+}
+
+// ---------------------------------------------------------------------------------- the stored planes (integer RNE)
+// round-to-nearest-even bf16 of x (as the upper 16 bits of an fp32)
+__device__ __forceinline__ unsigned bf16_rne(float x) {
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+// round to nearest even at every level, hi + mid + lo == x exactly
+__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
+    h = bf16_rne(x);
+    const float r1 = x - __builtin_bit_cast(float, h << 16);          // exact
+    m = bf16_rne(r1);
+    const float r2 = r1 - __builtin_bit_cast(float, m << 16);         // exact
+    l = bf16_rne(r2);
+}
+// 8 consecutive channels of one token -> 16 B per plane at P + o, P + o + pstride, P + o + 2 pstride
+__device__ __forceinline__ void split3_store(uint16_t* P, long o, long pstride, f32x4 v0, f32x4 v1) {
+    unsigned h[8], md[8], lo[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        split3(v0[i], h[i], md[i], lo[i]);
+        split3(v1[i], h[4 + i], md[4 + i], lo[4 + i]);
+    }
+    u32x4 oh, om, ol;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        oh[q] = h[2 * q] | (h[2 * q + 1] << 16);
+        om[q] = md[2 * q] | (md[2 * q + 1] << 16);
+        ol[q] = lo[2 * q] | (lo[2 * q + 1] << 16);
+    }
+    *reinterpret_cast<u32x4*>(P + o) = oh;
+    *reinterpret_cast<u32x4*>(P + o + pstride) = om;
+    *reinterpret_cast<u32x4*>(P + o + 2 * pstride) = ol;
 }
 
 // v_mfma_f32_16x16x32_bf16: A lane (m = l & 15, kg = l >> 4) holds k = 8 kg + e; D register r of lane (n, hg) is row 4 hg + r, column n

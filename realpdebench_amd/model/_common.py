@@ -1,6 +1,6 @@
 """Plumbing the models share between their parameter trees and the C ABI: the autograd glue (``HipFunction``), the weight-gradient
-finish (``wgrad``, ``colsum``, ``sum_rows``), the cache of kernel-side layouts (``LayoutCache``) and the base of the models whose
-training step is not built (``EvalOnly``)."""
+finish (``wgrad``, ``colsum``, ``sum_rows``), the weight matrix of a padded 3x3x3 convolution (``padded_weight``), the cache of
+kernel-side layouts (``LayoutCache``) and the base of the models whose training step is not built (``EvalOnly``)."""
 import torch
 
 from .. import ops
@@ -83,6 +83,15 @@ def colsum(x, M, N, deferrable=False):
         ops.colsum(ops.Sub(x, c0), part, M, chunk, ld=N)
         ops.reduce_partials(part, rows, chunk, out_f32=ops.Sub(out, c0), deferrable=deferrable)
     return out
+
+
+def padded_weight(conv, N, K):
+    """Conv3d weight [Co][Ci][3][3][3] -> [N][27 * K] fp32, tap-major and channel-minor rows, zero rows / columns on the pad channels."""
+    w = conv.weight.detach()
+    Co, Ci = w.shape[:2]
+    wm = torch.zeros(N, 27, K, dtype=torch.float32, device=w.device)
+    wm[:Co, :, :Ci] = w.permute(0, 2, 3, 4, 1).reshape(Co, 27, Ci)
+    return wm.reshape(N, 27 * K)
 
 
 class LayoutCache:

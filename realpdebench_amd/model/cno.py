@@ -29,9 +29,9 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import Sub, _p, _stream, gemm_nt, split3
+from ..ops import Sub, _p, _stream, conv3x_wprep, gemm_nt, split3
 from ..ops import add as ops_add
-from ._common import EvalOnly, HipFunction, wgrad
+from ._common import EvalOnly, HipFunction, padded_weight, wgrad
 from .model import Model
 
 I16 = torch.int16
@@ -94,15 +94,6 @@ def fold_affine(conv, bn, N):
     sc, sh = torch.zeros(N, dtype=torch.float32, device=bias.device), torch.zeros(N, dtype=torch.float32, device=bias.device)
     sc[:Co], sh[:Co] = sc64.float(), sh64.float()
     return sc, sh
-
-
-def padded_weight(conv, N, K):
-    """Conv3d weight [Co][Ci][3][3][3] -> [N][27 * K] fp32, tap-major and channel-minor rows, zero rows / columns on the pad channels."""
-    w = conv.weight.detach()
-    Co, Ci = w.shape[:2]
-    wm = torch.zeros(N, 27, K, dtype=torch.float32, device=w.device)
-    wm[:Co, :, :Ci] = w.permute(0, 2, 3, 4, 1).reshape(Co, 27, Ci)
-    return wm.reshape(N, 27 * K)
 
 
 def flipped_weight(conv, N, K):
@@ -279,7 +270,7 @@ class CNO3d(EvalOnly, Model):
     @staticmethod
     def k_wprep(wm, N, K):
         wz = torch.empty(3 * N * 27 * K, device=wm.device, dtype=I16)
-        _lib.call("rpb_conv3x_wprep", _p(wm), _p(wz, I16), N, K, _stream(), label="conv3x_wprep", nbytes=10 * N * 27 * K)
+        conv3x_wprep(wm, wz, N, K)
         return wz
 
     @staticmethod

@@ -26,8 +26,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import _p, _stream
-from ._common import EvalOnly
+from ..ops import _p, _stream, conv3x_wprep
+from ._common import EvalOnly, padded_weight
 from .model import Model
 
 I16 = torch.int16
@@ -154,24 +154,19 @@ class DeepONet(EvalOnly, Model):
         prep = {}
         for i in range(4):
             conv, bn = getattr(self.branch, f"conv{i + 1}")[:2]
-            w = conv.weight.detach()
-            Co, Ci = w.shape[:2]
-            wt = w.permute(0, 2, 3, 4, 1)                                         # [Co][kt][kh][kw][Ci]: tap-major, channel-minor rows
+            Co, Ci = conv.weight.shape[:2]
             N = max(Co, 64)
             bias = torch.zeros(N, **f)
             bias[:Co] = conv.bias.detach()
             if i == 0:                                                            # im2col + GEMM, K padded to a multiple of 64
                 K = -(-27 * Ci // 64) * 64
                 wm = torch.zeros(N, K, **f)
-                wm[:Co, :27 * Ci] = wt.reshape(Co, 27 * Ci)
+                wm[:Co, :27 * Ci] = conv.weight.detach().permute(0, 2, 3, 4, 1).reshape(Co, 27 * Ci)      # tap-major, channel-minor rows
                 wz = self.k_gemm_wprep(wm)
             else:                                                                 # conv3x: Ci padded to a multiple of 64 (stage 2: 32 -> 64)
                 K = max(Ci, 64)
-                wm = torch.zeros(N, 27, K, **f)
-                wm[:Co, :, :Ci] = wt.reshape(Co, 27, Ci)
-                wm = wm.reshape(N, 27 * K)
                 wz = torch.empty(3 * N * 27 * K, device=device, dtype=torch.int16)
-                _lib.call("rpb_conv3x_wprep", _p(wm), _p(wz, I16), N, K, _stream(), label="conv3x_wprep", nbytes=10 * N * 27 * K)
+                conv3x_wprep(padded_weight(conv, N, K).to(device), wz, N, K)
             sc64 = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
             sh64 = bn.bias.detach().double() - bn.running_mean.detach().double() * sc64
             prep[f"s{i + 1}"] = dict(wz=wz, bias=bias, N=N, K=K, C=Co, sc=sc64.float().contiguous(), sh=sh64.float().contiguous())
