@@ -744,6 +744,27 @@ int rpb_cno_pack(const float* x, void* planes, long M, int Cin, void* stream);
 /*     rpb_cno_conv3x: `res` may alias `out` element for element (same address, ldr == ldo): a lane reads res[m][n] and then writes
  *     out[m][n], nobody else touches that element.  The training step accumulates data gradients into one buffer that way.
  *
+ * CNO3d on the opt-in "f16x2" eval arithmetic (CNO3d.set_arith("f16x2"); csrc/rpb_cno3h.hip; additions do not change RPB_ABI_VERSION;
+ * DESIGN.md section 17.2).
+ *     rpb_cno_conv3x_f16x2: the implicit GEMM of rpb_conv3x_f16x2 (same planes P[2][M][Ci] fp16 of the activations scaled by 2^ea[0], same
+ *     rpb_conv3x_wprep_f16x2 weights scaled by 2^ew[0], three products, dropped term <= 2^-22 |a b|; ea, ew read from device memory) with
+ *     the epilogue  v = fmaf(acc * 2^-(ea + ew), sc[n], sh[n]);  if (act) v = v > 0 ? v : 0.2 v;  if (res) v += res[m * ldr + n]  and the
+ *     first nvalid channels as fp32 rows out[m * ldo + n]; out and res point at the first column the launch owns, res may alias out
+ *     element for element.  There is no plane output: the planes of the result need its maximum, which exists when all producers of a
+ *     buffer have finished.  Instead `amax` (a device word, may be NULL) receives atomicMax of bits(v) & 0x7fffffff over exactly the
+ *     elements the launch writes (m < M, n < nvalid; at most one atomic per wave; NaN / inf patterns sort on top; order-independent, so
+ *     outputs stay bit-reproducible).  The caller zeroes the word once; producers of disjoint column ranges share it (the concat).
+ *     Ci % 64 == 0, N in {64, 128}, 1 <= nvalid <= N, act in {0, 1}, ldo and ldr >= nvalid.
+ *     rpb_amax_exp_finish: the word -> e with max * 2^e in [2^14, 2^15), 0 for zero or non-finite (the second half of rpb_amax_exp); the
+ *     planes then come from rpb_split2h(x, planes, M, C, ldx, e) over the whole row width.
+ *     rpb_cno_pack_f16x2: the first layer's input x [M][Cin] fp32 (1 <= Cin <= 64, any M * Cin) -> e[0] (as rpb_amax_exp) and planes
+ *     P[2][M][64] with columns Cin..63 zero, bit-equal to rpb_split2h of the zero-padded rows under the same e. */
+int rpb_cno_conv3x_f16x2(const void* planes, const void* Wz, const float* sc, const float* sh, const float* res, float* out, int* amax,
+                         long M, int N, int Ci, int nvalid, int act, int ldr, int ldo, int Hc, int Wc, int Dc, const int* ea,
+                         const int* ew, void* stream);
+int rpb_amax_exp_finish(int* e, void* stream);
+int rpb_cno_pack_f16x2(const float* x, void* planes, long M, int Cin, int* e, void* stream);
+/*
  * CNO3d training step (opt-in: CNO3d.enable_training()) -- batch-statistics BatchNorm3d + LeakyReLU(0.2) + residual on rows [M][C],
  * forward and backward (csrc/rpb_cno_train.hip; additions do not change RPB_ABI_VERSION).  C in {16, 32, 64, 128}; every row pointer arrives
  * at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed summation order (two calls are bit-equal).

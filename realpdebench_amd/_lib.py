@@ -207,6 +207,9 @@ SIGNATURES = {
     "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),
     "rpb_cno_conv3x": (_I, "ppppppp" + "l" + "iiiiiii" + "iii" + "p"),
     "rpb_cno_pack": (_I, "pp" + "li" + "p"),
+    "rpb_cno_conv3x_f16x2": (_I, "ppppppp" + "l" + "iiiiii" + "iii" + "pp" + "p"),
+    "rpb_amax_exp_finish": (_I, "p" + "p"),
+    "rpb_cno_pack_f16x2": (_I, "pp" + "li" + "p" + "p"),
     "rpb_cno_bn_rows": (_I, ""),
     "rpb_cno_bn_stats": (_I, "p" + "ili" + "p" + "p"),
     "rpb_cno_bn_finish": (_I, "p" + "ili" + "pppp" + "dd" + "pppp" + "p"),

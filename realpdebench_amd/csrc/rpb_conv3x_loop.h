@@ -2,8 +2,8 @@
 // body of conv3x_kernel<WN> (csrc/rpb_conv3x.hip) and cno_conv3x_kernel<WN> (csrc/rpb_cno.hip), which differ in their epilogues only.
 // It is a fragment and not a function on purpose: as a forced-inline __device__ template the body is optimised on its own, without
 // the kernel's launch bounds, and every instance came out differently; included as text, every bf16x3 instance keeps its code
-// (profiles/conv3_fwd_unify.txt, profiles/conv3x_loop_share.txt).  csrc/rpb_conv3h.hip (two fp16 planes) keeps its own text: the
-// same record has what sharing did to its <1> instance.
+// (profiles/conv3_fwd_unify.txt, profiles/conv3x_loop_share.txt).  The two-fp16-plane kernels keep a text of their own,
+// csrc/rpb_conv3h_loop.h: the same record has what one body for both plane schemes did to the f16x2 <1> instance.
 //
 // Expects  a template parameter WN (waves over co: 1, 2 or 4) and an argument object `a` with
 //              P [3][M][Ci] bf16 planes, Wz (rpb_conv3x_wprep order), M, N, Ci, T, H, W;

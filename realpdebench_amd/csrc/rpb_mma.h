@@ -14,7 +14,7 @@
 //                      rpb_split_pair_rne / split8_rne on purpose: the hardware conversion of those keeps a NaN a NaN where the integer form
 //                      rounds its payload like any other bit pattern, and every producer of a plane buffer has to give the same bits
 //                      (rpb_cno_conv3x promises the planes rpb_split3 would have written).  One definition enforces that.
-// (Not here, because it only looks similar: split2h of rpb_conv3h.hip -- scalar, scaled by ldexpf.)
+// (Not here, because it only looks similar: split2h of rpb_conv3h.h -- scalar, scaled by ldexpf.)
 #pragma once
 #include "rpb_common.h"
 

@@ -21,6 +21,12 @@ Layers narrower than 64 channels run padded to 64 with zero weight rows / column
 buffer a convolution reads are zeroed here (zero weights do not cancel NaN).  A concat is two producers writing disjoint column ranges
 of one plane buffer.
 
+``set_arith("f16x2")`` (opt-in, evaluation forward only) runs the same 35 layers on two fp16 planes per operand:
+  rpb_cno_pack_f16x2     x -> exponent e and fp16 planes P[2][M][64] of x * 2^e
+  rpb_cno_conv3x_f16x2   x 35: fp32 rows of the result, and the maximum of |v| into the destination buffer's word (atomicMax)
+  rpb_amax_exp_finish, rpb_split2h   once per buffer, after its last producer: word -> exponent, rows -> planes
+No host synchronisation; a concat is two producers of one row buffer and one word.
+
 Parameters carry the reference's names, shapes and dtypes (the same ``nn`` module tree, ``decoder_inv.3`` -- constructed, never used in
 ``forward`` -- included), so ``state_dict`` / ``load_state_dict`` are the reference's; kernel layouts are derived tensors rebuilt when a
 parameter changed.
@@ -29,7 +35,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import Sub, _p, _stream, conv3x_wprep, gemm_nt, split3
+from ..ops import Sub, _p, _stream, amax_exp_finish, conv3_f16x2_weights, conv3x_wprep, gemm_nt, split2h, split3
 from ..ops import add as ops_add
 from ._common import EvalOnly, HipFunction, padded_weight, wgrad
 from .model import Model
@@ -37,6 +43,7 @@ from .model import Model
 I16 = torch.int16
 N_LAYERS = 3
 MAX_CH = 64                    # widest first-layer input / last-layer output: one 64-channel tile
+N_WORDS = 32                   # activation buffers of one f16x2 forward (``_forward_rows_f16x2``): one amax / exponent word each
 # Layers whose data gradient runs on the exact-fp32 implicit GEMM (rpb_gemm_nt) instead of the bf16x3 kernel: the ones that add into the
 # gradient of the neck's residual chain.  A BatchNorm shift gradient is a column sum of that gradient, which sees a per-channel bias of
 # the error sqrt(M) times stronger than its unbiased part; the bf16x3 kernel's error as a data gradient has such a bias (column mean 3-4
@@ -136,11 +143,42 @@ class _Act:
         return Sub(self.rows, col)
 
 
+class _ActH:
+    """One activation buffer of the f16x2 evaluation forward: fp32 rows [M][ld] (what the producers write and a residual reads), the
+    fp16 planes [2][M][ld] of the rows scaled by 2^e (what the next convolution reads) and one int32 word of the forward's ``words``
+    tensor: the producers max their |v| bit patterns into it, ``finish`` turns it into e and splits the rows.  ``zero``: the producers
+    leave columns unwritten that a convolution reads.  ``rows=False``: the first layer's input, whose planes rpb_cno_pack_f16x2 writes."""
+
+    def __init__(self, M, ld, device, zero, words, index, rows=True):
+        self.rows = (torch.zeros if zero else torch.empty)(M, ld, dtype=torch.float32, device=device) if rows else None
+        self.planes = torch.empty(2 * M * ld, dtype=I16, device=device)
+        self.word = Sub(words, index)
+        self.M, self.ld, self.ready = M, ld, False
+
+    def at(self, col=0):
+        return Sub(self.rows, col)
+
+    def finish(self):
+        """After the last producer: word -> exponent, rows -> planes over the whole row width (zero columns give zero planes)."""
+        amax_exp_finish(self.word)
+        split2h(self.rows, self.planes, self.M, self.ld, self.word)
+        self.ready = True
+        return self
+
+
 def _ptr(t, dtype=torch.float32):
     """address of a tensor of ``dtype``, of an ``ops.Sub`` (a block of an fp32 allocation, whatever it holds), or the address itself"""
     if t is None or isinstance(t, int):
         return t
     return _p(t) if isinstance(t, Sub) else _p(t, dtype)
+
+
+def _iptr(t):
+    """address of an int32 word: a tensor, an ``ops.Sub`` (a word of an int32 tensor, or of an fp32 allocation whatever it holds), or
+    the address itself"""
+    if t is None or isinstance(t, int):
+        return t
+    return _p(t, t.t.dtype) if isinstance(t, Sub) else _p(t, torch.int32)
 
 
 class CNO3d(EvalOnly, Model):
@@ -187,6 +225,17 @@ class CNO3d(EvalOnly, Model):
         self.decoder = nn.ModuleList([CNOBlock3d(dec_in[i], dec_out[i]) for i in range(N_LAYERS)])
         self.decoder_inv = nn.ModuleList([CNOBlock3d(inv[i], inv[i]) for i in range(N_LAYERS + 1)])                  # [3] is never used
         self.res_nets = nn.Sequential(*([ResidualBlock3d(ef[l]) for l in range(N_LAYERS)] + [ResidualBlock3d(ef[N_LAYERS]) for _ in range(6)]))
+        self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
+
+    def set_arith(self, arith):
+        """Arithmetic of the evaluation / rollout forward's 35 convolutions: ``"f32"`` (default, the parity path: operands as three bf16
+        planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power of
+        two, three products, dropped term <= 2^-22; csrc/rpb_cno3h.hip).  Only the evaluation forward changes:
+        the opt-in training step (``enable_training()``) stays on its kernels under either setting."""
+        if arith not in ("f32", "f16x2"):
+            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
+        self.arith = arith
+        return self
 
     # ------------------------------------------------------------------ the opt-in training step
     def enable_training(self):
@@ -247,6 +296,22 @@ class CNO3d(EvalOnly, Model):
             prep[name] = dict(wz=wz, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
         return prep
 
+    def _prep_f16x2(self, device):
+        """``_prep`` for ``set_arith("f16x2")``: per layer the weights as two scaled fp16 planes with their exponent ``ew`` (int32 [1] on
+        the device) next to the same folded affine; same cache, same invalidation rule."""
+        tensors = list(self.parameters()) + list(self.buffers())
+        return self._layouts.get("prep_f16x2", tensors, lambda: self._build_prep_f16x2(device))
+
+    def _build_prep_f16x2(self, device):
+        prep = {}
+        for name, (conv, bn) in self._convs().items():
+            Co, Ci = conv.weight.shape[:2]
+            N, K = max(Co, 64), max(Ci, 64)
+            wz, ew = conv3_f16x2_weights(padded_weight(conv, N, K).to(device), N, K)
+            sc, sh = fold_affine(conv, bn, N)
+            prep[name] = dict(wz=wz, ew=ew, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
+        return prep
+
     def _prep_train(self, device):
         """The training step's layouts: they depend on the convolutions alone (BatchNorm enters through the statistics kernels)."""
         tensors = [t for conv, _ in self._convs().values() for t in (conv.weight, conv.bias)]
@@ -286,6 +351,20 @@ class CNO3d(EvalOnly, Model):
                   nvalid, int(act), ldr, ldo, ldp, *mesh, _stream(), label=f"cno_conv3x[N{N},Ci{Ci}]",
                   nbytes=6 * M * Ci + (4 * M * nvalid if out is not None else 0) + (6 * M * nvalid if out_planes is not None else 0)
                   + (4 * M * nvalid if res is not None else 0), flops=2 * M * N * 27 * Ci)
+
+    @staticmethod
+    def k_pack_f16x2(x, planes, M, Cin, e):
+        """x [M][Cin] fp32 -> e[0] with max|x| * 2^e in [2^14, 2^15) and fp16 planes P[2][M][64] of x * 2^e, columns Cin..63 zero."""
+        _lib.call("rpb_cno_pack_f16x2", _ptr(x), _ptr(planes, I16), M, Cin, _iptr(e), _stream(), label="cno_pack_f16x2",
+                  nbytes=8 * M * Cin + 4 * M * 64)
+
+    @staticmethod
+    def k_conv_f16x2(planes, wz, sc, sh, M, N, Ci, mesh, nvalid, act, ea, ew, res=None, ldr=0, out=None, ldo=0, amax=None):
+        """One CNO layer on two fp16 planes (rpb_cno_conv3x_f16x2).  ``planes``: int16 tensor or raw address; ``res`` / ``out``: fp32 tensors,
+        ``ops.Sub`` or raw addresses (already at the first column); ``amax`` / ``ea`` / ``ew``: int32 tensors, ``ops.Sub`` or raw addresses."""
+        _lib.call("rpb_cno_conv3x_f16x2", _ptr(planes, I16), _ptr(wz, I16), _ptr(sc), _ptr(sh), _ptr(res), _ptr(out), _iptr(amax), M, N, Ci,
+                  nvalid, int(act), ldr, ldo, *mesh, _iptr(ea), _iptr(ew), _stream(), label=f"cno_conv3x_f16x2[N{N},Ci{Ci}]",
+                  nbytes=4 * M * Ci + 4 * M * nvalid + (4 * M * nvalid if res is not None else 0), flops=2 * M * N * 27 * Ci)
 
     # the row passes of the training step (csrc/rpb_cno_train.hip); row operands: fp32 tensors, ``ops.Sub`` or raw addresses at the first column
     @staticmethod
@@ -492,6 +571,8 @@ class CNO3d(EvalOnly, Model):
     def _forward_rows(self, x, B, mesh, keep=None):
         """x [M][in_dim] fp32 -> [M][out_dim] fp32.  ``keep`` (a dict) receives the fp32 rows of the lift output, ``skip[0..2]`` and the
         neck output (tests); the extra fp32 stores do not change any value."""
+        if self.arith == "f16x2":
+            return self._forward_rows_f16x2(x, mesh, keep)
         dev = x.device
         M = x.shape[0]
         prep = self._prep(dev)
@@ -563,6 +644,88 @@ class CNO3d(EvalOnly, Model):
         d = planes(64, 64)
         layer("project.0", c3, d)
         return layer("project.1", d, act=False, f32=True)
+
+    def _forward_rows_f16x2(self, x, mesh, keep=None):
+        """``_forward_rows`` under ``set_arith("f16x2")``: the same data flow on ``_ActH`` buffers.  Every layer writes fp32 rows and maxes
+        into the word of its destination; when all producers of a buffer are done (two for a concat) ``finish`` turns the word into the
+        exponent and splits the rows into planes -- one extra read and write of the activation per buffer, no host synchronisation
+        (DESIGN.md section 17.2).  Residuals and ``keep`` read the fp32 rows, which always exist here."""
+        dev, M = x.device, x.shape[0]
+        prep = self._prep_f16x2(dev)
+        words = torch.zeros(N_WORDS, dtype=torch.int32, device=dev)  # one word per buffer, zeroed once
+        used = [0]
+
+        def buf(ld, written, rows=True):
+            used[0] += 1
+            return _ActH(M, ld, dev, written < ld, words, used[0] - 1, rows=rows)
+
+        def layer(name, src, dst=None, col=0, act=True, res=None):
+            """src: a finished _ActH read whole; dst: _ActH written at column ``col`` (None: the model output, no amax)"""
+            s = prep[name]
+            assert src.ld == s["K"] and src.ready, name
+            out = torch.empty(M, s["Co"], device=dev, dtype=torch.float32) if dst is None else None
+            self.k_conv_f16x2(src.planes, s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, s["Co"], act, src.word, s["ew"],
+                              res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
+                              out=out if dst is None else dst.at(col), ldo=s["Co"] if dst is None else dst.ld,
+                              amax=None if dst is None else dst.word)
+            return out
+
+        def res_block(i, xa, width):
+            """res_nets[i]: x + BN(conv(L(BN(conv x))))"""
+            ld = max(width, 64)
+            h, ya = buf(ld, width), buf(ld, width)
+            layer(f"res_nets.{i}.1", xa, h)
+            layer(f"res_nets.{i}.2", h.finish(), ya, act=False, res=xa)
+            return ya.finish()
+
+        ef = self.encoder_features
+        p0 = buf(64, 64, rows=False)                                  # (the pack kernel writes the zero pad and the exponent itself)
+        self.k_pack_f16x2(x, p0.planes, M, self.in_dim, p0.word)
+        p0.ready = True
+        p1 = buf(64, 64)
+        layer("lift.0", p0, p1)
+        xa = buf(64, ef[0])
+        layer("lift.1", p1.finish(), xa, act=False)
+        xa.finish()
+
+        def kept(name, b, width):
+            if keep is not None:
+                keep[name] = b.rows[:, :width].contiguous()
+
+        kept("lift", xa, ef[0])
+        skip = []
+        for i in range(N_LAYERS):
+            skip.append(res_block(i, xa, ef[i]))
+            kept(f"skip{i}", skip[i], ef[i])
+            nxt = buf(max(ef[i + 1], 64), ef[i + 1])
+            layer(f"encoder.{i}", xa, nxt)
+            xa = nxt.finish()
+        n_res = len(self.res_nets)
+        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
+            xa = res_block(n_res - 1 - j, xa, ef[3])
+        kept("neck", xa, ef[3])
+        # decoder: cat(x, ED_expansion(skip)) is two producers of one row buffer and one word; finish runs once, after both
+        a = buf(128, 128)
+        layer("ED_expansion.3", xa, a)
+        b = buf(128, 128)
+        layer("decoder_inv.0", a.finish(), b)
+        c1 = buf(128, 128)
+        layer("decoder.0", b.finish(), c1, col=0)                     # 64 channels -> columns 0..63
+        layer("ED_expansion.2", skip[2], c1, col=64)                  # 64 channels -> columns 64..127
+        b = buf(128, 128)
+        layer("decoder_inv.1", c1.finish(), b)
+        c2 = buf(64, 64)
+        layer("decoder.1", b.finish(), c2, col=0)                     # 32 -> columns 0..31
+        layer("ED_expansion.1", skip[1], c2, col=32)                  # 32 -> columns 32..63
+        b = buf(64, 64)
+        layer("decoder_inv.2", c2.finish(), b)
+        c3 = buf(64, 32)
+        layer("decoder.2", b.finish(), c3, col=0)                     # 16 -> columns 0..15
+        layer("ED_expansion.0", skip[0], c3, col=16)                  # 16 -> columns 16..31; 32..63 stay zero
+        d = buf(64, 64)
+        layer("project.0", c3.finish(), d)
+        assert used[0] == N_WORDS
+        return layer("project.1", d.finish(), act=False)
 
     def check_input(self, shape):
         """The shapes ``forward`` takes: [B, T, H, W, in_dim] with in_dim < T."""

@@ -726,6 +726,12 @@ def amax_exp(x, e, M, C, ldx=None):
     _lib.call("rpb_amax_exp", _p(x), M, C, C if ldx is None else ldx, _p(e, torch.int32), _stream(), label="amax_exp", nbytes=4 * M * C)
 
 
+def amax_exp_finish(e):
+    """e[0] (int32 on the device; a tensor or a ``Sub`` of one): the maximum of |x| bit patterns that launches formed with atomicMax
+    -> the exponent of ``amax_exp``.  Stays on the device."""
+    _lib.call("rpb_amax_exp_finish", _p(e, torch.int32), _stream(), label="amax_exp_finish", nbytes=8)
+
+
 def split2h(x, planes, M, C, e, ldx=None):
     """planes[2][M][C] (fp16 bit patterns in an int16 tensor) = hi / lo of x[M][ldx] * 2^e[0], both rounded to nearest even."""
     _lib.call("rpb_split2h", _p(x), _p(planes, torch.int16), M, C, C if ldx is None else ldx, _p(e, torch.int32), _stream(),

@@ -3,7 +3,10 @@
 of model/cno.py), the 128 -> 128 layer's issued bf16 MFMA rate against the rate rpb_mfma_probe measures in the same run, and the fused
 launch (rpb_cno_conv3x writing fp32 rows + bf16 planes) against the two passes it replaces (rpb_conv3x + rpb_split3) at the same shape.
 Launches under ~100 us are dominated by the event overhead in the table.
-    python tools/cno_probe.py [--batches 1 8] [--runs 20] [--out profiles/cno_probe.txt]"""
+``--arith f16x2`` measures CNO3d.set_arith("f16x2") instead: both arithmetics alternately in this process on the same seeded input (the
+default path is the comparison; the spread is what repeating one configuration gives), the HIP-event table of each, the 128 -> 128
+layer's issued fp16 MFMA rate, the share of the split passes and the Rel-L2 of the f16x2 output against the default's.
+    python tools/cno_probe.py [--arith f32|f16x2] [--batches 1 8] [--runs 20] [--repeats 3] [--out profiles/cno_probe.txt]"""
 import argparse
 import os
 import statistics
@@ -73,10 +76,70 @@ def fused_vs_pair(C, B, runs, sustained):
             f"fp32-grade {useful:.1f} TFLOP/s delivered"]
 
 
+def event_table(m, x, lines):
+    """one forward under HIP events -> {label: summary}; the table is appended to ``lines``"""
+    with torch.no_grad():
+        _lib.PROFILE = {}
+        m(x)
+        torch.cuda.synchronize()
+    fam = _lib.profile_summary()
+    _lib.PROFILE = None
+    tot = sum(v["total_ms"] for v in fam.values())
+    lines.append(f"  HIP-event table, arith = {m.arith} (one forward, sum {tot:.3f} ms incl. event overhead; allocation and zero-fill are not launches of this table)")
+    lines.append(f"  {'family':<32}{'calls':>6}{'total ms':>10}{'share':>7}{'GB':>9}{'of 8 TB/s':>11}{'TFLOP/s':>9}")
+    for k, v in sorted(fam.items(), key=lambda kv: -kv[1]["total_ms"]):
+        t = v["total_ms"] * 1e-3
+        lines.append(f"  {k:<32}{v['calls']:>6}{v['total_ms']:>10.3f}{v['total_ms'] / tot:>7.2f}{v['bytes'] * v['calls'] / 1e9:>9.3f}"
+                     f"{v['bytes'] * v['calls'] / t / HBM_PEAK:>11.3f}{v['flops'] * v['calls'] / t / 1e12:>9.2f}")
+    return fam, tot
+
+
+def arith_compare(m, B, runs, repeats, sustained, lines):
+    """f32 and f16x2 alternately, ``repeats`` times each: the spread of a configuration is the range of its medians."""
+    T, H, W = SHAPE[:3]
+    M = B * T * H * W
+    x = torch.randn(B, *SHAPE, device=DEV, generator=torch.Generator(device=DEV).manual_seed(B))
+    meds = {"f32": [], "f16x2": []}
+    with torch.no_grad():
+        for _ in range(repeats):
+            for arith in ("f32", "f16x2"):
+                m.set_arith(arith)
+                meds[arith].append(median_ms(lambda: m(x), runs)[0])
+        want = m.set_arith("f32")(x)
+        got = m.set_arith("f16x2")(x)
+        err = float((got.double() - want.double()).norm() / want.double().norm())
+        del want, got
+    med = {k: statistics.median(v) for k, v in meds.items()}
+    spread = {k: max(v) - min(v) for k, v in meds.items()}
+    gain = med["f32"] - med["f16x2"]
+    for k in ("f32", "f16x2"):
+        lines.append(f"B={B} arith={k}: eval forward medians of {runs} runs after 3 warm-ups, {repeats} alternating repeats: "
+                     + " ".join(f"{t:.3f}" for t in meds[k]) + f" ms; median {med[k]:.3f} ms, spread {spread[k]:.3f} ms; {B / med[k] * 1e3:.2f} samples/s")
+    lines.append(f"B={B}: f32 - f16x2 = {gain:.3f} ms ({med['f32'] / med['f16x2']:.3f}x); largest spread {max(spread.values()):.3f} ms: "
+                 + ("f16x2 is faster by more than the spread" if gain > max(spread.values()) else "f16x2 is NOT faster by more than the spread"))
+    lines.append(f"B={B}: Rel-L2 of the f16x2 output against the default's on the same seeded input: {err:.2e}")
+    for arith in ("f32", "f16x2"):
+        fam, tot = event_table(m.set_arith(arith), x, lines)
+    passes = sum(v["total_ms"] for k, v in fam.items() if k in ("split2h", "amax_exp_finish", "cno_pack_f16x2"))
+    lines.append(f"  split passes (split2h + amax_exp_finish + cno_pack_f16x2): {passes:.3f} ms = {passes / tot:.3f} of the f16x2 table; "
+                 f"split2h moves {fam['split2h']['bytes'] * fam['split2h']['calls'] / 1e9:.3f} GB")
+    v = fam["cno_conv3x_f16x2[N128,Ci128]"]
+    # v_mfma_f32_32x32x16_f16 per launch: 128-token tiles x 27 taps x 16-channel chunks x (4 x N / 32) output tiles x three products
+    mf = -(-M // 128) * 27 * (128 // 16) * 3 * 4 * (128 // 32)
+    issued = mf * 32768 / (v["avg_ms"] * 1e-3) / 1e12
+    lines.append(f"  128 -> 128 layer: {v['avg_ms']:.3f} ms per launch; issued {issued:.0f} TFLOP/s fp16 MFMA = {issued / sustained:.2f} of the sustained "
+                 f"rate of this run ({sustained:.0f} TFLOP/s, rpb_mfma_probe); fp32-grade {2.0 * M * 128 * 27 * 128 / (v['avg_ms'] * 1e-3) / 1e12:.1f} TFLOP/s delivered")
+    m.set_arith("f32")
+    del x
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3, help="with --arith f16x2: alternating repeats of each arithmetic")
+    ap.add_argument("--arith", default="f32", choices=["f32", "f16x2"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -84,6 +147,18 @@ def main():
     torch.manual_seed(0)
     m = CNO3d(in_dim=SHAPE[-1], in_size=SHAPE[1], N_layers=3, out_dim=SHAPE[-1]).to(DEV).eval()
     sustained = sustained_bf16()
+    if a.arith == "f16x2":
+        lines = [f"CNO3d N_layers = 3, shape {SHAPE}: set_arith('f16x2') against the default arithmetic, alternately in one process",
+                 f"sustained bf16 MFMA rate of this chip (rpb_mfma_probe, random operands): {sustained:.0f} TFLOP/s"]
+        for B in a.batches:
+            arith_compare(m, B, a.runs, a.repeats, sustained, lines)
+        txt = "\n".join(lines)
+        print(txt)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(txt + "\n")
+        return
     cells = SHAPE[0] * SHAPE[1] * SHAPE[2]
     lines = [f"CNO3d N_layers = 3, shape {SHAPE} ({cells} cells per sample, 15.85 MFLOP useful per cell = {15.85e6 * cells / 1e12:.2f} TFLOP per sample)",
              f"sustained bf16 MFMA rate of this chip (rpb_mfma_probe, random operands): {sustained:.0f} TFLOP/s"]
