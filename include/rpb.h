@@ -37,8 +37,11 @@ extern "C" {
  *      round 6: rpb_dp_p2p_*, rpb_cell_mix_eval_dft_f16x2, rpb_cell_mix_eval_crop_f16x2, rpb_proj_fwd_f16x2 added (additions only);
  *      rpb_amax_exp, rpb_split2h, rpb_conv3x_wprep_f16x2, rpb_conv3x_f16x2 added (additions only)
  *   3  rpb_proj_wgrad, rpb_proj_wgrad_slots, rpb_proj_wgrad_row, rpb_proj_wgrad_roles removed; rpb_proj_dgrad reads gh from `gu` only
- *      and lost its b1, w2, gout and act arguments */
-#define RPB_ABI_VERSION 3
+ *      and lost its b1, w2, gout and act arguments
+ *   4  the MWT3d training step: rpb_mwt_conv3_keep, rpb_mwt_spec_out_keep, rpb_mwt_lo_bwd(_rows), rpb_mwt_conv3_dgrad,
+ *      rpb_mwt_conv3_wgrad(_splits), rpb_mwt_modes_bwd, rpb_mwt_head_bwd(_rows), rpb_mwt_lift_wgrad(_rows) added (additions only; the
+ *      number moves so that a binding that expects them refuses a library without them) */
+#define RPB_ABI_VERSION 4
 const char* rpb_last_error(void);
 int rpb_abi_version(void);
 /* bf16 activation STORAGE (BASELINE.json configs[4]; the opt-in rollout path): how many bf16 planes of the fp32 constants (conv / fc1 weights,
@@ -706,6 +709,39 @@ int rpb_mwt_conv3x(const float* x, const void* wpx, const float* cb48, const flo
  *     out [B][T * r][Nx][Ny][Cout] */
 int rpb_mwt_head(const float* x, const float* w0t, const float* b0, const float* w1, const float* b1, float* out, int B, int Nx, int Ny,
                  int T, int Cout, int r, void* stream);
+/*
+ * MWT3d training step (opt-in: MWT3d.enable_training(); csrc/rpb_mwt_train.hip).  The adjoints of decompose,
+ * reconstruct and of the rpb_mwt_axis stages are those entry points on transposed tables; below is what the forward's fusion forces.
+ * No atomics, fixed summation order: two calls are bit-equal.  Partials are finished by rpb_reduce_partials.
+ *     rpb_mwt_conv3_keep / rpb_mwt_spec_out_keep: rpb_mwt_conv3 / rpb_mwt_spec_out (same kernel text, bit-equal out) that also store the
+ *     ReLU output in front of Lo: z, rv [cells][36]. */
+int rpb_mwt_conv3_keep(const float* x, const float* wp, const float* cb48, const float* lop, const float* lb, float* out, float* z, int B,
+                       int Nx, int Ny, int T, int accumulate, void* stream);
+int rpb_mwt_spec_out_keep(const float* S, const float* GT, const float* loT, const float* lb, float* out, float* rv, long lines, int T,
+                          int K2, int accumulate, void* stream);
+/*     lo_bwd (kernels A, B and C): gz [ncell][36] = (gout lo) where z > 0, else 0 (lo [36 out][36 in] = Linear.weight); part
+ *     [rpb_mwt_lo_bwd_rows(ncell)][36 * 36 + 36] = per-workgroup partials of (dLo [o][c] = sum gout[o] z[c] | dlb [o] = sum gout[o]). */
+int rpb_mwt_lo_bwd_rows(long ncell);
+int rpb_mwt_lo_bwd(const float* gout, const float* z, const float* lo, float* gz, float* part, long ncell, void* stream);
+/*     conv3_dgrad: out (+)= Conv3d(36, 36, 3, padding = 1) of g without bias, ReLU or Lo, on the main loop of rpb_mwt_conv3; wpd = the wp
+ *     of rpb_mwt_conv3_wprep for the flipped, transposed taps w'[i][o][26 - tap] = w[o][i][tap]. */
+int rpb_mwt_conv3_dgrad(const float* g, const float* wpd, float* out, int B, int Nx, int Ny, int T, int accumulate, void* stream);
+/*     conv3_wgrad: part [rpb_mwt_conv3_wgrad_splits(cells)][36 * 36 * 27 + 36] = split-cell partials of (dW [o][i][tap] = sum_cells
+ *     g[cell][o] x[cell + tap][i], zero padding at the borders of every sample | db [o] = sum g[cell][o]); g, x [B][Nx][Ny][T][36]. */
+int rpb_mwt_conv3_wgrad_splits(long ncell);
+int rpb_mwt_conv3_wgrad(const float* g, const float* x, float* part, int B, int Nx, int Ny, int T, void* stream);
+/*     modes_bwd: X, gY -> gX [B][2][NB][36] = gY W^H per retained bin (W = Wt[tab[bin]]), and dWt[tab[bin]][i][o] += sum_b conj(X[b][i])
+ *     gY[b][o] as (re, im) pairs: the gradient in the Wt layout; the caller zeroes dWt once per CZ block, levels accumulate. */
+int rpb_mwt_modes_bwd(const float* X, const float* gY, const float* Wt, const int* tab, float* gX, float* dWt, int B, int NB, void* stream);
+/*     head_bwd: recomputes h = ReLU(Lc0 x + b0); gx [cells][36]; part [rpb_mwt_head_bwd_rows(cells)][dout * 128 + dout + 128 * 36 + 128] =
+ *     partials of (dLc1 [dout][128] | db1 | dLc0 [128][36] | db0), dout = Cout * r <= 16; gout [B][T * r][Nx][Ny][Cout]. */
+int rpb_mwt_head_bwd_rows(long ncell);
+int rpb_mwt_head_bwd(const float* x, const float* gout, const float* w0t, const float* b0, const float* w1, float* gx, float* part, int B,
+                     int Nx, int Ny, int T, int Cout, int r, void* stream);
+/*     lift_wgrad: part [rpb_mwt_lift_wgrad_rows(cells)][36 * Cin + 36] = partials of (dLk [36][Cin] | db); g [B][H][W][T][36],
+ *     x [B][T][H][W][Cin]. */
+int rpb_mwt_lift_wgrad_rows(long ncell);
+int rpb_mwt_lift_wgrad(const float* g, const float* x, float* part, int B, int T, int H, int W, int Cin, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * DeepONet (realpdebench/model/deeponet.py) -- evaluation forward (additions do not change RPB_ABI_VERSION).  The branch CNN's

@@ -7,7 +7,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 3          # RPB_ABI_VERSION of include/rpb.h
+ABI_VERSION = 4         # RPB_ABI_VERSION of include/rpb.h
 LIB_PATH = os.environ.get("RPB_LIB_PATH") or os.path.join(_HERE, "csrc", "librpb_hip.so")     # RPB_LIB_PATH: an instrumented build (tools/dbg)
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -202,6 +202,18 @@ SIGNATURES = {
     "rpb_mwt_conv3x_wprep": (_I, "pp" + "i" + "p" + "p"),
     "rpb_mwt_conv3x": (_I, "pppppp" + "iiiii" + "i" + "pp" + "p"),
     "rpb_mwt_head": (_I, "pppppp" + "iiiiii" + "p"),
+    "rpb_mwt_conv3_keep": (_I, "ppppppp" + "iiiii" + "p"),
+    "rpb_mwt_spec_out_keep": (_I, "pppppp" + "liii" + "p"),
+    "rpb_mwt_lo_bwd_rows": (_I, "l"),
+    "rpb_mwt_lo_bwd": (_I, "ppppp" + "l" + "p"),
+    "rpb_mwt_conv3_dgrad": (_I, "ppp" + "iiiii" + "p"),
+    "rpb_mwt_conv3_wgrad_splits": (_I, "l"),
+    "rpb_mwt_conv3_wgrad": (_I, "ppp" + "iiii" + "p"),
+    "rpb_mwt_modes_bwd": (_I, "pppppp" + "ii" + "p"),
+    "rpb_mwt_head_bwd_rows": (_I, "l"),
+    "rpb_mwt_head_bwd": (_I, "ppppppp" + "iiiiii" + "p"),
+    "rpb_mwt_lift_wgrad_rows": (_I, "l"),
+    "rpb_mwt_lift_wgrad": (_I, "ppp" + "iiiii" + "p"),
     "rpb_don_bn_relu_pool": (_I, "pppp" + "iiiiiiii" + "p"),
     "rpb_don_trunk": (_I, "pppppppppp" + "iiii" + "p"),
     "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),

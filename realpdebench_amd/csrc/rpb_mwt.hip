@@ -4,8 +4,8 @@
 // channels are padded to 48 = 3 row tiles in REGISTERS (never in HBM), cells are the MFMA columns.  Everything else is a streaming or a
 // tiny kernel on the vector unit.  No kernel uses atomics: two calls give bit-equal results.
 #include "rpb_common.h"
+#include "rpb_mwt_conv3.h"      // MWT_C = 36 = c * k^2; mwt_conv3_k, mwt_spec_out_k
 
-#define MWT_C 36       // c * k^2
 #define MWT_K2 9       // k^2
 #define MWT_NC 4       // c
 
@@ -160,136 +160,10 @@ __global__ __launch_bounds__(256) void mwt_modes_k(const float* __restrict__ X, 
     Y[((bb * 2 + 1) * NB + bin) * MWT_C + o] = yi;
 }
 
-// ---------------------------------------------------------------------------------- last inverse stage (c2r along T) + ReLU + Lo (+=)
-// S [lines][K2 = 2 * kept T modes][36], GT [T][K2], loT [36 in][36 out], lb [36] -> out [lines * T][36]
-#define MWT_SO_CELLS 7
-__global__ __launch_bounds__(MWT_SO_CELLS* MWT_C) void mwt_spec_out_k(const float* __restrict__ S, const float* __restrict__ GT,
-                                                                      const float* __restrict__ loT, const float* __restrict__ lb,
-                                                                      float* __restrict__ out, long ncell, int T, int K2, int accumulate) {
-    __shared__ float v[MWT_SO_CELLS][MWT_C];
-    const int cl = threadIdx.x / MWT_C, c = threadIdx.x % MWT_C;
-    const long q = blockIdx.x * (long)MWT_SO_CELLS + cl;
-    const bool ok = q < ncell;
-    float a = 0.f;
-    if (ok) {
-        const long line = q / T;
-        const int t = (int)(q % T);
-        for (int k = 0; k < K2; ++k) a = fmaf(GT[t * K2 + k], S[(line * K2 + k) * MWT_C + c], a);
-    }
-    v[cl][c] = fmaxf(a, 0.f);
-    __syncthreads();
-    if (!ok) return;
-    float acc = lb[c];
-#pragma unroll
-    for (int k = 0; k < MWT_C; ++k) acc = fmaf(v[cl][k], loT[k * MWT_C + c], acc);
-    if (accumulate) acc += out[q * MWT_C + c];
-    out[q * MWT_C + c] = acc;
-}
-
-// ---------------------------------------------------------------------------------- 3x3x3 conv + bias + ReLU + Lo + bias (+=)
-// One wave = 64 consecutive cells = 4 column tiles of v_mfma_f32_16x16x4_f32; rows = output channel (3 tiles, 36 of 48 used).
-// Operand maps of the instruction: A[row = l & 15][k = l >> 4], B[k = l >> 4][col = l & 15], D register r = D[row = 4 (l >> 4) + r][col = l & 15].
-// K = 27 taps x 36 input channels; inside a tap the k index of step j, lane group g = l >> 4 is input channel 9 g + j, so a lane reads 9
-// consecutive floats of its neighbour cell per tap.  wp [27][9][3][64]: the A operand in lane order (rpb_mwt_conv3_wprep).
-// The ReLU'd accumulator tile is the B operand of the second product as it stands: register r of row tile t on lane group g is hidden
-// channel 16 t + 4 g + r, which is the k index that lop [3 t][4 r][3 u][64] pairs it with.
-typedef float mwt4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ mwt4 mwt_mfma(float a, float b, mwt4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__global__ __launch_bounds__(256) void mwt_conv3_k(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ cb,
-                                                   const float* __restrict__ lop, const float* __restrict__ lb, float* __restrict__ out,
-                                                   long ncell, int Nx, int Ny, int T, int accumulate) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, cl = lane & 15;
-    const long base = (blockIdx.x * 4L + wave) * 64;
-    if (base >= ncell) return;                       // wave-uniform
-    long cq[4];
-    int cx[4], cy[4], ct[4];
-    bool cv[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const long q = base + n * 16 + cl;
-        cv[n] = q < ncell;
-        cq[n] = cv[n] ? q : ncell - 1;
-        long r = cq[n];
-        ct[n] = (int)(r % T);
-        r /= T;
-        cy[n] = (int)(r % Ny);
-        r /= Ny;
-        cx[n] = (int)(r % Nx);
-    }
-    mwt4 acc[3][4];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[t][n] = mwt4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int tap = 0; tap < 27; ++tap) {
-        const int dx = tap / 9 - 1, dy = (tap / 3) % 3 - 1, dt = tap % 3 - 1;
-        float bv[4][9];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const bool ok = cv[n] && (unsigned)(cx[n] + dx) < (unsigned)Nx && (unsigned)(cy[n] + dy) < (unsigned)Ny &&
-                            (unsigned)(ct[n] + dt) < (unsigned)T;
-            // a neighbour inside the grid is inside the same sample; everything else reads cell 0 and is replaced by the zero pad
-            const float* p = x + (ok ? (cq[n] + ((long)dx * Ny + dy) * T + dt) * MWT_C : 0L) + 9 * g;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const float v = p[j];
-                bv[n][j] = ok ? v : 0.f;
-            }
-        }
-        const float* wt = wp + (long)tap * 9 * 3 * 64 + lane;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            float a[3];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) a[t] = wt[(j * 3 + t) * 64];
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[t][n] = mwt_mfma(a[t], bv[n][j], acc[t][n]);
-        }
-    }
-    // bias + ReLU on the rows 16 t + 4 g + r (cb is padded to 48 with zeros, so the pad rows stay 0)
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const mwt4 b4 = *reinterpret_cast<const mwt4*>(cb + 16 * t + 4 * g);
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][n][r] = fmaxf(acc[t][n][r] + b4[r], 0.f);
-    }
-    mwt4 o2[3][4];
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) o2[u][n] = mwt4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const float a2 = lop[((t * 4 + r) * 3 + u) * 64 + lane];
-#pragma unroll
-                for (int n = 0; n < 4; ++n) o2[u][n] = mwt_mfma(a2, acc[t][n][r], o2[u][n]);
-            }
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-        const int o0 = 16 * u + 4 * g;
-        if (o0 >= MWT_C) continue;                   // rows 36..47 are padding
-        const mwt4 b4 = *reinterpret_cast<const mwt4*>(lb + o0);
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            if (!cv[n]) continue;
-            mwt4* dst = reinterpret_cast<mwt4*>(out + cq[n] * MWT_C + o0);
-            mwt4 v = o2[u][n] + b4;
-            if (accumulate) v += *dst;
-            *dst = v;
-        }
-    }
-}
+// ---------------------------------------------------------------------------------- last inverse stage (c2r along T) + ReLU + Lo (+=),
+// ---------------------------------------------------------------------------------- 3x3x3 conv + bias + ReLU + Lo + bias (+=):
+// mwt_spec_out_k<false> and mwt_conv3_k<MWT_CONV_EVAL> of rpb_mwt_conv3.h: the kernel texts are shared with the training step
+// (rpb_mwt_train.hip), whose variants keep one more tensor each; the instances here are the evaluation forward's.
 
 // weights [36 co][36 ci][27] , lo [36][36] -> wp [27][9][3][64], lop [3][4][3][64] (zeros on the pad rows)
 __global__ void mwt_conv3_wprep_k(const float* __restrict__ w, const float* __restrict__ lo, float* __restrict__ wp, float* __restrict__ lop) {
@@ -417,8 +291,8 @@ extern "C" int rpb_mwt_spec_out(const float* S, const float* GT, const float* lo
     RPB_REQUIRE(S && GT && loT && lb && out, "rpb_mwt_spec_out: null pointer");
     RPB_REQUIRE(lines > 0 && T > 0 && K2 > 0, "rpb_mwt_spec_out: bad shape lines=%ld T=%d K2=%d", lines, T, K2);
     const long ncell = lines * T;
-    hipLaunchKernelGGL(mwt_spec_out_k, dim3(mwt_blocks(ncell, MWT_SO_CELLS)), dim3(MWT_SO_CELLS * MWT_C), 0, MWT_STREAM, S, GT, loT, lb, out,
-                       ncell, T, K2, accumulate);
+    hipLaunchKernelGGL(mwt_spec_out_k<false>, dim3(mwt_blocks(ncell, MWT_SO_CELLS)), dim3(MWT_SO_CELLS * MWT_C), 0, MWT_STREAM, S, GT, loT, lb,
+                       out, static_cast<float*>(nullptr), ncell, T, K2, accumulate);
     RPB_CHECK_LAUNCH("rpb_mwt_spec_out");
 }
 
@@ -435,8 +309,8 @@ extern "C" int rpb_mwt_conv3(const float* x, const float* wp, const float* cb48,
     RPB_REQUIRE(B > 0 && Nx > 0 && Ny > 0 && T > 0, "rpb_mwt_conv3: bad shape B=%d Nx=%d Ny=%d T=%d", B, Nx, Ny, T);
     RPB_REQUIRE(x != out, "rpb_mwt_conv3: in-place convolution is not possible");
     const long ncell = (long)B * Nx * Ny * T;
-    hipLaunchKernelGGL(mwt_conv3_k, dim3(mwt_blocks(ncell, 256)), dim3(256), 0, MWT_STREAM, x, wp, cb48, lop, lb, out, ncell, Nx, Ny, T,
-                       accumulate);
+    hipLaunchKernelGGL(mwt_conv3_k<MWT_CONV_EVAL>, dim3(mwt_blocks(ncell, 256)), dim3(256), 0, MWT_STREAM, x, wp, cb48, lop, lb, out,
+                       static_cast<float*>(nullptr), ncell, Nx, Ny, T, accumulate);
     RPB_CHECK_LAUNCH("rpb_mwt_conv3");
 }
 

@@ -52,7 +52,10 @@ def load_model(train_dataset, device="cpu", **kwargs):
         kwargs["shape_in"] = input_shape                      # load_model.py:93-107
         kwargs["shape_out"] = output_shape
         kwargs.pop("config", None)
+        hip_training = kwargs.pop("hip_training", False)
         model = MWT3d(**kwargs).to(device)
+        if hip_training:                                      # opt-in: the HIP training step
+            model.enable_training()
     elif model_name == "deeponet":
         from .deeponet import DeepONet
         model = DeepONet(shape_in=input_shape, shape_out=output_shape, input_channels=input_shape[-1],       # load_model.py:132-143

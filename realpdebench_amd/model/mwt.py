@@ -2,8 +2,11 @@
 realpdebench/model/MWT_libs/models.py:498-790, built by ``load_model`` like model/load_model.py:93-107) for the configuration family of
 the reference's ``configs/*/mwt.yaml``: ``k: 3, alpha: 5, c: 4, nCZ: 4, L: 0, base: legendre``.
 
-Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training backward is not built:
-every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph.
+Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default every attempt to
+backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph.
+``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
+``train_loss`` then run through ``_common.HipFunction``; the adjoints of the wavelet maps and of the DFT stages are the forward's own
+launches on transposed tables, the rest is ``csrc/rpb_mwt_train.hip``.
 
 Pipeline (activations channels-last fp32 ``[B][Nx][Ny][T][36]``, 36 = (c, k^2) = (4, 9); every product runs in a HIP kernel of
 ``csrc/rpb_mwt.hip``; no reference permute survives):
@@ -33,10 +36,10 @@ import torch.nn as nn
 from numpy.polynomial import Polynomial
 from numpy.polynomial import legendre as npleg
 
-from .. import _lib
+from .. import _lib, ops
 from ..dft import _fwd_complex, _fwd_real, _inv_complex, _inv_real
 from ..ops import _p, _stream
-from ._common import EvalOnly
+from ._common import EvalOnly, HipFunction
 from .model import Model
 
 I16, I32 = torch.int16, torch.int32
@@ -109,6 +112,17 @@ def cz_buffers(k, base="legendre"):
     }
 
 
+def adjoint_tables(ec_d, ec_s, rc):
+    """The tables on which ``reconstruct`` / ``decompose`` are each other's adjoints (the wavelet maps are constant; k^2 = 9).
+    ``rc_adj`` [4][18][9]: ``reconstruct(0, g_s, g_d, rc_adj)`` is the adjoint of ``decompose`` (child j reads ec_s / ec_d rows 9j..9j+8,
+    transposed).  ``ec_d_adj``, ``ec_s_adj`` [36][9]: ``decompose(g, ec_d_adj, ec_s_adj)`` gives (g_ud, g_(x + us)) of ``reconstruct``
+    (rows 9..17 / 0..8 of every ``rc[j]``, transposed).  ``rc``: the four maps in the order ee, eo, oe, oo."""
+    rc_adj = torch.stack([torch.cat([ec_s[9 * j:9 * j + 9].t(), ec_d[9 * j:9 * j + 9].t()]) for j in range(4)]).contiguous()
+    ec_d_adj = torch.cat([r[9:18].t() for r in rc]).contiguous()
+    ec_s_adj = torch.cat([r[0:9].t() for r in rc]).contiguous()
+    return rc_adj, ec_d_adj, ec_s_adj
+
+
 # ----------------------------------------------------------------------------------------------------------- corner-block table
 def _axis_rows(n, modes):
     """Retained frequency rows of a two-sided axis of length ``n`` and, per row, (high, weight index): ``[:l]`` reads weight rows
@@ -146,6 +160,14 @@ class LevelPlan:
         self.GY = f(_inv_complex(Ny, self.ky))              # [2 Ny, 2 KY]
         self.GT = f(_inv_real(T, kt, float(Nx) * Ny * T))   # [T, 2 m]: c2r of irfftn incl. 1 / (Nx Ny T)
         self.tab = torch.from_numpy(tab).to(device)
+        self._adj = {}
+
+    def adj(self, name):
+        """The transposed stage matrix ``name``: the stages are constant linear maps, so the adjoint of an ``rpb_mwt_axis`` launch is
+        the same launch on this table (the training step; built once per plan)."""
+        if name not in self._adj:
+            self._adj[name] = getattr(self, name).t().contiguous()
+        return self._adj[name]
 
 
 # ----------------------------------------------------------------------------------------------------------- parameter tree
@@ -184,6 +206,8 @@ class _CZ(nn.Module):
 class MWT3d(EvalOnly, Model):
     batch_independent = True      # no batch statistics are ever computed (BN is never called)
     training_unavailable = EvalOnly.TRAIN_MSG.format("MWT", "MWT3d")
+    hip_training = False          # enable_training() sets it on the instance
+    dp_unavailable = None         # (enabled instances: why trainer.make_trainer refuses more than one rank)
 
     def __init__(self, k=3, alpha=2, c=1, nCZ=3, L=0, base="legendre", initializer=None, shape_in=None, shape_out=None, **kwargs):
         super().__init__()
@@ -229,13 +253,47 @@ class MWT3d(EvalOnly, Model):
         forward: ``"f32"`` (default, the parity path: ``rpb_mwt_conv3`` on the fp32 MFMA), ``"bf16x3"`` (opt-in: operands as three bf16
         planes, ``hi + mid + lo`` exact, six products per fp32 product, fp32 accumulation) or ``"f16x2"`` (opt-in: operands as two fp16
         planes of the tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_mwt3x.hip).  Everything else in
-        the forward is unchanged; training stays refused under every mode."""
+        the forward is unchanged; training stays refused under every mode, and the opt-in training step (``enable_training()``) runs
+        the ``"f32"`` kernels whatever is selected here."""
         if arith not in ARITHS:
             raise ValueError(f"arith must be 'f32', 'bf16x3' or 'f16x2', got {arith!r}")
         self.arith = arith
         return self
 
+    # ------------------------------------------------------------------ the opt-in training step
+    def enable_training(self):
+        """Opt this instance into the HIP training step (``hip_training: true`` in a config).  In ``train()``
+        mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction``, always on the ``"f32"`` kernels whatever
+        ``set_arith`` says.  No batch statistics exist (``BN.*`` is never called), so the instance keeps ``batch_independent`` and
+        ``micro_batch`` works; more than one rank is refused (the step has only been verified on one)."""
+        self.hip_training = True
+        self.training_unavailable = None
+        self.dp_unavailable = "MWT3d training has only been verified on one rank: data-parallel training is not built, run it on one rank"
+        return self
+
+    def _require_eval(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(type(self).training_unavailable)
+
+    def train_loss(self, input, target):
+        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
+        if self.hip_training and self.training:
+            return Model.train_loss(self, input, target)
+        if torch.is_grad_enabled():
+            raise NotImplementedError(type(self).training_unavailable)
+        return Model.train_loss(self, input, target)
+
     # ------------------------------------------------------------------ checkpoints (models.py:791-844)
+    def state_dict(self, *args, **kwargs):
+        """The reference's names, shapes and dtypes.  Inside ``ArenaTrainer`` the complex64 weights view the one fp32 allocation every
+        other parameter views, and ``torch.save`` refuses two dtypes on one storage: such entries are handed out as copies."""
+        sd = super().state_dict(*args, **kwargs)
+        if not kwargs.get("keep_vars", False):
+            for k, v in sd.items():
+                if torch.is_tensor(v) and v.is_complex() and v.untyped_storage().nbytes() > v.numel() * v.element_size():
+                    sd[k] = v.clone()
+        return sd
+
     def load_checkpoint(self, checkpoint_path, device="cpu"):
         """Key and shape matching as in the reference: entries whose name and shape agree are loaded, the rest are reported and left.
         Returns the bookkeeping entries like the other models; a bare weights file (which the reference's method accepts too) gives
@@ -260,10 +318,16 @@ class MWT3d(EvalOnly, Model):
 
     def _prep(self, device):
         """The kernel-side layouts; the 16-bit planes of the convolution weights only for the selected arithmetic."""
-        return self._layouts.get("prep", list(self.parameters()) + list(self.buffers()), lambda: self._build_prep(device),
+        return self._layouts.get("prep", list(self.parameters()) + list(self.buffers()), lambda: self._build_prep(device, self.arith),
                                  extra=self.arith)
 
-    def _build_prep(self, device):
+    def _prep_train(self, device):
+        """The layouts of the training step: the ``"f32"`` ones plus the transposed wavelet tables, the flipped and transposed
+        convolution taps and the ``Lo`` weights as they are."""
+        return self._layouts.get("prep_train", list(self.parameters()) + list(self.buffers()),
+                                 lambda: self._build_prep(device, "f32", train=True))
+
+    def _build_prep(self, device, arith, train=False):
         f = dict(device=device, dtype=torch.float32)
         czs = []
         for cz in self.MWT_CZ:
@@ -276,8 +340,13 @@ class MWT3d(EvalOnly, Model):
                 cb = torch.zeros(48, **f)
                 cb[:36] = m.conv[0].bias.detach()
                 d[name] = (wp, cb, lop, m.Lo.bias.detach().contiguous())
-                if self.arith != "f32":           # the A operand as 16-bit planes, only for the selected mode
-                    d[name] += self.k_conv3_wprep(m.conv[0].weight.detach().contiguous(), self.arith)
+                if arith != "f32":                # the A operand as 16-bit planes, only for the selected mode
+                    d[name] += self.k_conv3_wprep(m.conv[0].weight.detach().contiguous(), arith)
+                if train:                         # the data gradient: the same main loop on w'[i][o][26 - tap] = w[o][i][tap]
+                    d[name + "d"] = self.k_conv3_dgrad_wprep(m.conv[0].weight.detach())
+            if train:
+                d["lo"] = {name: getattr(cz, name).Lo.weight.detach().contiguous() for name in ("A", "B", "C")}
+                d["rc_adj"], d["ec_d_adj"], d["ec_s_adj"] = adjoint_tables(cz.ec_d, cz.ec_s, [cz.rc_ee, cz.rc_eo, cz.rc_oe, cz.rc_oo])
             A = cz.A
             ws = torch.stack([getattr(A, f"weights{i}").detach() for i in range(1, 5)])          # [4][i][o][x][y][t]
             d["Wt"] = torch.view_as_real(ws.permute(0, 3, 4, 5, 1, 2).contiguous()).contiguous()  # [4][x][y][t][i][o][2]
@@ -372,8 +441,9 @@ class MWT3d(EvalOnly, Model):
         return out
 
     @staticmethod
-    def k_spectral(d, plan, Wt, loT, lb, out=None):
-        """sparseKernelFT3d on ``d`` [B][Nx][Ny][T][36]; ``out`` given = accumulate into it."""
+    def k_spectral(d, plan, Wt, loT, lb, out=None, keep=None):
+        """sparseKernelFT3d on ``d`` [B][Nx][Ny][T][36]; ``out`` given = accumulate into it.  ``keep`` (a dict; the training step)
+        receives the spectrum ``X`` and ``rv`` = the ReLU output in front of Lo (rpb_mwt_spec_out_keep: the same kernel text)."""
         B, Nx, Ny, T, C = d.shape
         m, KX, KY = plan.modes, plan.KX, plan.KY
         y = MWT3d.k_axis(d, plan.FT, B * Nx * Ny, C)                        # [B][Nx][Ny][(ri, kt)][36]
@@ -388,9 +458,127 @@ class MWT3d(EvalOnly, Model):
         acc = out is not None
         if out is None:
             out = torch.empty_like(d)
+        nbytes, flops = 4 * d.numel() * (2 if acc else 1) + 4 * z.numel(), 2 * d.numel() * (2 * m + C)
+        if keep is not None:
+            keep["X"], keep["rv"] = X, torch.empty_like(d)
+            _lib.call("rpb_mwt_spec_out_keep", _p(z), _p(plan.GT), _p(loT), _p(lb), _p(out), _p(keep["rv"]), B * Nx * Ny, T, 2 * m, int(acc),
+                      _stream(), label="mwt_spec_out[keep]", nbytes=nbytes + 4 * d.numel(), flops=flops)
+            return out
         _lib.call("rpb_mwt_spec_out", _p(z), _p(plan.GT), _p(loT), _p(lb), _p(out), B * Nx * Ny, T, 2 * m, int(acc), _stream(),
-                  label="mwt_spec_out", nbytes=4 * d.numel() * (2 if acc else 1) + 4 * z.numel(), flops=2 * d.numel() * (2 * m + C))
+                  label="mwt_spec_out", nbytes=nbytes, flops=flops)
         return out
+
+    # ------------------------------------------------------------------ the kernels of the training step (csrc/rpb_mwt_train.hip)
+    @staticmethod
+    def k_conv3_keep(x, pack, out=None):
+        """``k_conv3`` on the fp32 MFMA that also returns z = ReLU(conv(x) + b) [B][Nx][Ny][T][36]: (out, z)."""
+        wp, cb, lop, lb = pack[:4]
+        B, Nx, Ny, T, _ = x.shape
+        acc = out is not None
+        if out is None:
+            out = torch.empty_like(x)
+        z = torch.empty_like(x)
+        _lib.call("rpb_mwt_conv3_keep", _p(x), _p(wp), _p(cb), _p(lop), _p(lb), _p(out), _p(z), B, Nx, Ny, T, int(acc), _stream(),
+                  label="mwt_conv3[keep]", nbytes=4 * x.numel() * (4 if acc else 3), flops=2 * x.numel() * (27 * 36 + 36))
+        return out, z
+
+    @staticmethod
+    def k_conv3_dgrad_wprep(w):
+        """Conv3d weight [36][36][3][3][3] -> the lane-ordered A operand of the data gradient: the taps flipped, the channels swapped."""
+        wd = w.transpose(0, 1).flip(2, 3, 4).contiguous()
+        wpd = torch.empty(27 * 9 * 3 * 64, device=w.device, dtype=torch.float32)
+        unused = torch.empty(3 * 4 * 3 * 64, device=w.device, dtype=torch.float32)       # (the Lo half of the prep kernel's output)
+        _lib.call("rpb_mwt_conv3_wprep", _p(wd), _p(wd), _p(wpd), _p(unused), _stream())
+        return wpd
+
+    @staticmethod
+    def k_conv3_dgrad(g, wpd, out=None):
+        """Conv3d(36, 36, 3, padding=1) of ``g`` on the taps of ``k_conv3_dgrad_wprep``; ``out`` given = accumulate into it."""
+        B, Nx, Ny, T, _ = g.shape
+        acc = out is not None
+        if out is None:
+            out = torch.empty_like(g)
+        _lib.call("rpb_mwt_conv3_dgrad", _p(g), _p(wpd), _p(out), B, Nx, Ny, T, int(acc), _stream(), label="mwt_conv3_dgrad",
+                  nbytes=4 * g.numel() * (3 if acc else 2), flops=2 * g.numel() * 27 * 36)
+        return out
+
+    @staticmethod
+    def k_conv3_wgrad(g, x):
+        """(dW [36][36][3][3][3], db [36]) of the convolution from g_z and its input, both [B][Nx][Ny][T][36]."""
+        B, Nx, Ny, T, _ = x.shape
+        L = 36 * 36 * 27 + 36
+        splits = _lib.query("rpb_mwt_conv3_wgrad_splits", B * Nx * Ny * T)
+        part = torch.empty(splits, L, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_conv3_wgrad", _p(g), _p(x), _p(part), B, Nx, Ny, T, _stream(), label="mwt_conv3_wgrad",
+                  nbytes=4 * 27 * 2 * x.numel(), flops=2 * x.numel() * 27 * 36)
+        tot = torch.empty(L, device=x.device, dtype=torch.float32)
+        ops.reduce_partials(part, splits, L, out_f32=tot)
+        return tot[:36 * 36 * 27].view(36, 36, 3, 3, 3), tot[36 * 36 * 27:]
+
+    @staticmethod
+    def k_lo_bwd(gout, z, lo):
+        """(g_z, dLo [36][36], dlb [36]): g_z = (g_out Lo) [z > 0] on cells [..][36]; ``lo`` = Linear.weight."""
+        ncell = z.numel() // 36
+        rows = _lib.query("rpb_mwt_lo_bwd_rows", ncell)
+        L = 36 * 36 + 36
+        gz = torch.empty_like(z)
+        part = torch.empty(rows, L, device=z.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_lo_bwd", _p(gout), _p(z), _p(lo), _p(gz), _p(part), ncell, _stream(), label="mwt_lo_bwd",
+                  nbytes=12 * z.numel(), flops=2 * z.numel() * 72)
+        tot = torch.empty(L, device=z.device, dtype=torch.float32)
+        ops.reduce_partials(part, rows, L, out_f32=tot)
+        return gz, tot[:36 * 36].view(36, 36), tot[36 * 36:]
+
+    @staticmethod
+    def k_modes_bwd(X, gY, Wt, tab, dWt, B, NB):
+        """g_X (like X) of rpb_mwt_modes; ``dWt`` (the gradient in the Wt layout, zeroed by the caller) += this level's share."""
+        gX = torch.empty_like(X)
+        _lib.call("rpb_mwt_modes_bwd", _p(X), _p(gY), _p(Wt), _p(tab, I32), _p(gX), _p(dWt), B, NB, _stream(), label="mwt_modes_bwd",
+                  nbytes=24 * B * NB * 36 + 24 * NB * 36 * 36, flops=16 * B * NB * 36 * 36)
+        return gX
+
+    @staticmethod
+    def k_spectral_bwd(gv, X, plan, Wt, dWt):
+        """Backward of ``k_spectral`` behind its ReLU: g_v [B][Nx][Ny][T][36] (from ``k_lo_bwd``) -> g_d; the seven linear stages are
+        rpb_mwt_axis on the transposed matrices (``LevelPlan.adj``) around rpb_mwt_modes_bwd."""
+        B, Nx, Ny, T, C = gv.shape
+        m, KX, KY = plan.modes, plan.KX, plan.KY
+        g = MWT3d.k_axis(gv, plan.adj("GT"), B * Nx * Ny, C)
+        g = MWT3d.k_axis(g, plan.adj("GY"), B * Nx, m * C)
+        g = MWT3d.k_axis(g, plan.adj("GX"), B, KY * m * C)
+        g = MWT3d.k_modes_bwd(X, g, Wt, plan.tab, dWt, B, KX * KY * m)
+        g = MWT3d.k_axis(g, plan.adj("FX"), B, KY * m * C)
+        g = MWT3d.k_axis(g, plan.adj("FY"), B * Nx, m * C)
+        return MWT3d.k_axis(g, plan.adj("FT"), B * Nx * Ny, C).view(B, Nx, Ny, T, C)
+
+    @staticmethod
+    def k_head_bwd(x, gout, w0t, b0, w1, Cout, r):
+        """(g_x, dLc1 [dout][128], db1, dLc0 [128][36], db0) of ``k_head``; the hidden layer is recomputed."""
+        B, Nx, Ny, T, _ = x.shape
+        dout = Cout * r
+        rows = _lib.query("rpb_mwt_head_bwd_rows", B * Nx * Ny * T)
+        L = dout * 128 + dout + 128 * 36 + 128
+        gx = torch.empty_like(x)
+        part = torch.empty(rows, L, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_head_bwd", _p(x), _p(gout), _p(w0t), _p(b0), _p(w1), _p(gx), _p(part), B, Nx, Ny, T, Cout, r, _stream(),
+                  label="mwt_head_bwd", nbytes=4 * (2 * x.numel() + gout.numel()), flops=2 * B * Nx * Ny * T * 128 * (3 * 36 + 2 * dout))
+        tot = torch.empty(L, device=x.device, dtype=torch.float32)
+        ops.reduce_partials(part, rows, L, out_f32=tot)
+        o1, o2 = dout * 128, dout * 128 + dout
+        return gx, tot[:o1].view(dout, 128), tot[o1:o2], tot[o2:o2 + 128 * 36].view(128, 36), tot[o2 + 128 * 36:]
+
+    @staticmethod
+    def k_lift_wgrad(g, x):
+        """(dLk [36][Cin], db [36]) from g [B][H][W][T][36] and the model input x [B][T][H][W][Cin]."""
+        B, T, H, W, Cin = x.shape
+        rows = _lib.query("rpb_mwt_lift_wgrad_rows", B * T * H * W)
+        L = 36 * Cin + 36
+        part = torch.empty(rows, L, device=x.device, dtype=torch.float32)
+        _lib.call("rpb_mwt_lift_wgrad", _p(g), _p(x), _p(part), B, T, H, W, Cin, _stream(), label="mwt_lift_wgrad",
+                  nbytes=4 * (g.numel() + x.numel()), flops=2 * g.numel() * (Cin + 1))
+        tot = torch.empty(L, device=x.device, dtype=torch.float32)
+        ops.reduce_partials(part, rows, L, out_f32=tot)
+        return tot[:36 * Cin].view(36, Cin), tot[36 * Cin:]
 
     @staticmethod
     def k_head(x, w0t, b0, w1, b1, Cout, r):
@@ -422,7 +610,115 @@ class MWT3d(EvalOnly, Model):
             keep["Ud"], keep["Us"] = Ud, Us
         return x
 
+    # ------------------------------------------------------------------ the training step (through _common.HipFunction)
+    def _cz_forward_train(self, x, p, relu, rec):
+        """``_cz_forward`` on the ``"f32"`` kernels; ``rec`` (a dict, or None under no_grad) receives per level d, s, the spectrum X and
+        the three ReLU outputs rv (A), zB, zC.  The keep-variants are the same kernel texts: the output is bit-equal to the eval forward's."""
+        if rec is None:
+            saved, self.arith = self.arith, "f32"
+            try:
+                return self._cz_forward(x, p, relu)
+            finally:
+                self.arith = saved
+        Ud, Us, levels = [], [], []
+        for i in range(self.ns):
+            d, x = self.k_decompose(x, p["ec_d"], p["ec_s"])
+            lv = {"d": d, "s": x}
+            ud = self.k_spectral(d, self._plan(d.shape[1], d.shape[2], d.device), p["Wt"], p["loT"], p["lb"], keep=lv)
+            _, lv["zB"] = self.k_conv3_keep(x, p["B"], out=ud)
+            us, lv["zC"] = self.k_conv3_keep(d, p["C"])
+            Ud.append(ud)
+            Us.append(us)
+            levels.append(lv)
+        x = self.k_coarse(x, p["T0w"], p["T0b"])
+        for i in range(self.ns - 1, -1, -1):
+            x = self.k_reconstruct(x, Us[i], Ud[i], p["rc"], relu and i == 0)
+        rec["levels"], rec["out"] = levels, x          # out: the next block's input; it holds the gate of the ReLU between two blocks
+        return x
+
+    @torch.no_grad()
+    def _forward_hip(self, x, state):
+        x = x.contiguous().float()
+        p = self._prep_train(x.device)
+        h = self.k_lift(x, p["Lkw"], p["Lkb"])
+        blocks = []
+        for i, cz in enumerate(p["cz"]):
+            rec = None if state is None else {}
+            h = self._cz_forward_train(h, cz, i < self.nCZ - 1, rec)
+            blocks.append(rec)
+        if state is not None:
+            state.update(x=x, blocks=blocks)
+        return self.k_head(h, p["w0t"], p["b0"], p["w1"], p["b1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])
+
+    def _cz_backward(self, g, p, cz, rec, grads):
+        """g = dLoss/d(output of evenOdd at the finest level) -> dLoss/d(block input); the block's parameter gradients go into ``grads``.
+        A, B and C are shared by all levels: their gradients sum over levels (fixed order, coarsest first)."""
+        levels = rec["levels"]
+
+        def add(param, t):
+            grads[param] = grads[param] + t if param in grads else t
+
+        g_ud, g_us = [], []
+        for i in range(self.ns):                     # adjoint of reconstruct = decompose on the transposed rc; g_us = g_x = g_(x + us)
+            gud, g = self.k_decompose(g, p["ec_d_adj"], p["ec_s_adj"])
+            g_ud.append(gud)
+            g_us.append(g)
+        B, _, mult, T, _ = g.shape
+        g2 = (g.sum(2) if mult > 1 else g).reshape(B * T, 36)        # the coarsest x was broadcast along Ny; tiny: plain torch, as T0 is
+        s_last = levels[-1]["s"].reshape(B * T, 36 * mult)           # the row-major view rpb_mwt_coarse reads
+        add(cz.T0.weight, g2.t() @ s_last)
+        add(cz.T0.bias, g2.sum(0))
+        gs = (g2 @ p["T0w"]).reshape(B, 1, mult, T, 36)
+        dWt = torch.zeros_like(p["Wt"])
+        for i in range(self.ns - 1, -1, -1):
+            lv = levels[i]
+            d, s = lv["d"], lv["s"]
+            gv, dlo, dlb = self.k_lo_bwd(g_ud[i], lv["rv"], p["lo"]["A"])
+            add(cz.A.Lo.weight, dlo)
+            add(cz.A.Lo.bias, dlb)
+            gd = self.k_spectral_bwd(gv, lv["X"], self._plan(d.shape[1], d.shape[2], d.device), p["Wt"], dWt)
+            for name, gout, z, src in (("C", g_us[i], lv["zC"], d), ("B", g_ud[i], lv["zB"], s)):
+                m = getattr(cz, name)
+                gz, dlo, dlb = self.k_lo_bwd(gout, z, p["lo"][name])
+                dW, db = self.k_conv3_wgrad(gz, src)
+                for param, t in ((m.Lo.weight, dlo), (m.Lo.bias, dlb), (m.conv[0].weight, dW), (m.conv[0].bias, db)):
+                    add(param, t)
+                self.k_conv3_dgrad(gz, p[name + "d"], out=gd if name == "C" else gs)      # d collects A and C; s collects B and the coarser level
+            zero = torch.zeros(B, d.shape[1], 1, T, 36, device=d.device, dtype=torch.float32)
+            gs = self.k_reconstruct(zero, gs, gd, p["rc_adj"], False)                       # adjoint of decompose
+        gw = torch.view_as_complex(dWt).permute(0, 4, 5, 1, 2, 3)    # [4][x][y][t][i][o] -> [4][i][o][x][y][t], once per block
+        for j in range(4):
+            grads[getattr(cz.A, f"weights{j + 1}")] = gw[j].contiguous()
+        return gs
+
+    @torch.no_grad()
+    def _backward_hip(self, state, g_out, need_gx=False):
+        """{parameter: gradient} from dLoss/d(out).  ``state`` is only read: a second call gives bit-equal gradients (no kernel uses
+        atomics and every sum has a fixed order).  BN.* has no gradient: it is never called."""
+        if need_gx:
+            raise NotImplementedError("MWT3d training computes no input gradient (no trainer asks for one)")
+        x, blocks = state["x"], state["blocks"]
+        p = self._prep_train(x.device)
+        grads = {}
+        g, grads[self.Lc1.weight], grads[self.Lc1.bias], grads[self.Lc0.weight], grads[self.Lc0.bias] = self.k_head_bwd(
+            blocks[-1]["out"], g_out, p["w0t"], p["b0"], p["w1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])
+        for i in range(self.nCZ - 1, -1, -1):
+            if i < self.nCZ - 1:
+                g = g * (blocks[i]["out"] > 0)       # the ReLU between two blocks, gated by the saved (ReLU'd) block output
+            g = self._cz_backward(g, p["cz"][i], self.MWT_CZ[i], blocks[i], grads)
+        grads[self.Lk.weight], grads[self.Lk.bias] = self.k_lift_wgrad(g, x)
+        return grads
+
     def forward(self, x):
+        if self.hip_training and self.training:      # the opt-in training step, through HipFunction; always the "f32" kernels
+            if tuple(x.shape[1:]) != self.shape_in:
+                raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(x.shape)}")
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise NotImplementedError("MWT3d training computes no input gradient (no trainer asks for one)")
+            self._require_hip(x)
+            if not torch.is_grad_enabled():
+                return self._forward_hip(x, None)
+            return HipFunction.apply(x, self, *self.parameters())
         self._require_eval(x)
         self._require_hip(x)
         if tuple(x.shape[1:]) != self.shape_in:

@@ -123,6 +123,18 @@ class Trainer:
         return ck
 
 
+def arena_floats(t):
+    """A parameter's values as the flat fp32 run the arena holds: complex64 as (re, im) pairs."""
+    return (torch.view_as_real(t) if t.is_complex() else t).reshape(-1)
+
+
+def arena_view(flat, offset, like):
+    """The view of the fp32 arena ``flat`` at ``offset`` with the shape and dtype of ``like`` (fp32, or complex64 over 2 * numel floats)."""
+    if like.is_complex():
+        return torch.view_as_complex(flat[offset:offset + 2 * like.numel()].view(*like.shape, 2))
+    return flat[offset:offset + like.numel()].view(like.shape)
+
+
 class ArenaTrainer:
     """Training step for the models whose parameters are ordinary ``nn.Parameter`` tensors (Transolver, Galerkin Transformer,
     U-Net) -- the reference's loop body (train.py:323-334) with the optimizer and the gradient exchange on the arena design
@@ -159,21 +171,24 @@ class ArenaTrainer:
         self.betas, self.eps, self.clip = betas, eps, float(clip_grad_norm or 0.0)
         self.iteration = 0
         self.params = [p for p in model.parameters() if p.requires_grad]
-        if any(p.dtype != torch.float32 for p in self.params):
-            raise TypeError("ArenaTrainer: fp32 parameters only")
+        if any(p.dtype not in (torch.float32, torch.complex64) for p in self.params):
+            raise TypeError("ArenaTrainer: fp32 parameters only (and complex64 ones as pairs of fp32)")
         dev = self.params[0].device
+        # a complex64 parameter (MWT3d's spectral weights) takes 2 * numel floats: Adam then acts on real and imaginary parts
+        # independently, which is what torch.optim.Adam does with complex parameters
+        self.nfloat = [p.numel() * (2 if p.is_complex() else 1) for p in self.params]
         offs, off = [], 0
-        for p in self.params:
+        for n in self.nfloat:
             offs.append(off)
-            off += (p.numel() + 63) // 64 * 64                     # 256 B-aligned segments
+            off += (n + 63) // 64 * 64                             # 256 B-aligned segments
         self.offsets, self.total = offs, off
         self.flat = torch.zeros(off, device=dev)
         with torch.no_grad():
-            for p, o in zip(self.params, offs):
-                self.flat[o:o + p.numel()].copy_(p.data.reshape(-1))
-                p.data = self.flat[o:o + p.numel()].view(p.shape)   # the parameter now LIVES in the arena
+            for p, o, n in zip(self.params, offs, self.nfloat):
+                self.flat[o:o + n].copy_(arena_floats(p.data))
+                p.data = arena_view(self.flat, o, p)                # the parameter now LIVES in the arena
         self.grad = torch.zeros_like(self.flat)
-        self.gviews = [self.grad[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, offs)]
+        self.gviews = [arena_view(self.grad, o, p) for p, o in zip(self.params, offs)]
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
         # ---- data parallel
@@ -353,7 +368,7 @@ class ArenaTrainer:
         self.exp_avg_sq.copy_(state["exp_avg_sq"])
         if iteration is not None:
             self.iteration = int(iteration)
-        flags = torch.stack([self.exp_avg_sq[o:o + p.numel()].any() for p, o in zip(self.params, self.offsets)])
+        flags = torch.stack([self.exp_avg_sq[o:o + n].any() for n, o in zip(self.nfloat, self.offsets)])
         self._had_grad = [bool(f) for f in flags.cpu()]
 
 

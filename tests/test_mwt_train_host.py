@@ -1,0 +1,229 @@
+"""MWT3d training step, host side (no GPU).
+
+* The adjoint identities the backward pipeline rests on, in fp64 on tests/mwt_restatement.py: ``reconstruct`` on
+  ``adjoint_tables(...)[0]`` is the adjoint of ``decompose``, ``decompose`` on the other two tables is the adjoint of ``reconstruct``
+  (the Ny-broadcast of the coarsest level of a W = 2H grid included), ``axis`` on the transposed matrix is the adjoint of ``axis``.
+  Tolerance 1e-12 (both sides fp64, a few hundred terms).
+* fp64 autograd of ``mwt_restatement.forward`` against the reference's fp64 gradients (tests/golden/mwt_train_small.npz), within the
+  project's MWT rule max(1e-5, 4 x selferr) per tensor.
+* The exactly-zero entries of the spectral weights' gradients are the ones ``corner_table`` predicts.
+* The opt-in plumbing that needs no GPU, the flipped and transposed taps against ``conv_transpose3d``, the complex64 arena view,
+  and that every case of tests/mwt_train_cases.py is well conditioned."""
+import math
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mwt_common as MC                           # noqa: E402
+import mwt_restatement as R                       # noqa: E402
+import mwt_train_cases as TK                      # noqa: E402
+import mwt_train_common as TC                     # noqa: E402
+from mwt_train_helpers import GOLD, TRAIN_MSG, compare_gradients, new_model, tol      # noqa: E402
+from realpdebench_amd.model import mwt as M       # noqa: E402
+
+ADJ_TOL = 1e-12
+
+
+def _r(seed, *shape):
+    return torch.rand(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * 2 - 1
+
+
+def _tables():
+    buf = {k: v.double() for k, v in M.cz_buffers(3).items()}
+    rc = torch.stack([buf["rc_ee"], buf["rc_eo"], buf["rc_oe"], buf["rc_oo"]])
+    return buf["ec_d"], buf["ec_s"], rc, M.adjoint_tables(buf["ec_d"], buf["ec_s"], list(rc))
+
+
+def _close(a, b):
+    return abs(float(a) - float(b)) <= ADJ_TOL * max(abs(float(a)), abs(float(b)), 1.0)
+
+
+@pytest.mark.parametrize("shape", [(2, 4, 8, 8), (1, 1, 2, 9), (2, 3, 5, 2)], ids=str)
+def test_reconstruct_on_transposed_tables_is_the_adjoint_of_decompose(shape):
+    B, Nx, Ny, T = shape
+    ec_d, ec_s, _, (rc_adj, _, _) = _tables()
+    x, gd, gs = _r(1, B, 2 * Nx, 2 * Ny, T, 36), _r(2, B, Nx, Ny, T, 36), _r(3, B, Nx, Ny, T, 36)
+    d, s = R.decompose(x, ec_d, ec_s)
+    back = R.reconstruct(torch.zeros(B, Nx, 1, T, 36, dtype=torch.float64), gs, gd, rc_adj, False)
+    assert _close((d * gd).sum() + (s * gs).sum(), (x * back).sum())
+
+
+@pytest.mark.parametrize("shape,xNy", [((2, 4, 8, 8), 8), ((2, 1, 2, 8), 1), ((1, 1, 4, 9), 1), ((2, 3, 5, 2), 5)], ids=str)
+def test_decompose_on_transposed_tables_is_the_adjoint_of_reconstruct(shape, xNy):
+    B, Nx, Ny, T = shape
+    _, _, rc, (_, ec_d_adj, ec_s_adj) = _tables()
+    x, us, ud, g = _r(4, B, Nx, xNy, T, 36), _r(5, B, Nx, Ny, T, 36), _r(6, B, Nx, Ny, T, 36), _r(7, B, 2 * Nx, 2 * Ny, T, 36)
+    out = R.reconstruct(x, us, ud, rc, False)
+    g_ud, g_xus = R.decompose(g, ec_d_adj, ec_s_adj)
+    g_x = g_xus.sum(2, keepdim=True) if xNy != Ny else g_xus            # the broadcast along Ny sums in the adjoint
+    assert _close((out * g).sum(), (ud * g_ud).sum() + (us * g_xus).sum() + (x * g_x).sum())
+
+
+@pytest.mark.parametrize("outer,O,K,inner", [(11, 3, 5, 7), (1, 10, 16, 180), (4, 8, 10, 36)])
+def test_axis_on_the_transposed_matrix_is_the_adjoint_of_axis(outer, O, K, inner):
+    x, Mx, g = _r(8, outer, K, inner), _r(9, O, K), _r(10, outer, O, inner)
+    y = R.axis(x.reshape(-1), Mx, outer, inner)
+    back = R.axis(g.reshape(-1), Mx.t().contiguous(), outer, inner)
+    assert _close((y * g.reshape(-1)).sum(), (x.reshape(-1) * back).sum())
+
+
+def test_level_plan_caches_its_transposed_matrices():
+    plan = M.LevelPlan(4, 8, 8, 5)
+    for name in ("FT", "FY", "FX", "GX", "GY", "GT"):
+        assert torch.equal(plan.adj(name), getattr(plan, name).t()) and plan.adj(name).is_contiguous() and plan.adj(name) is plan.adj(name)
+
+
+# ------------------------------------------------------------------------------------------------ the whole backward, fp64
+def _autograd(case):
+    shape_in, shape_out = TC.CASES[case]
+    real, none = TC.param_names(case)
+    sd = {k: (v.to(torch.complex128) if v.is_complex() else v.double() if v.is_floating_point() else v) for k, v in TC.weights(case).items()}
+    for k in real:
+        sd[k].requires_grad_()
+    x, y = (t.double() for t in TC.case_inputs(case))
+    loss = ((R.forward(sd, x, shape_in, shape_out, TC.NCZ) - y) ** 2).mean()
+    loss.backward()
+    return loss, sd, real, none
+
+
+@pytest.fixture(scope="module")
+def autograd_runs():
+    return {case: _autograd(case) for case in TC.CASES}
+
+
+@pytest.mark.parametrize("case", list(TC.CASES))
+def test_restatement_autograd_matches_reference(autograd_runs, case):
+    loss, sd, real, none = autograd_runs[case]
+    assert [str(n) for n in GOLD[f"{case}_none"]] == none and all(k.startswith("BN.") for k in none)
+    e = abs(float(loss.detach()) - float(GOLD[f"{case}_loss"])) / float(GOLD[f"{case}_loss"])
+    print(f"case {case}: loss rel {e:.2e} (tol {tol(GOLD[case + '_loss_selferr']):.1e})")
+    assert e < tol(GOLD[f"{case}_loss_selferr"])
+    assert all(sd[k].grad is not None for k in real)
+    misses = compare_gradients(case, {k: sd[k].grad for k in real})
+    assert not misses, misses
+
+
+@pytest.mark.parametrize("case", list(TC.CASES))
+def test_zero_gradients_of_the_spectral_weights_are_what_the_corner_table_predicts(autograd_runs, case):
+    """An entry of weights1..4 has a gradient iff some level's table maps a retained bin to it: entries the crop l = min(alpha, N//2+1)
+    never reaches, and entries that lose the overlap to the high slice, are exact zeros."""
+    _, sd, _, _ = autograd_runs[case]
+    _, H, W, _ = TC.CASES[case][0]
+    m = MC.ALPHA
+    reached = torch.zeros(4 * m ** 3, dtype=torch.bool)
+    for i in range(int(math.log2(H))):
+        Nx, Ny = H >> (i + 1), W >> (i + 1)
+        reached[torch.from_numpy(M.corner_table(Nx, Ny, m)[2]).long()] = True
+    reached = reached.view(4, m, m, m)
+    assert 0 < int(reached.sum()) < reached.numel()
+    for b in range(TC.NCZ):
+        for j in range(4):
+            g = sd[f"MWT_CZ.{b}.A.weights{j + 1}"].grad                  # [i][o][x][y][t]
+            nonzero = (g.abs().amax(dim=(0, 1)) > 0)
+            assert torch.equal(nonzero, reached[j]), (case, b, j)
+
+
+# ------------------------------------------------------------------------------------------------ plumbing
+class _One(torch.utils.data.Dataset):
+    def __init__(self, shape_in, shape_out):
+        self.s = (torch.zeros(*shape_in), torch.zeros(*shape_out))
+
+    def __len__(self):
+        return 1
+
+    def __getitem__(self, i):
+        return self.s
+
+
+def test_opt_in_plumbing(monkeypatch):
+    from realpdebench_amd.model import load_model
+    from realpdebench_amd.trainer import make_trainer
+    shape_in, shape_out = TC.CASES["r"]
+    x, y = torch.zeros(1, *shape_in), torch.zeros(1, *shape_out)
+    m = new_model("r")
+    assert m.batch_independent is True and not m.hip_training and TRAIN_MSG in m.training_unavailable and m.dp_unavailable is None
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        make_trainer(m, lr=1e-3, num_update=10)
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        m.train_loss(x, y)
+    assert m.enable_training() is m
+    assert m.hip_training and m.training_unavailable is None and m.batch_independent is True
+    assert "one rank" in m.dp_unavailable
+    assert TRAIN_MSG in type(m).training_unavailable and not type(m).hip_training, "the class, and every other instance, is unchanged"
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):       # eval() under grad mode still refuses
+        m.eval()(x)
+    with pytest.raises(NotImplementedError, match=TRAIN_MSG):
+        m.eval().train_loss(x, y)
+    with pytest.raises(NotImplementedError, match="no input gradient"):
+        m.train()(x.clone().requires_grad_())
+    with pytest.raises(RuntimeError, match="MI355X only"):          # train(): the HIP path, which has no CPU fallback
+        m.train()(x)
+    for arith in M.ARITHS:                                          # the arithmetic switch changes none of this
+        m.set_arith(arith)
+        with pytest.raises(RuntimeError, match="MI355X only"):
+            m.train().train_loss(x, y)
+    # more than one rank is refused by message, before anything is built
+    monkeypatch.setattr(torch.distributed, "is_initialized", lambda: True)
+    monkeypatch.setattr(torch.distributed, "get_world_size", lambda *a: 2)
+    with pytest.raises(NotImplementedError, match="only been verified on one rank"):
+        make_trainer(m, lr=1e-3, num_update=10)
+    monkeypatch.undo()
+    cfg = dict(model_name="mwt", k=3, alpha=5, c=4, nCZ=2, L=0, base="legendre")
+    assert not load_model(_One(shape_in, shape_out), **cfg).hip_training
+    assert not load_model(_One(shape_in, shape_out), hip_training=False, **cfg).hip_training
+    on = load_model(_One(shape_in, shape_out), hip_training=True, **cfg)
+    assert on.hip_training and on.batch_independent is True and on.training_unavailable is None
+
+
+def test_shipped_yamls_do_not_opt_in():
+    import yaml
+    for scenario in ("cylinder", "controlled_cylinder", "fsi", "foil", "combustion"):
+        with open(os.path.join(ROOT, "realpdebench_amd", "configs", scenario, "mwt.yaml")) as fh:
+            assert "hip_training" not in yaml.safe_load(fh)
+
+
+def test_flipped_transposed_taps_are_conv_transpose():
+    g = torch.Generator().manual_seed(36)
+    w = torch.rand(36, 36, 3, 3, 3, generator=g, dtype=torch.float64) - 0.5
+    dy = torch.rand(2, 36, 3, 4, 5, generator=g, dtype=torch.float64) - 0.5
+    want = F.conv_transpose3d(dy, w, padding=1)
+    got = F.conv3d(dy, TK.flipped_taps(w), padding=1)
+    assert float((got - want).norm() / want.norm()) < 1e-12
+
+
+def test_arena_view_round_trip():
+    from realpdebench_amd.trainer import arena_floats, arena_view
+    g = torch.Generator().manual_seed(5)
+    p = torch.complex(torch.rand(3, 2, 5, generator=g), torch.rand(3, 2, 5, generator=g))
+    q = torch.rand(7, 3, generator=g)
+    flat = torch.zeros(64 + 64)
+    flat[:60].copy_(arena_floats(p))
+    flat[64:85].copy_(arena_floats(q))
+    vp, vq = arena_view(flat, 0, p), arena_view(flat, 64, q)
+    assert vp.dtype == torch.complex64 and vp.shape == p.shape and torch.equal(torch.view_as_real(vp), torch.view_as_real(p))
+    assert vq.dtype == torch.float32 and torch.equal(vq, q)
+    flat[1] = 9.0                                                   # the view IS the arena: element 0's imaginary part
+    assert float(vp.reshape(-1)[0].imag) == 9.0 and float(vp.reshape(-1)[0].real) == float(p.reshape(-1)[0].real)
+    with pytest.raises(TypeError, match="fp32 parameters only"):
+        from realpdebench_amd.trainer import ArenaTrainer
+        lin = torch.nn.Linear(2, 2).double()
+        ArenaTrainer(lin, lr=1e-3, num_update=10)
+
+
+# ------------------------------------------------------------------------------------------------ the per-kernel cases
+@pytest.mark.parametrize("make,shape", TK.all_cases(), ids=lambda v: v.__name__ if callable(v) else str(v))
+def test_kernel_cases_are_well_conditioned(make, shape):
+    c = make(*shape)
+    r64, r32 = c.refs()
+    for key in r64:
+        for kind, e32 in zip(TK.K.MEASURES, TK.K.measures(r32[key], r64[key])):
+            assert 8 * e32 <= TK.K.BADLY_CONDITIONED, (c.name, key, kind, e32)
+    if make is TK.head_bwd_case:
+        assert TK.head_margin(c) > TK.HEAD_MARGIN, c.name
