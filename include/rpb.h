@@ -827,6 +827,35 @@ int rpb_cno_bn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, 
                              const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy, int ldd,
                              void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
 
+/*
+ * DeepONet training step (opt-in: DeepONet.enable_training()) -- the row passes of the backward pass and of the chunked output net
+ * (csrc/rpb_deeponet_train.hip; additions do not change RPB_ABI_VERSION).  The forward batch statistics are
+ * rpb_cno_bn_stats / rpb_cno_bn_finish, the forward pooling is rpb_don_bn_relu_pool with (a, b) of the batch statistics.  C in {32, 64, 128,
+ * 256}; every row pointer arrives at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed
+ * summation order (two calls are bit-equal).
+ *     rpb_don_pool_bwd: y [B][T][H][W][ldy] (the saved convolution output), v = relu(fmaf(y, a, b)).  mode 0, MaxPool3d(2): g [B][T/2][H/2]
+ *     [W/2][ldg]; gz [cell] = g [window] at the first maximum of v in (t, h, w) scan order of the window if that maximum is > 0, else 0; 0 on
+ *     the trailing frame / row / column the flooring pool drops.  mode 1, AdaptiveAvgPool3d((1, 4, 4)): g [B][4][4][ldg]; gz [cell] = (v > 0)
+ *     sum over the bins (i, j) containing (h, w) of g[i][j] / (T |bin_i| |bin_j|), bins as rpb_don_bn_relu_pool.  gz [B][T][H][W][ldz], columns
+ *     0..C-1.  part[rpb_don_train_rows()][2 C] (fp64) = per-workgroup (sum gz, sum gz xhat), xhat = (y - mean) rstd.
+ *     rpb_don_sum64: sums[L] = the rows of part[rows][L] added in a fixed order.
+ *     rpb_don_bn_bwd_apply: dy[m * ldd + c] = a (gz - sums[c] / M - xhat sums[C + c] / M), columns C..Cpad-1 written as zero; dy may be gz
+ *     itself (ldd == ldz); dbeta[c] = sums[c], dgamma[c] = sums[C + c] (may be null).
+ *     rpb_don_point_mul: x[r][j] = b[s][j] t[n][j] for the R points q = q0 + r of the B N (sample, point) pairs, s = q / N, n = q % N; t [N][p],
+ *     b [B][p], x [R][p] (a chunk may end inside a sample).  p in {64, 128, 256}.
+ *     rpb_don_point_mul_bwd: gx [R][p] = the rows of points n0..n0+R-1 of ONE sample whose branch vector is b [p]: gt[n0 + r] += gx[r] (.) b
+ *     (the caller zeroes gt and visits the samples in order on one stream) and part[rpb_don_train_rows()][p] = per-workgroup sums (formed in
+ *     fp64) of gx[r] (.) t[n0 + r]; rpb_reduce_partials (accumulate = 1) adds them into gb[s]. */
+int rpb_don_train_rows(void);
+int rpb_don_pool_bwd(const float* y, int ldy, const float* g, int ldg, const float* a, const float* b, const float* mean, const float* rstd,
+                     float* gz, int ldz, int B, int T, int H, int W, int C, int mode, double* part, void* stream);
+int rpb_don_sum64(const double* part, int rows, int L, double* sums, void* stream);
+int rpb_don_bn_bwd_apply(const float* gz, int ldz, const float* y, int ldy, const float* a, const float* mean, const float* rstd,
+                         const double* sums, long M, int C, int Cpad, float* dy, int ldd, float* dgamma, float* dbeta, void* stream);
+int rpb_don_point_mul(const float* t, const float* b, float* x, long q0, long R, int B, long N, int p, void* stream);
+int rpb_don_point_mul_bwd(const float* gx, const float* t, const float* b, float* gt, float* part, long n0, long R, long N, int p,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,12 @@ SIGNATURES = {
     "rpb_cno_bn_act_bwd_stats": (_I, "pi" + "pi" + "pppp" + "lii" + "p" + "p"),
     "rpb_cno_sum64": (_I, "p" + "ii" + "p" + "p"),
     "rpb_cno_bn_act_bwd_apply": (_I, "pi" + "pi" + "pppp" + "p" + "liiii" + "pi" + "pi" + "pp" + "p"),
+    "rpb_don_train_rows": (_I, ""),
+    "rpb_don_pool_bwd": (_I, "pi" + "pi" + "pppp" + "pi" + "iiiiii" + "p" + "p"),
+    "rpb_don_sum64": (_I, "p" + "ii" + "p" + "p"),
+    "rpb_don_bn_bwd_apply": (_I, "pi" + "pi" + "ppp" + "p" + "lii" + "pi" + "pp" + "p"),
+    "rpb_don_point_mul": (_I, "ppp" + "ll" + "il" + "i" + "p"),
+    "rpb_don_point_mul_bwd": (_I, "ppppp" + "lll" + "i" + "p"),
 }
 
 _lib = None

@@ -1,10 +1,12 @@
 """DeepONet on MI355X -- drop-in for ``realpdebench.model.deeponet.DeepONet`` (reference realpdebench/model/deeponet.py, built by
 ``load_model`` like model/load_model.py:132-143) for the reference's ``configs/*/deeponet.yaml`` (p = 64 / 128 / 256).
 
-Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  The training step is not built: every
-attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph, and
-``trainer.make_trainer`` refuses the model at construction.  Dropout is the identity and BatchNorm3d uses its running statistics in
-every mode (no batch-statistics path exists).
+Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
+every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph,
+``trainer.make_trainer`` refuses the model at construction, dropout is the identity and BatchNorm3d uses its running statistics in
+every mode.  ``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
+``train_loss`` then run through ``_common.HipFunction`` with batch-statistics BatchNorm and active dropout (``_forward_hip`` /
+``_backward_hip`` below, csrc/rpb_deeponet_train.hip); ``eval()`` mode stays the pipeline below, untouched.
 
 Pipeline (activations channels-last fp32 rows ``[B * T * H * W][C]``):
   branch  stage 1  rpb_im2col (27 C_in columns, zero-padded to a multiple of 64) + rpb_gemm3x (N = 32 zero-padded to 64)
@@ -26,13 +28,16 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import _p, _stream, conv3x_wprep
-from ._common import EvalOnly, padded_weight
+from ..ops import Sub, _p, _stream, conv3x, conv3x_wprep, reduce_partials, split3
+from ..ops import add as ops_add
+from ._common import EvalOnly, HipFunction, padded_weight, wgrad
+from .cno import flipped_weight, weight_grad_view
 from .model import Model
 
 I16 = torch.int16
 P_SUPPORTED = (64, 128, 256)
 _COL_FLOATS = 1 << 28          # stage-1 im2col buffer bound (1 GiB): larger batches run the first stage in chunks of samples
+_POINT_ROWS = 1 << 16          # training step: (sample, point) rows per chunk of the output net (its 512-wide rows: 128 MiB per buffer)
 
 
 # ----------------------------------------------------------------------------------------------------------- layouts (plain torch)
@@ -105,9 +110,22 @@ class _Trunk(nn.Module):
         self.fc = nn.Sequential(nn.Linear(3, 64), nn.ReLU(), nn.Linear(64, 128), nn.ReLU(), nn.Linear(128, p))
 
 
+def drop_seed(base, step, layer, chunk):
+    """The Philox seed of one dropout launch of the training step: ``(base + step * 2^24 + layer * 2^22 + chunk) mod 2^62``.  ``base``:
+    the instance's ``dropout_seed``; ``step``: the number of training forwards the instance has run (one per optimiser step: batch
+    statistics allow no micro-batches); ``layer``: 0 = branch.fc.2, 1 = output_net.2, 2 = output_net.5; ``chunk``: the output net's chunk of
+    points (< 2^22; 0 for the branch).  The GEMM epilogue keys Philox on (seed, element index WITHIN the launch), so a seed without the
+    chunk would repeat one mask in every chunk.  Distinct (step, layer, chunk) give distinct seeds for step < 2^38."""
+    assert 0 <= layer < 3 and 0 <= chunk < 1 << 22 and step >= 0
+    return (int(base) + (int(step) << 24) + (layer << 22) + chunk) % (1 << 62)
+
+
 class DeepONet(EvalOnly, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
     training_unavailable = EvalOnly.TRAIN_MSG.format("DeepONet", "DeepONet")
+    hip_training = False                            # enable_training() sets it on the instance
+    dp_unavailable = None                           # (enabled instances: why trainer.make_trainer refuses more than one rank)
+    _point_rows = _POINT_ROWS                       # (tests force several chunks by lowering it on an instance)
 
     def __init__(self, shape_in, shape_out, input_channels, output_channels, p, dropout_rate=0.1, device="cuda"):
         super().__init__()
@@ -130,6 +148,32 @@ class DeepONet(EvalOnly, Model):
         self.trunk = _Trunk(self.p)
         self.output_net = nn.Sequential(nn.Linear(self.p, 512), nn.ReLU(), nn.Dropout(dropout_rate), nn.Linear(512, 128), nn.ReLU(),
                                         nn.Dropout(dropout_rate), nn.Linear(128, self.output_channels))
+        self.dropout_rate = float(dropout_rate)
+        self.dropout_seed, self._drop_step, self._mask_override = 0, 0, None      # the opt-in training step, see enable_training / drop_seed
+
+    # ------------------------------------------------------------------ the opt-in training step
+    def enable_training(self, seed=None):
+        """Opt this instance into the HIP training step (batch-statistics BatchNorm, active dropout; ``hip_training: true`` in a config).
+        Batch statistics couple the samples of a step, so the instance stops declaring ``batch_independent`` (no micro-batching) and
+        refuses more than one rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for DeepONet is not built).  ``seed``:
+        the base of the dropout seeds (``drop_seed``); default: torch's initial seed, as the trainer's run was seeded.
+
+        The step number of the seeds, ``_drop_step``, counts the training forwards this INSTANCE has completed since this call: a
+        ``no_grad`` forward in ``train()`` mode uses one up like a step with a graph, a forward that raises uses none.  It is not part of
+        ``state_dict`` (the checkpoint stays the reference's), so a run resumed from a checkpoint under the same seed starts again at
+        step 0 and redraws the masks of the first steps; a caller that minds sets ``model._drop_step`` to the resumed iteration."""
+        self.hip_training = True
+        self.training_unavailable = None
+        self.batch_independent = False
+        self.dp_unavailable = ("DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, "
+                               "run it on one rank")
+        self.dropout_seed = int(torch.initial_seed() if seed is None else seed) % (1 << 62)
+        self._drop_step = 0
+        return self
+
+    def _require_eval(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(type(self).training_unavailable)
 
     # ------------------------------------------------------------------ checkpoints
     def load_checkpoint(self, checkpoint_path, device="cpu"):
@@ -280,13 +324,24 @@ class DeepONet(EvalOnly, Model):
         z = self.k_gemm(h.view(B, 4096), *prep["fc0"], 512, relu=True)
         return self.k_gemm(z, *prep["fc3"], self.p, relu=False)
 
-    def forward(self, x):
-        self._require_eval(x)
-        self._require_hip(x)
+    def check_input(self, x):
         if x.dim() != 5 or x.shape[1] != self.shape_in[0] or x.shape[-1] != self.input_channels:
             raise ValueError(f"DeepONet was built for inputs [B, {self.shape_in[0]}, H, W, {self.input_channels}], got {tuple(x.shape)}")
         if min(pooled_extents(*x.shape[1:4])[3]) < 1:
             raise ValueError(f"DeepONet: input {tuple(x.shape)} leaves an empty extent after three MaxPool3d(2)")
+
+    def forward(self, x):
+        if self.hip_training and self.training:                       # the opt-in training step: batch statistics, through HipFunction
+            self._require_hip(x)
+            self.check_input(x)
+            if not torch.is_grad_enabled():
+                return self._forward_hip(x, None)
+            if x.requires_grad:
+                raise NotImplementedError("DeepONet training computes no input gradient (no trainer asks for one)")
+            return HipFunction.apply(x, self, *self.parameters())
+        self._require_eval(x)
+        self._require_hip(x)
+        self.check_input(x)
         with torch.no_grad():
             x = x.contiguous().float()
             B, _, H, W, _ = x.shape                                   # T_out from shape_out, H and W from the input (deeponet.py:122-126)
@@ -295,3 +350,319 @@ class DeepONet(EvalOnly, Model):
             b = self.branch_forward(x, prep)
             t = self._trunk(T_out, H, W, x.device)
             return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
+
+    def train_loss(self, input, target):
+        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
+        if self.hip_training and self.training:
+            return Model.train_loss(self, input, target)
+        if torch.is_grad_enabled():
+            raise NotImplementedError(type(self).training_unavailable)
+        return Model.train_loss(self, input, target)
+
+    # ------------------------------------------------------------------ the training step (DESIGN.md section 16.1)
+    def _prep_train(self, device):
+        """The training step's layouts: they depend on the parameters alone (BatchNorm enters through the statistics kernels)."""
+        return self._layouts.get("prep_train", list(self.parameters()), lambda: self._build_prep_train(device))
+
+    def _build_prep_train(self, device):
+        """Forward operands as ``_build_prep`` (without the folded running statistics) and, per GEMM, the transposed weight of its data
+        gradient (``*_t``; the flipped, transposed taps ``wd`` for the convolutions of stages 2-4)."""
+        f = dict(device=device, dtype=torch.float32)
+        wp, prep = self.k_gemm_wprep, {}
+        for i in range(4):
+            conv = getattr(self.branch, f"conv{i + 1}")[0]
+            Co, Ci = conv.weight.shape[:2]
+            N = max(Co, 64)
+            bias = torch.zeros(N, **f)
+            bias[:Co] = conv.bias.detach()
+            if i == 0:
+                K = -(-27 * Ci // 64) * 64
+                wm = torch.zeros(N, K, **f)
+                wm[:Co, :27 * Ci] = conv.weight.detach().permute(0, 2, 3, 4, 1).reshape(Co, 27 * Ci)
+                prep["s1"] = dict(wz=wp(wm), bias=bias, N=N, K=K, C=Co, Ci=Ci)
+            else:
+                K = max(Ci, 64)
+                wz = torch.empty(3 * N * 27 * K, device=device, dtype=I16)
+                conv3x_wprep(padded_weight(conv, N, K).to(device), wz, N, K)
+                wd = torch.empty(3 * N * 27 * K, device=device, dtype=I16)
+                conv3x_wprep(flipped_weight(conv, N, K).to(device), wd, K, N)
+                prep[f"s{i + 1}"] = dict(wz=wz, wd=wd, bias=bias, N=N, K=K, C=Co, Ci=Ci)
+
+        def linear(name, lin, w=None, n_pad=None):
+            w = lin.weight.detach() if w is None else w
+            b = lin.bias.detach()
+            if n_pad is not None and n_pad > w.shape[0]:                # zero rows up to the narrowest GEMM tile
+                w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], **f)])
+                b = torch.cat([b, torch.zeros(n_pad - b.shape[0], **f)])
+            w = w.contiguous()
+            prep[name] = dict(wz=wp(w), wz_t=wp(w.t().contiguous()), bias=b.contiguous(), N=w.shape[0], K=w.shape[1])
+
+        fc0, fc3, tr, o = self.branch.fc[0], self.branch.fc[3], self.trunk.fc, self.output_net
+        linear("fc0", fc0, fc0.weight.detach().reshape(512, 256, 4, 4).permute(0, 2, 3, 1).reshape(512, 4096))
+        linear("fc3", fc3)
+        w1 = torch.zeros(64, 64, **f)
+        w1[:, :3] = tr[0].weight.detach()
+        linear("t0", tr[0], w1)
+        linear("t2", tr[2])
+        linear("t4", tr[4])
+        linear("o0", o[0])
+        linear("o3", o[3])
+        linear("o6", o[6], n_pad=64)
+        return prep
+
+    def _coords(self, T, H, W, device):
+        """[N][64] fp32: the (t, h, w) coordinates of ``get_grid`` (float64 linspace per axis, cast) in columns 0..2, zeros beyond."""
+        def build():
+            axes = [torch.tensor(np.linspace(0, 1, n), dtype=torch.float) for n in (T, H, W)]
+            c = torch.zeros(T * H * W, 64)
+            c[:, :3] = torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3)
+            return c.to(device)
+
+        return self._layouts.get("coords", (), build, extra=(T, H, W, str(device)))
+
+    @staticmethod
+    def _gemm(a, s, out, M, act=0, aux=None, drop=None, t=False):
+        """out [M][N] = epilogue(a [M][K] W^T) on rpb_gemm3x; ``t``: the transposed weight (data gradient, no bias); ``drop``: None, a
+        mask tensor (or ``ops.Sub`` at its first row) or (seed, keep)."""
+        N, K = (s["K"], s["N"]) if t else (s["N"], s["K"])
+        mask = None if drop is None or isinstance(drop, tuple) else drop
+        seed, keep = drop if isinstance(drop, tuple) else (0, 0.0)
+        _lib.call("rpb_gemm3x", _p(a), _p(s["wz_t" if t else "wz"], I16), None if t else _p(s["bias"]), None, None, _p(out), M, N, K, K, N, act,
+                  _p(aux), None, _p(mask), int(seed), float(keep), _stream(), label=f"don_gemm3x[N{N},K{K}]",
+                  nbytes=4 * (M * K + M * N) + 6 * N * K, flops=2 * M * N * K)
+        return out
+
+    def _bn_batch(self, y, ld, M, C, bn, parts=None):
+        """Batch statistics of y [M][ld] -> ab [4][C] = (a, b, mean, rstd); the running statistics are updated on the device.  ``parts``:
+        fp64 partials already accumulated (stage 1's chunks), [2 if C == 256 else 1][rows][2 Ch]."""
+        if M < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{M} cells, {C} channels]")
+        rows, Ch, nh = _lib.query("rpb_cno_bn_rows"), min(C, 128), max(1, C // 128)
+        if parts is None:
+            parts = torch.empty(nh, rows, 2 * Ch, device=y.device, dtype=torch.float64)
+            for h in range(nh):                                           # C = 256: two column halves
+                self.k_bn_stats(Sub(y, h * Ch), ld, M, Ch, parts[h])
+        ab = torch.empty(4, C, device=y.device, dtype=torch.float32)
+        for h in range(nh):
+            o = h * Ch
+            _lib.call("rpb_cno_bn_finish", _p(parts[h], torch.float64), parts.shape[1], M, Ch, _p(Sub(bn.weight.data, o)), _p(Sub(bn.bias.data, o)),
+                      _p(Sub(bn.running_mean, o)), _p(Sub(bn.running_var, o)), float(bn.eps), float(bn.momentum), _p(Sub(ab, o)),
+                      _p(Sub(ab, C + o)), _p(Sub(ab, 2 * C + o)), _p(Sub(ab, 3 * C + o)), _stream(), label="don_bn_finish",
+                      nbytes=16 * parts.shape[1] * Ch)
+        torch.autograd.graph.increment_version(bn.running_mean)           # written through raw pointers: the layout cache is keyed on these
+        torch.autograd.graph.increment_version(bn.running_var)
+        bn.num_batches_tracked += 1
+        return ab
+
+    @staticmethod
+    def k_bn_stats(y, ld, M, C, part):
+        _lib.call("rpb_cno_bn_stats", _p(y), ld, M, C, _p(part, torch.float64), _stream(), label="don_bn_stats", nbytes=4 * M * C)
+
+    # the row passes of the training step (csrc/rpb_deeponet_train.hip); row operands: fp32 tensors or ``ops.Sub`` at the first column
+    @staticmethod
+    def k_train_rows():
+        return _lib.query("rpb_don_train_rows")
+
+    @staticmethod
+    def k_pool_bwd(y, ldy, g, ldg, ab, gz, ldz, B, T, H, W, C, mode, part):
+        _lib.call("rpb_don_pool_bwd", _p(y), ldy, _p(g), ldg, _p(ab[0]), _p(ab[1]), _p(ab[2]), _p(ab[3]), _p(gz), ldz, B, T, H, W, C, mode,
+                  _p(part, torch.float64), _stream(), label="don_pool_bwd", nbytes=8 * B * T * H * W * C)
+
+    @staticmethod
+    def k_sum64(part, rows, L, sums):
+        _lib.call("rpb_don_sum64", _p(part, torch.float64), rows, L, _p(sums, torch.float64), _stream(), label="don_sum64", nbytes=8 * rows * L)
+
+    @staticmethod
+    def k_bn_bwd_apply(gz, ldz, y, ldy, ab, sums, M, C, Cpad, dy, ldd, dgamma=None, dbeta=None):
+        _lib.call("rpb_don_bn_bwd_apply", _p(gz), ldz, _p(y), ldy, _p(ab[0]), _p(ab[2]), _p(ab[3]), _p(sums, torch.float64), M, C, Cpad, _p(dy),
+                  ldd, _p(dgamma), _p(dbeta), _stream(), label="don_bn_bwd_apply", nbytes=4 * M * (2 * C + Cpad))
+
+    @staticmethod
+    def k_point_mul(t, b, x, q0, R, B, N, p):
+        _lib.call("rpb_don_point_mul", _p(t), _p(b), _p(x), q0, R, B, N, p, _stream(), label="don_point_mul", nbytes=8 * R * p)
+
+    @staticmethod
+    def k_point_mul_bwd(gx, t, b, gt, part, n0, R, N, p):
+        _lib.call("rpb_don_point_mul_bwd", _p(gx), _p(t), _p(b), _p(gt), _p(part), n0, R, N, p, _stream(), label="don_point_mul_bwd",
+                  nbytes=16 * R * p)
+
+    def _drop(self, layer, chunk, step, row0=0):
+        """The dropout argument of one GEMM launch: None (rate 0), the explicit mask's rows from ``row0`` (tests), or (seed, keep)."""
+        if self.dropout_rate <= 0:
+            return None
+        if self._mask_override is not None:
+            m = self._mask_override[layer]
+            return Sub(m, row0 * m.shape[1])
+        return (drop_seed(self.dropout_seed, step, layer, chunk), 1.0 - self.dropout_rate)
+
+    def _point_chunk(self, prep, t, b, q0, R, B, N, step, ci):
+        """x, h1, h2 of the points q0 .. q0 + R - 1 (forward, and the backward's recomputation with the same seeds / masks)."""
+        dev, p = t.device, self.p
+        x = torch.empty(R, p, device=dev, dtype=torch.float32)
+        self.k_point_mul(t, b, x, q0, R, B, N, p)
+        h1 = self._gemm(x, prep["o0"], torch.empty(R, 512, device=dev, dtype=torch.float32), R, act=3, drop=self._drop(1, ci, step, q0))
+        h2 = self._gemm(h1, prep["o3"], torch.empty(R, 128, device=dev, dtype=torch.float32), R, act=3, drop=self._drop(2, ci, step, q0))
+        return x, h1, h2
+
+    @torch.no_grad()
+    def _forward_hip(self, x, state):
+        """Training forward: batch-statistics BatchNorm (running statistics updated), active dropout, the trunk and the output net as
+        GEMM chains.  ``state`` (a dict, or None) receives what the backward pass reads: per stage the input rows, the convolution
+        output and (a, b, mean, rstd); the branch's hidden row, ``b``; the trunk's hidden rows, ``t``; the step number of the dropout
+        seeds.  Nothing of size B N 512 is kept: the backward pass recomputes the output net chunk by chunk."""
+        x = x.contiguous().float()
+        dev, f = x.device, dict(device=x.device, dtype=torch.float32)
+        B, T, H, W, Cin = x.shape
+        T_out, p, Cout = self.shape_out[0], self.p, self.output_channels
+        prep, ext, rows = self._prep_train(dev), pooled_extents(T, H, W), _lib.query("rpb_cno_bn_rows")
+        for Ti, Hi, Wi in ext:                                        # before anything is launched: no statistic moves, no step is used up
+            if B * Ti * Hi * Wi < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, C, {Ti}, {Hi}, {Wi}]")
+        step = self._drop_step
+        stages = []
+        # stage 1 in chunks of samples (the im2col buffer stays bounded); the 64-wide rows are kept (the backward pass needs them anyway),
+        # the statistics are accumulated over the chunks before anything is pooled
+        s1, cells = prep["s1"], T * H * W
+        nb = max(1, _COL_FLOATS // (cells * s1["K"]))
+        nchunk = -(-B // nb)
+        y = torch.empty(B * cells, 64, **f)
+        parts = torch.empty(1, nchunk * rows, 64, device=dev, dtype=torch.float64)
+        for k, b0 in enumerate(range(0, B, nb)):
+            nbc = min(nb, B - b0)
+            col = torch.empty(nbc * cells, s1["K"], **f)
+            _lib.call("rpb_im2col", _p(x[b0:b0 + nbc]), _p(col), nbc, T, H, W, Cin, 3, s1["K"], _stream(), label="don_im2col",
+                      nbytes=4 * nbc * cells * (Cin + s1["K"]))
+            self._gemm(col, s1, Sub(y, b0 * cells * 64), nbc * cells)
+            self.k_bn_stats(Sub(y, b0 * cells * 64), 64, nbc * cells, 32, parts[0, k * rows:(k + 1) * rows])
+        bn = self.branch.conv1[1]
+        ab = self._bn_batch(y, 64, B * cells, 32, bn, parts)
+        h = self.k_bn_relu_pool(y, ab[0], ab[1], B, T, H, W, 32, 64, 0)
+        stages.append(dict(y=y, ab=ab, src=None))
+        for i in (2, 3, 4):
+            s, (Ti, Hi, Wi) = prep[f"s{i}"], ext[i - 1]
+            M = B * Ti * Hi * Wi
+            y = self.k_conv(h, s, (Ti, Hi, Wi))
+            ab = self._bn_batch(y, s["N"], M, s["C"], getattr(self.branch, f"conv{i}")[1])
+            stages.append(dict(y=y, ab=ab, src=h))
+            h = self.k_bn_relu_pool(y, ab[0], ab[1], B, Ti, Hi, Wi, s["C"], s["C"], 0 if i < 4 else 1)
+        h4 = h.view(B, 4096)
+        z = self._gemm(h4, prep["fc0"], torch.empty(B, 512, **f), B, act=3, drop=self._drop(0, 0, step))
+        b = self._gemm(z, prep["fc3"], torch.empty(B, p, **f), B)
+        # trunk: three GEMMs over the coordinate matrix, the two hidden activations kept
+        N = T_out * H * W
+        coords = self._coords(T_out, H, W, dev)
+        u1 = self._gemm(coords, prep["t0"], torch.empty(N, 64, **f), N, act=3)
+        u2 = self._gemm(u1, prep["t2"], torch.empty(N, 128, **f), N, act=3)
+        t = self._gemm(u2, prep["t4"], torch.empty(N, p, **f), N)
+        # output net in chunks of points
+        Q, RC = B * N, self._point_rows
+        out = torch.empty(Q, Cout, **f)
+        o = torch.empty(min(RC, Q), 64, **f)
+        for ci, q0 in enumerate(range(0, Q, RC)):
+            R = min(RC, Q - q0)
+            _, _, h2 = self._point_chunk(prep, t, b, q0, R, B, N, step, ci)
+            self._gemm(h2, prep["o6"], o, R)
+            out[q0:q0 + R] = o[:R, :Cout]
+        self._drop_step = step + 1                                    # a forward that ran to its end used this step's seeds
+        if state is not None:
+            state.update(x=x, stages=stages, h4=h4, z=z, b=b, coords=coords, u1=u1, u2=u2, t=t, step=step, shape=(B, T, H, W, T_out))
+        return out.view(B, T_out, H, W, Cout)
+
+    @torch.no_grad()
+    def _backward_hip(self, state, g_out, need_gx=False):
+        """{parameter: gradient} from dLoss/d(out).  The output net walks the forward's chunks again (x, h1, h2 recomputed with the same
+        seeds), then the trunk from ``gt``, the branch's Linear layers from ``gb`` and the four stages in reverse: pooling + ReLU +
+        BatchNorm backward row passes give ``dy``, ``wgrad`` gives (dW, db), rpb_conv3x on the flipped taps gives the gradient of the
+        stage's input.  No atomics; ``state`` is only read: a second call gives bit-equal gradients."""
+        if need_gx:
+            raise NotImplementedError("DeepONet training computes no input gradient (no trainer asks for one)")
+        dev, f = g_out.device, dict(device=g_out.device, dtype=torch.float32)
+        B, T, H, W, T_out = state["shape"]
+        p, Cout, N = self.p, self.output_channels, T_out * H * W
+        prep, rows = self._prep_train(dev), self.k_train_rows()
+        t, b, step = state["t"], state["b"], state["step"]
+        grads, acc = {}, {}
+
+        def accumulate(key, dW, db):                                    # chunk after chunk, in order
+            acc[key] = (dW, db) if key not in acc else (ops_add(acc[key][0], dW), ops_add(acc[key][1], db))
+
+        # ---- output net
+        Q, RC = B * N, self._point_rows
+        gq = g_out.reshape(Q, Cout)
+        gt, gb = torch.zeros(N, p, **f), torch.zeros(B, p, **f)
+        part = torch.empty(rows, p, **f)
+        for ci, q0 in enumerate(range(0, Q, RC)):
+            R = min(RC, Q - q0)
+            x, h1, h2 = self._point_chunk(prep, t, b, q0, R, B, N, step, ci)
+            go = torch.zeros(R, 64, **f)
+            go[:, :Cout] = gq[q0:q0 + R]
+            accumulate("o6", *wgrad(go, h2, R, 64, 128))
+            gh2 = self._gemm(go, prep["o6"], torch.empty(R, 128, **f), R, act=4, aux=h2, drop=self._drop(2, ci, step, q0), t=True)
+            accumulate("o3", *wgrad(gh2, h1, R, 128, 512))
+            gh1 = self._gemm(gh2, prep["o3"], torch.empty(R, 512, **f), R, act=4, aux=h1, drop=self._drop(1, ci, step, q0), t=True)
+            accumulate("o0", *wgrad(gh1, x, R, 512, p))
+            gx = self._gemm(gh1, prep["o0"], torch.empty(R, p, **f), R, t=True)
+            q = q0
+            while q < q0 + R:                                            # one launch per sample the chunk touches: gt[n] += has one writer
+                s, n0 = divmod(q, N)
+                Rs = min(N - n0, q0 + R - q)
+                self.k_point_mul_bwd(Sub(gx, (q - q0) * p), t, Sub(b, s * p), gt, part, n0, Rs, N, p)
+                reduce_partials(part, rows, p, out_f32=Sub(gb, s * p), accumulate=True)
+                q += Rs
+        o = self.output_net
+        grads[o[6].weight], grads[o[6].bias] = acc["o6"][0][:Cout].contiguous(), acc["o6"][1][:Cout].contiguous()
+        grads[o[3].weight], grads[o[3].bias] = acc["o3"]
+        grads[o[0].weight], grads[o[0].bias] = acc["o0"]
+        # ---- trunk
+        tr, u1, u2 = self.trunk.fc, state["u1"], state["u2"]
+        grads[tr[4].weight], grads[tr[4].bias] = wgrad(gt, u2, N, p, 128)
+        gu2 = self._gemm(gt, prep["t4"], torch.empty(N, 128, **f), N, act=4, aux=u2, t=True)
+        grads[tr[2].weight], grads[tr[2].bias] = wgrad(gu2, u1, N, 128, 64)
+        gu1 = self._gemm(gu2, prep["t2"], torch.empty(N, 64, **f), N, act=4, aux=u1, t=True)
+        dW, grads[tr[0].bias] = wgrad(gu1, state["coords"], N, 64, 64)
+        grads[tr[0].weight] = dW[:, :3].contiguous()
+        # ---- branch: the two Linear layers
+        fc, z, h4 = self.branch.fc, state["z"], state["h4"]
+        grads[fc[3].weight], grads[fc[3].bias] = wgrad(gb, z, B, p, 512)
+        gz0 = self._gemm(gb, prep["fc3"], torch.empty(B, 512, **f), B, act=4, aux=z, drop=self._drop(0, 0, step), t=True)
+        dW, grads[fc[0].bias] = wgrad(gz0, h4, B, 512, 4096)
+        grads[fc[0].weight] = dW.view(512, 4, 4, 256).permute(0, 3, 1, 2).reshape(512, 4096)       # (h, w, c) columns -> the reference's (c, h, w)
+        g, ldg = self._gemm(gz0, prep["fc0"], torch.empty(B, 4096, **f), B, t=True), 256          # [B][4][4][256]
+        # ---- branch: the four stages, last first
+        ext = pooled_extents(T, H, W)
+        for i in (4, 3, 2, 1):
+            s, (Ti, Hi, Wi), st = prep[f"s{i}"], ext[i - 1], state["stages"][i - 1]
+            conv, bn = getattr(self.branch, f"conv{i}")[:2]
+            C, Nw, M = s["C"], s["N"], B * Ti * Hi * Wi
+            y, ab = st["y"], st["ab"]
+            dy = torch.empty(M, Nw, **f)
+            part64 = torch.empty(rows, 2 * C, device=dev, dtype=torch.float64)
+            sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
+            dgb = torch.empty(2, C, **f)
+            self.k_pool_bwd(y, Nw, g, ldg, ab, dy, Nw, B, Ti, Hi, Wi, C, 1 if i == 4 else 0, part64)
+            self.k_sum64(part64, rows, 2 * C, sums)
+            self.k_bn_bwd_apply(dy, Nw, y, Nw, ab, sums, M, C, Nw, dy, Nw, dgamma=dgb[0], dbeta=dgb[1])
+            grads[bn.weight], grads[bn.bias] = dgb[0], dgb[1]
+            if i == 1:                                                  # the im2col GEMM form, chunked like the forward
+                cells = Ti * Hi * Wi
+                nb = max(1, _COL_FLOATS // (cells * s["K"]))
+                tot = None
+                for b0 in range(0, B, nb):
+                    nbc = min(nb, B - b0)
+                    col = torch.empty(nbc * cells, s["K"], **f)
+                    _lib.call("rpb_im2col", _p(state["x"][b0:b0 + nbc]), _p(col), nbc, Ti, Hi, Wi, s["Ci"], 3, s["K"], _stream(),
+                              label="don_im2col", nbytes=4 * nbc * cells * (s["Ci"] + s["K"]))
+                    dWc = wgrad(Sub(dy, b0 * cells * 64), col, nbc * cells, 64, s["K"])
+                    tot = dWc if tot is None else (ops_add(tot[0], dWc[0]), ops_add(tot[1], dWc[1]))
+                Ci = s["Ci"]
+                grads[conv.weight] = tot[0][:C, :27 * Ci].reshape(C, 3, 3, 3, Ci).permute(0, 4, 1, 2, 3).contiguous()
+                grads[conv.bias] = tot[1][:C].contiguous()
+                break
+            K = s["K"]
+            dW, db = wgrad(dy, st["src"], M, Nw, 27 * K, ldg=Nw, lda=K, conv=(Ti, Hi, Wi))
+            grads[conv.weight], grads[conv.bias] = weight_grad_view(dW, C, s["Ci"], Nw, K), db[:C].contiguous()
+            planes = torch.empty(3 * M * Nw, device=dev, dtype=I16)
+            split3(dy, planes, M, Nw)
+            g, ldg = torch.empty(M, K, **f), K
+            conv3x(planes, s["wd"], g, M, K, Nw, (Ti, Hi, Wi))
+        return grads

@@ -60,6 +60,8 @@ def load_model(train_dataset, device="cpu", **kwargs):
         from .deeponet import DeepONet
         model = DeepONet(shape_in=input_shape, shape_out=output_shape, input_channels=input_shape[-1],       # load_model.py:132-143
                          output_channels=output_shape[-1], p=kwargs["p"], dropout_rate=kwargs["dropout_rate"], device=device).to(device)
+        if kwargs.get("hip_training"):                        # opt-in: the HIP training step with batch-statistics BatchNorm and dropout
+            model.enable_training()
     elif model_name == "cno":
         from .cno import CNO3d
         if output_shape[0] > input_shape[0] and output_shape[0] % input_shape[0] == 0:                       # load_model.py:60-75
