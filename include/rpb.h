@@ -856,6 +856,19 @@ int rpb_don_point_mul(const float* t, const float* b, float* x, long q0, long R,
 int rpb_don_point_mul_bwd(const float* gx, const float* t, const float* b, float* gt, float* part, long n0, long R, long N, int p,
                           void* stream);
 
+/*
+ * DeepONet on the opt-in "f16x2" eval arithmetic (DeepONet.set_arith("f16x2"); csrc/rpb_deeponet_h.hip; additions do not change
+ * RPB_ABI_VERSION).
+ *     rpb_don_point_mlp_f16x2: the contract of rpb_don_point_mlp on the fp16 MFMA from two-plane operands (three products, dropped term
+ *     <= 2^-22 |a b|).  w1z / w2z / w3z: fp16 (hi, lo) planes of W 2^ew in the lane order of rpb_don_point_mlp's operands with two planes
+ *     where that has three (model/deeponet.py point_weights_f16x2), max|W| 2^ew in [2^14, 2^15) per weight; sc [5] in device memory:
+ *     2^-ew1, 2^-ew2, 2^-ew3, max_u ||W1_u||_1 and max|b1| (both rounded up).  Every point's activations are scaled by a power of two of
+ *     their own, formed in registers: from the exact column maximum for b (.) t and for the 128-wide hidden layer, from the bound
+ *     max_u ||W1_u||_1 max|x| + max|b1| for the 512-wide one; the epilogues undo it.  No atomics, two calls are bit-equal.  Non-finite
+ *     inputs are outside the contract. */
+int rpb_don_point_mlp_f16x2(const float* t, const float* b, const void* w1z, const float* b1z, const void* w2z, const float* b2z,
+                            const void* w3z, const float* b3, const float* sc, float* out, int B, long N, int p, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,7 @@ SIGNATURES = {
     "rpb_don_bn_relu_pool": (_I, "pppp" + "iiiiiiii" + "p"),
     "rpb_don_trunk": (_I, "pppppppppp" + "iiii" + "p"),
     "rpb_don_point_mlp": (_I, "ppppppppp" + "ilii" + "p"),
+    "rpb_don_point_mlp_f16x2": (_I, "pppppppppp" + "ilii" + "p"),
     "rpb_cno_conv3x": (_I, "ppppppp" + "l" + "iiiiiii" + "iii" + "p"),
     "rpb_cno_pack": (_I, "pp" + "li" + "p"),
     "rpb_cno_conv3x_f16x2": (_I, "ppppppp" + "l" + "iiiiii" + "iii" + "pp" + "p"),

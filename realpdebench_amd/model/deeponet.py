@@ -20,6 +20,10 @@ Pipeline (activations channels-last fp32 rows ``[B * T * H * W][C]``; DESIGN.md 
           trunk weight changes
   output  rpb_don_point_mlp: out[b][n] = output_net(b[b] * t[n]) in one launch
 
+``set_arith("f16x2")`` (opt-in, evaluation forward only) moves the output net to rpb_don_point_mlp_f16x2
+(csrc/rpb_deeponet_h.hip: two fp16 planes per operand, one power-of-two scale per point formed in registers) and stages 2-4 to
+rpb_amax_exp + rpb_split2h + rpb_conv3x_f16x2; stage 1, the branch Linear layers and the trunk stay on the kernels above.
+
 Parameters carry the reference's names, shapes and dtypes (``nn`` modules of the same tree, ``nn.Sequential`` indices included), so
 ``state_dict`` / ``load_state_dict`` are the reference's; kernel layouts are derived tensors rebuilt when a parameter changed.
 """
@@ -28,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import Sub, _p, _stream, conv3x, conv3x_wprep, reduce_partials, split3
+from ..ops import Sub, _p, _stream, amax_exp, conv3_f16x2_weights, conv3x, conv3x_f16x2, conv3x_wprep, reduce_partials, split2h, split3
 from ..ops import add as ops_add
 from ._common import EvalOnly, HipFunction, padded_weight, wgrad
 from .cno import flipped_weight, weight_grad_view
@@ -36,6 +40,7 @@ from .model import Model
 
 I16 = torch.int16
 P_SUPPORTED = (64, 128, 256)
+ARITHS = ("f32", "f16x2")      # DeepONet.set_arith
 _COL_FLOATS = 1 << 28          # stage-1 im2col buffer bound (1 GiB): larger batches run the first stage in chunks of samples
 _POINT_ROWS = 1 << 16          # training step: (sample, point) rows per chunk of the output net (its 512-wide rows: 128 MiB per buffer)
 
@@ -76,6 +81,48 @@ def point_weights(W1, b1, W2, b2, W3, b3):
     w3 = W3p.reshape(32, 4, 2, 2, 2, 4).permute(1, 2, 4, 0, 3, 5).reshape(4, 2, 64, 8)                  # (mt, s, kg * 32 + m, eh * 4 + i)
     regs = lambda b, tiles: b.reshape(tiles, 4, 2, 4).permute(0, 2, 1, 3).reshape(tiles, 2, 16).contiguous().float()
     return (_lane_planes(w1, 2), regs(b1, 16), _lane_planes(w2, 3), regs(b2, 4), _lane_planes(w3, 2), b3.contiguous().float())
+
+
+def pow2_scale(m):
+    """(2^e, 2^-e) as fp32 tensors of m's shape, e the exponent with m 2^e in [2^14, 2^15) (the rule of ``rpb_amax_exp``), capped at 62;
+    e = 0 for m == 0.  ``m``: finite fp32, >= 0.  Integer arithmetic on the bit patterns, on m's device: no host synchronisation."""
+    e = 141 - (m.float().contiguous().view(torch.int32) >> 23)
+    e = torch.where(m == 0, torch.zeros_like(e), e.clamp(max=62))
+    return ((e + 127) << 23).view(torch.float32), ((127 - e) << 23).view(torch.float32)
+
+
+def f16_planes(x):
+    """fp32 (already scaled into fp16's range) -> (hi, lo) fp16 bit patterns (int16), both rounded to nearest even: hi + lo == x to
+    2^-22 |x| (``split8h`` of csrc/rpb_mma.h)."""
+    x = x.contiguous().float()
+    h = x.half()
+    l = (x - h.float()).half()
+    return h.view(torch.int16), l.view(torch.int16)
+
+
+def point_weights_f16x2(W1, b1, W2, b2, W3, b3):
+    """The operands of ``rpb_don_point_mlp_f16x2``: ``point_weights`` with every weight scaled by its own 2^ew (max|W| 2^ew in
+    [2^14, 2^15)) and split into two fp16 planes in the same lane order.  Returns (w1h [16][p/16][2][64][8], b1z, w2h [16][2][4][2][64][8],
+    b2z, w3h [4][2][2][64][8], b3, sc); sc [5] fp32 on the weights' device: 2^-ew1, 2^-ew2, 2^-ew3 and the two constants of the kernel's
+    bound |h1_u| <= max_u ||W1_u||_1 max_k |x_k| + max|b1|, both rounded up.  Plain torch, no host synchronisation."""
+    p, Cout = W1.shape[1], W3.shape[0]
+    assert W1.shape == (512, p) and W2.shape == (128, 512) and W3.shape == (Cout, 128) and Cout <= 16 and p % 16 == 0
+    KS = p // 16
+    s1, i1 = pow2_scale(W1.abs().max())
+    s2, i2 = pow2_scale(W2.abs().max())
+    s3, i3 = pow2_scale(W3.abs().max())
+    w1 = (W1.float() * s1).reshape(16, 32, KS, 2, 8).permute(0, 2, 3, 1, 4).reshape(16, KS, 64, 8)
+    w2 = (W2.float() * s2).reshape(4, 32, 16, 2, 2, 2, 4).permute(2, 3, 0, 5, 1, 4, 6).reshape(16, 2, 4, 64, 8)
+    W3p = torch.zeros(32, 128, dtype=torch.float32, device=W3.device)
+    W3p[:Cout] = W3.float() * s3
+    w3 = W3p.reshape(32, 4, 2, 2, 2, 4).permute(1, 2, 4, 0, 3, 5).reshape(4, 2, 64, 8)
+    regs = lambda b, tiles: b.reshape(tiles, 4, 2, 4).permute(0, 2, 1, 3).reshape(tiles, 2, 16).contiguous().float()
+    planes = lambda w, dim: torch.stack(f16_planes(w), dim=dim).contiguous()
+    l1 = W1.double().abs().sum(1).max()
+    l1f = l1.float()
+    l1f = torch.where(l1f.double() < l1, torch.nextafter(l1f, torch.full_like(l1f, float("inf"))), l1f)       # rounded up
+    sc = torch.stack([i1, i2, i3, l1f, b1.float().abs().max()]).contiguous()
+    return (planes(w1, 2), regs(b1, 16), planes(w2, 3), regs(b2, 4), planes(w3, 2), b3.contiguous().float(), sc)
 
 
 def adaptive_bins(n_in, n_out):
@@ -126,6 +173,7 @@ class DeepONet(EvalOnly, Model):
     hip_training = False                            # enable_training() sets it on the instance
     dp_unavailable = None                           # (enabled instances: why trainer.make_trainer refuses more than one rank)
     _point_rows = _POINT_ROWS                       # (tests force several chunks by lowering it on an instance)
+    f16x2_convs = True                              # set_arith("f16x2") also moves branch stages 2-4 (tools/deeponet_probe.py measures both)
 
     def __init__(self, shape_in, shape_out, input_channels, output_channels, p, dropout_rate=0.1, device="cuda"):
         super().__init__()
@@ -150,6 +198,18 @@ class DeepONet(EvalOnly, Model):
                                         nn.Dropout(dropout_rate), nn.Linear(128, self.output_channels))
         self.dropout_rate = float(dropout_rate)
         self.dropout_seed, self._drop_step, self._mask_override = 0, 0, None      # the opt-in training step, see enable_training / drop_seed
+        self.arith = "f32"              # arithmetic of the eval / rollout forward's output net and branch stages 2-4, see set_arith
+
+    def set_arith(self, arith):
+        """Arithmetic of the evaluation / rollout forward's output net and of the convolutions of branch stages 2-4: ``"f32"`` (default,
+        the parity path: operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16
+        planes of the tensor scaled by a power of two -- one per point inside the output net --, three products, dropped term <= 2^-22;
+        csrc/rpb_deeponet_h.hip).  Only the evaluation forward changes: the opt-in training step
+        (``enable_training()``) stays on its kernels under either setting."""
+        if arith not in ARITHS:
+            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
+        self.arith = arith
+        return self
 
     # ------------------------------------------------------------------ the opt-in training step
     def enable_training(self, seed=None):
@@ -222,6 +282,23 @@ class DeepONet(EvalOnly, Model):
         prep["point"] = point_weights(*(t.detach() for t in (o[0].weight, o[0].bias, o[3].weight, o[3].bias, o[6].weight, o[6].bias)))
         return prep
 
+    def _prep_f16x2(self, device):
+        """What ``set_arith("f16x2")`` adds to ``_prep``: the output net's weights as scaled fp16 planes with their device-side
+        constants (``point_weights_f16x2``) and, per convolution of stages 2-4, ``ops.conv3_f16x2_weights`` planes + exponent."""
+        tensors = [getattr(self.branch, f"conv{i}")[0].weight for i in (2, 3, 4)] + list(self.output_net.parameters())
+        return self._layouts.get("prep_f16x2", tensors, lambda: self._build_prep_f16x2(device))
+
+    def _build_prep_f16x2(self, device):
+        prep = {}
+        for i in (2, 3, 4):
+            conv = getattr(self.branch, f"conv{i}")[0]
+            Co, Ci = conv.weight.shape[:2]
+            N, K = max(Co, 64), max(Ci, 64)
+            prep[f"s{i}"] = conv3_f16x2_weights(padded_weight(conv, N, K).to(device), N, K)
+        o = self.output_net
+        prep["point"] = point_weights_f16x2(*(t.detach() for t in (o[0].weight, o[0].bias, o[3].weight, o[3].bias, o[6].weight, o[6].bias)))
+        return prep
+
     def _trunk(self, T, H, W, device):
         """t [N][p] of the (T, H, W) grid.  ONE grid is kept (84 MB at the cylinder shape): it is recomputed when the grid, the device or a
         trunk weight changed."""
@@ -271,6 +348,20 @@ class DeepONet(EvalOnly, Model):
         return out
 
     @staticmethod
+    def k_conv_f16x2(x, s, wh, mesh):
+        """``k_conv`` on two fp16 planes of x 2^ea (rpb_amax_exp + rpb_split2h + rpb_conv3x_f16x2); ``wh`` = (planes, exponent) of the
+        weights (``ops.conv3_f16x2_weights``)."""
+        M, Ci = x.shape
+        N = s["N"]
+        ea = torch.empty(1, device=x.device, dtype=torch.int32)
+        planes = torch.empty(2 * M * Ci, device=x.device, dtype=torch.int16)
+        amax_exp(x, ea, M, Ci)
+        split2h(x, planes, M, Ci, ea)
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+        conv3x_f16x2(planes, wh[0], out, M, N, Ci, mesh, ea, wh[1], bias=s["bias"])
+        return out
+
+    @staticmethod
     def k_bn_relu_pool(x, sc, sh, B, T, H, W, C, ldo, mode):
         """x [B * T * H * W][ldx] -> MaxPool3d(2) (mode 0) or AdaptiveAvgPool3d((1, 4, 4)) (mode 1) of relu(x * sc + sh), [cells][ldo]."""
         ldx = x.shape[-1]
@@ -300,9 +391,25 @@ class DeepONet(EvalOnly, Model):
                   flops=2 * B * N * (p * 512 + 512 * 128 + 128 * Cout))
         return out
 
+    @staticmethod
+    def k_point_mlp_f16x2(t, b, pw, out=None):
+        """``k_point_mlp`` on two fp16 planes; ``pw`` = ``point_weights_f16x2(...)``; ``out``: B N C_out floats to write (a tensor or an
+        ``ops.Sub`` of one), default a new tensor."""
+        w1h, b1z, w2h, b2z, w3h, b3, sc = pw
+        N, p = t.shape
+        B, Cout = b.shape[0], b3.shape[0]
+        if out is None:
+            out = torch.empty(B, N, Cout, device=t.device, dtype=torch.float32)
+        _lib.call("rpb_don_point_mlp_f16x2", _p(t), _p(b), _p(w1h, I16), _p(b1z), _p(w2h, I16), _p(b2z), _p(w3h, I16), _p(b3), _p(sc), _p(out),
+                  B, N, p, Cout, _stream(), label="don_point_mlp_f16x2",
+                  nbytes=4 * (B * N * Cout + N * p + B * p) + 4 * (512 * p + 128 * 512 + 32 * 128),
+                  flops=2 * B * N * (p * 512 + 512 * 128 + 128 * Cout))
+        return out
+
     # ------------------------------------------------------------------ forward
-    def branch_forward(self, x, prep, keep=None):
-        """b [B][p]; ``keep`` (a list) receives the four pooled stage outputs, channels-last [B][T'][H'][W'][C] (tests)."""
+    def branch_forward(self, x, prep, keep=None, prep_h=None):
+        """b [B][p]; ``keep`` (a list) receives the four pooled stage outputs, channels-last [B][T'][H'][W'][C] (tests); ``prep_h``
+        (``_prep_f16x2``): stages 2-4 on the f16x2 convolution."""
         B = x.shape[0]
         ext = pooled_extents(*x.shape[1:4])
         s1 = prep["s1"]
@@ -317,7 +424,7 @@ class DeepONet(EvalOnly, Model):
             keep.append(h.view(B, T1, H1, W1, 64)[..., :32])
         for i in (2, 3, 4):
             s, (T, H, W) = prep[f"s{i}"], ext[i - 1]
-            c = self.k_conv(h, s, (T, H, W))
+            c = self.k_conv(h, s, (T, H, W)) if prep_h is None else self.k_conv_f16x2(h, s, prep_h[f"s{i}"], (T, H, W))
             h = self.k_bn_relu_pool(c, s["sc"], s["sh"], B, T, H, W, s["C"], s["C"], 0 if i < 4 else 1)
             if keep is not None:
                 keep.append(h.view(B, *((T // 2, H // 2, W // 2) if i < 4 else (1, 4, 4)), s["C"]))
@@ -347,8 +454,11 @@ class DeepONet(EvalOnly, Model):
             B, _, H, W, _ = x.shape                                   # T_out from shape_out, H and W from the input (deeponet.py:122-126)
             T_out = self.shape_out[0]
             prep = self._prep(x.device)
-            b = self.branch_forward(x, prep)
+            prep_h = self._prep_f16x2(x.device) if self.arith == "f16x2" else None
+            b = self.branch_forward(x, prep, prep_h=prep_h if self.f16x2_convs else None)
             t = self._trunk(T_out, H, W, x.device)
+            if prep_h is not None:
+                return self.k_point_mlp_f16x2(t, b, prep_h["point"]).view(B, T_out, H, W, self.output_channels)
             return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
 
     def train_loss(self, input, target):

@@ -1,0 +1,139 @@
+"""DeepONet's opt-in f16x2 eval arithmetic, host side (no GPU): the ``set_arith`` surface, the operand layout and plane order of
+``point_weights_f16x2`` pushed through a numpy emulation of rpb_don_point_mlp_f16x2 (tests/deeponet_arith_helpers.py), and the
+per-point exponent rule.
+
+Bound of the emulation against the fp64 restatement: Rel-L2 < 2e-6, the project's f16x2 kernel bound; the
+emulation measures 0.4-2.9e-7 on the inputs below.  Hi planes alone give ~5e-4, a wrong plane order or epilogue factor gives O(1)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import deeponet_common as DC                      # noqa: E402
+import deeponet_restatement as R                  # noqa: E402
+import deeponet_arith_helpers as AH               # noqa: E402
+from deeponet_helpers import rel                  # noqa: E402
+from realpdebench_amd.model import deeponet as M  # noqa: E402
+
+
+def _new(case="a"):
+    shape_in, shape_out, p, _ = DC.CASES[case]
+    return M.DeepONet(shape_in, shape_out, shape_in[-1], shape_out[-1], p)
+
+
+def test_set_arith_surface():
+    m = _new()
+    assert m.arith == "f32" and M.ARITHS == ("f32", "f16x2")
+    assert m.set_arith("f16x2") is m and m.arith == "f16x2"
+    for bad in ("fp8", "bf16x3", "", None):
+        with pytest.raises(ValueError, match="arith must be"):
+            m.set_arith(bad)
+    assert m.arith == "f16x2"
+    assert m.set_arith("f32") is m and m.arith == "f32"
+
+
+def test_training_surface_is_unchanged_under_f16x2():
+    msg = "DeepONet training step is not built yet"
+    m = _new().set_arith("f16x2")
+    x = torch.zeros(1, *DC.CASES["a"][0])
+    with pytest.raises(NotImplementedError, match=msg):
+        m.train_loss(x, x)
+    with pytest.raises(NotImplementedError, match=msg):
+        m(x.clone().requires_grad_())
+    from realpdebench_amd.trainer import make_trainer
+    with pytest.raises(NotImplementedError, match=msg):
+        make_trainer(m, lr=1e-3, num_update=10)
+    with torch.no_grad(), pytest.raises(RuntimeError, match="no CPU fallback"):
+        m(x)
+    a, b = _new().enable_training(seed=5), _new().set_arith("f16x2").enable_training(seed=5)
+    for k in ("hip_training", "training_unavailable", "batch_independent", "dp_unavailable", "dropout_seed", "_drop_step"):
+        assert getattr(a, k) == getattr(b, k), k
+    assert b.arith == "f16x2" and b.hip_training and b.training_unavailable is None
+
+
+def _weights(p, cout):
+    g = torch.Generator().manual_seed(p + cout)
+    v = lambda *s: torch.rand(*s, generator=g) * 2 - 1
+    return (v(512, p) * 0.2, v(512) * 0.2, v(128, 512) * 0.1, v(128) * 0.2, v(cout, 128) * 0.2, v(cout)), v
+
+
+@pytest.mark.parametrize("p,cout", [(64, 3), (128, 16)])
+def test_point_kernel_f16x2_operand_layout(p, cout):
+    ws, v = _weights(p, cout)
+    pw = M.point_weights_f16x2(*ws)
+    assert [tuple(t.shape) for t in pw] == [(16, p // 16, 2, 64, 8), (16, 2, 16), (16, 2, 4, 2, 64, 8), (4, 2, 16), (4, 2, 2, 64, 8),
+                                            (cout,), (5,)]
+    assert all(pw[i].dtype == torch.int16 for i in (0, 2, 4)) and pw[6].dtype == torch.float32
+    t, b = v(32, p), v(1, p)
+    t[5] = 0                                                      # a zero column among the others
+    t[6] *= 2.0 ** -20
+    t[7] *= 2.0 ** 12
+    want = R.point_mlp(AH.sd_of(ws), t.double(), b.double())[0]
+    stats = {}
+    e = rel(AH.emulate_point_kernel_f16x2(t, b, pw, stats), want)
+    print(f"p={p} C_out={cout}: emulation Rel-L2 {e:.2e}, largest plane value {stats['peak']:.0f}, ex {stats['ex'].min()}..{stats['ex'].max()}, "
+          f"e1 {stats['e1'].min()}..{stats['e1'].max()}, e2 {stats['e2'].min()}..{stats['e2'].max()}")
+    assert e < 2e-6
+    assert stats["ex"][5] == 0 and np.isfinite(stats["peak"]) and stats["peak"] <= AH.F16_MAX
+
+
+def test_weight_planes_sum_to_the_scaled_weight():
+    ws, _ = _weights(64, 3)
+    W1, _, W2, _, W3, _ = ws
+    pw = M.point_weights_f16x2(*ws)
+    ref = M.point_weights(*ws)
+    for W, zh, z3, idx in ((W1, pw[0], ref[0], 0), (W2, pw[2], ref[2], 1), (W3, pw[4], ref[4], 2)):
+        inv = float(pw[6][idx])
+        ew = -int(np.log2(inv))
+        assert 2.0 ** -ew == inv and 2.0 ** 14 <= float(W.abs().max()) * 2.0 ** ew < 2.0 ** 15
+        hi, lo = AH.decode(zh)
+        exact = sum((pl.to(torch.int32) << 16).view(torch.float32).double() for pl in z3.unbind(-3)).numpy() * 2.0 ** ew   # same lane order
+        err = np.abs(hi + lo - exact)
+        assert np.all(err <= 2.0 ** -22 * np.abs(exact) + 2.0 ** -25), idx      # 2^-25: half a quantum of an fp16 subnormal lo
+        assert np.abs(hi).max() <= 2.0 ** 15
+    l1 = float(W1.double().abs().sum(1).max())
+    assert float(pw[6][3]) >= l1 and float(pw[6][3]) <= l1 * (1 + 2.0 ** -22)
+    assert float(pw[6][4]) == float(ws[1].abs().max())
+
+
+@pytest.mark.parametrize("scale", [1.0, 2.0 ** 12, 2.0 ** -20])
+def test_exponent_rule_keeps_every_plane_in_range(scale):
+    """Random columns and the adversarial one (x = c sign(W1[u]) for the row u of largest 1-norm: h1_u reaches the bound up to
+    max|b1| - b1_u): every plane value finite and <= 65504, the scaled maxima where the rule puts them."""
+    p, cout = 64, 3
+    ws, v = _weights(p, cout)
+    pw = M.point_weights_f16x2(*ws)
+    t, b = AH.adversarial(ws[0], v(32, p) * scale, v(1, p), row=3, c=3.0 * scale)
+    stats = {}
+    out = AH.emulate_point_kernel_f16x2(t, b, pw, stats)
+    want = R.point_mlp(AH.sd_of(ws), t.double(), b.double())[0]
+    m = (t * b).abs().max(1).values.numpy()
+    bound = float(pw[6][3]) * m + float(pw[6][4])
+    h1 = torch.relu((t * b).double() @ ws[0].double().t() + ws[1].double()).max(1).values.numpy()
+    print(f"scale {scale:g}: bound / true max of h1 {np.min(bound / h1):.2f}..{np.max(bound / h1):.1f} (adversarial column {bound[3] / h1[3]:.3f}); "
+          f"largest plane value {stats['peak']:.0f}; Rel-L2 {rel(out, want):.2e}")
+    assert np.isfinite(stats["peak"]) and stats["peak"] <= AH.F16_MAX
+    assert np.all(h1 <= bound) and bound[3] / h1[3] < 1.1
+    assert np.all((m * 2.0 ** stats["ex"] >= 2.0 ** 14) & (m * 2.0 ** stats["ex"] < 2.0 ** 15))
+    assert np.all((bound * 2.0 ** stats["e1"] >= 2.0 ** 13 * (1 - 1e-6)) & (bound * 2.0 ** stats["e1"] < 2.0 ** 14 * (1 + 1e-6)))
+    assert rel(out, want) < 2e-6
+
+
+def test_all_zero_column_takes_exponent_zero():
+    p, cout = 64, 3
+    ws, _ = _weights(p, cout)
+    pw = M.point_weights_f16x2(*ws)
+    stats = {}
+    out = AH.emulate_point_kernel_f16x2(torch.zeros(32, p), torch.ones(1, p), pw, stats)
+    want = R.point_mlp(AH.sd_of(ws), torch.zeros(1, p, dtype=torch.float64), torch.ones(1, p, dtype=torch.float64))[0, 0]
+    assert not stats["ex"].any()
+    assert np.abs(out - want.numpy()).max() < 2e-6 * float(want.abs().max())
+    assert np.array_equal(AH.col_exp(np.array([0.0, 1.0, 2.0 ** -126, 2.0 ** -140, 3.0e38], np.float32), 14), [0, 14, 62, 62, -113])
+    s, i = M.pow2_scale(torch.tensor([0.0, 1.0, 0.75, 2.0 ** -140, 3.0e38]))
+    assert s.tolist() == [1.0, 2.0 ** 14, 2.0 ** 15, 2.0 ** 62, 2.0 ** -113] and (s * i).tolist() == [1.0] * 5
