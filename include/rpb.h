@@ -869,6 +869,25 @@ int rpb_don_point_mul_bwd(const float* gx, const float* t, const float* b, float
 int rpb_don_point_mlp_f16x2(const float* t, const float* b, const void* w1z, const float* b1z, const void* w2z, const float* b2z,
                             const void* w3z, const float* b3, const float* sc, float* out, int B, long N, int p, int Cout, void* stream);
 
+/*
+ * Token GEMM on the opt-in "f16x2" eval arithmetic (GalerkinTransformer3d.set_arith("f16x2"); csrc/rpb_gemm3h.hip; additions do not
+ * change RPB_ABI_VERSION).
+ *     rpb_gemm3h: rpb_gemm3x's product out[M][ldo] = epilogue(A[M][lda] W^T) on the fp16 MFMA from two-plane operands (three products per
+ *     fp32 product, dropped term <= 2^-22 |a b|), restricted to what an evaluation forward uses: epilogue = bias[N], act in {0 none,
+ *     3 ReLU}, residual[M][ldo]; no mask tensor, no dropout, no pre_out / aux.  K % 64 == 0 with 64 <= K <= 512; N = 64, 128 or a multiple
+ *     of 256; any M >= 1; lda >= K, ldo >= N, both % 4 == 0 (A and out may be column ranges of wider tensors) -- rpb_gemm3h_supported says
+ *     so without launching, and rpb_gemm3h returns RPB_ERR_ARG for anything else.
+ *     rpb_gemm3h_wprep: W[N][K] fp32 -> Wz, 2 N K fp16 (hi, lo planes of W 2^ew in MFMA B-operand order), max|W| 2^ew in [2^14, 2^15) by
+ *     rpb_amax_exp's rule (capped at 62); sc: TWO floats of device memory, sc[0] receives 2^-ew, sc[1] is scratch.  No host
+ *     synchronisation.
+ *     Every row of A is scaled by a power of two of its own inside the launch, from the exact maximum of its K values (into
+ *     [2^14, 2^15), exponent capped at 62, an all-zero row unscaled); the epilogue undoes it per row.  Fixed summation order, no atomics:
+ *     two calls are bit-equal.  Nothing is written outside out[m][0..N), m < M.  Non-finite inputs are outside the contract. */
+int rpb_gemm3h_supported(long M, int N, int K, int lda, int ldo);
+int rpb_gemm3h_wprep(const float* W, void* Wz, float* sc, int N, int K, void* stream);
+int rpb_gemm3h(const float* A, const void* Wz, const float* sc, const float* bias, const float* residual, float* out, long M, int N, int K,
+               int lda, int ldo, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,9 @@ SIGNATURES = {
     "rpb_don_bn_bwd_apply": (_I, "pi" + "pi" + "ppp" + "p" + "lii" + "pi" + "pp" + "p"),
     "rpb_don_point_mul": (_I, "ppp" + "ll" + "il" + "i" + "p"),
     "rpb_don_point_mul_bwd": (_I, "ppppp" + "lll" + "i" + "p"),
+    "rpb_gemm3h_supported": (_I, "liiii"),
+    "rpb_gemm3h_wprep": (_I, "ppp" + "ii" + "p"),
+    "rpb_gemm3h": (_I, "pppppp" + "liiii" + "i" + "p"),
 }
 
 _lib = None

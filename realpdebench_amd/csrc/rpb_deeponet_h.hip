@@ -29,21 +29,7 @@
 // unspecified (finite or not), where the default kernel propagates them.
 #include "rpb_mma.h"
 
-// e with m 2^e in [2^TOP, 2^(TOP + 1)) for a finite m > 0, capped at 62; 0 for m == 0
-template <int TOP>
-__device__ __forceinline__ int col_exp(float m) {
-    const int e = TOP + 127 - (int)(__builtin_bit_cast(unsigned, m) >> 23);
-    return m == 0.f ? 0 : (e > 62 ? 62 : e);
-}
-// 2^e as fp32, -126 <= e <= 127
-__device__ __forceinline__ float pow2f(int e) { return asf((unsigned)(e + 127) << 23); }
-
-__device__ __forceinline__ f32x16 mma3h(const u32x4 (&w)[2], const u32x4 (&x)[2], f32x16 c) {
-    c = mfma32h(w[1], x[0], c);
-    c = mfma32h(w[0], x[1], c);
-    c = mfma32h(w[0], x[0], c);
-    return c;
-}
+// col_exp, pow2f and mma3h (operand a = the weights here) come from rpb_mma.h
 // 8 values of one k-step, already scaled -> (hi, lo) fp16 planes as dwords
 __device__ __forceinline__ void split_step(const float (&v)[8], u32x4 (&hp)[2]) {
     bf16x8 h, l;

@@ -238,6 +238,24 @@ __device__ __forceinline__ f32x16 mfma32h(V a, V b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
+// the three products of one k-step from (hi, lo) operand pairs, small terms first: lo*hi, hi*lo, hi*hi (lo*lo <= 2^-22 of the product is
+// dropped); a = the MFMA's A operand (rows of D), b = its B operand (columns of D).  rpb_deeponet_h.hip, rpb_gemm3h.hip
+__device__ __forceinline__ f32x16 mma3h(const u32x4 (&a)[2], const u32x4 (&b)[2], f32x16 c) {
+    c = mfma32h(a[1], b[0], c);
+    c = mfma32h(a[0], b[1], c);
+    c = mfma32h(a[0], b[0], c);
+    return c;
+}
+// The power-of-two scale of one MFMA row / column of activations (a point of rpb_deeponet_h.hip, a token row of rpb_gemm3h.hip):
+// e with m 2^e in [2^TOP, 2^(TOP + 1)) for a finite m > 0, capped at 62 so that 2^e and 2^-e stay normal fp32 numbers; 0 for m == 0
+template <int TOP>
+__device__ __forceinline__ int col_exp(float m) {
+    const int e = TOP + 127 - (int)(__builtin_bit_cast(unsigned, m) >> 23);
+    return m == 0.f ? 0 : (e > 62 ? 62 : e);
+}
+// 2^e as fp32, -126 <= e <= 127
+__device__ __forceinline__ float pow2f(int e) { return asf((unsigned)(e + 127) << 23); }
+
 // ---------------------------------------------------------------------------------- cross-lane
 // x + y from the lane the DPP control names (the halving butterflies of the heads)
 __device__ __forceinline__ float dpp_add(float x, float y, const int ctrl) {

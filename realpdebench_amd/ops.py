@@ -524,6 +524,33 @@ def gemm_nt(A, W, out, M, N, K, bias=None, addvec=None, residual=None, act=0, ld
               flops=2 * M * N * K)
 
 
+def gemm3h_supported(M, N, K, lda=None, ldo=None):
+    """True when ``gemm_nt_f16x2`` takes the product (csrc/rpb_gemm3h.hip: K % 64 == 0 up to 512, N = 64 / 128 / 256 k, leading
+    dimensions % 4)."""
+    return bool(_lib.load().rpb_gemm3h_supported(M, N, K, K if lda is None else lda, N if ldo is None else ldo))
+
+
+def gemm3h_wprep(W):
+    """The operand of ``gemm_nt_f16x2`` for a weight W[N][K]: ``(planes, sc)`` -- 2 N K fp16 (hi, lo planes of W 2^ew in MFMA B-operand
+    order, as int16 storage) and two floats, sc[0] = 2^-ew.  The exponent is formed and stays on the device."""
+    N, K = W.shape
+    wz = torch.empty(2 * N * K, dtype=torch.int16, device=W.device)
+    sc = torch.empty(2, dtype=F32, device=W.device)
+    _lib.call("rpb_gemm3h_wprep", _p(W), _p(wz, torch.int16), _p(sc), N, K, _stream(), label="gemm3h_wprep", nbytes=12 * N * K)
+    return wz, sc
+
+
+def gemm_nt_f16x2(A, wz, out, M, N, K, bias=None, residual=None, act=0, lda=None, ldo=None):
+    """out[M,N] = epilogue(A[M,K] @ W[N,K]^T) on the opt-in "f16x2" eval arithmetic (csrc/rpb_gemm3h.hip): two fp16 planes per operand,
+    three products per fp32 product, one power-of-two scale per row of A formed inside the launch.  ``wz = gemm3h_wprep(W)``;
+    act: 0 none, 3 ReLU.  A shape ``gemm3h_supported`` refuses is an error here: the caller chooses the path."""
+    planes, sc = wz
+    lda = K if lda is None else lda
+    ldo = N if ldo is None else ldo
+    _lib.call("rpb_gemm3h", _p(A), _p(planes, torch.int16), _p(sc), _p(bias), _p(residual), _p(out), M, N, K, lda, ldo, int(act),
+              _stream(), label=f"gemm3h[N{N},K{K}]", nbytes=4 * (M * lda + M * N) + 4 * N * K, flops=2 * M * N * K)
+
+
 def gemm_tn_split_bf16(M, N, K, ldg=None, lda=None):
     """True when the plain weight-gradient GEMM runs on the bf16 matrix pipe from split operands (csrc/rpb_gemm3x_tn.hip)."""
     return bool(_lib.query("rpb_gemm3x_tn_supported", M, N, K, N if ldg is None else ldg, K if lda is None else lda))

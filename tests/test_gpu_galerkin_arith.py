@@ -1,0 +1,234 @@
+"""GalerkinTransformer3d.set_arith("f16x2") on the GPU: the dense token GEMMs of the eval forward on rpb_gemm3h (the kernel itself:
+tests/test_gpu_gemm3h.py).  ``F16X2_SITES`` routes Q|K|V and lr1 there -- the shapes it is faster on; lr2 and the
+regressor's fc are wired, stay on the default kernel and are switched on for one instance in the reduced-mesh test.
+
+Golden case (tests/golden/galerkin_small.npz; M = 384 token rows): against the reference's vector within the 2e-5 of tests/test_gpu_galerkin.py, against the default path < 5e-6 (the bound of
+tests/test_gpu_mwt_arith.py and tests/test_gpu_deeponet_arith.py for the same arithmetic), not bit-equal to it, two calls bit-equal,
+``set_arith("f32")`` reproduces the default bits; the planes follow an in-place weight change and a ``load_state_dict`` performed in
+"f16x2" mode; a training step is bit-equal under either setting; the reduced cylinder mesh of ``test_cylinder_mode_counts_vs_oracle``
+(freq_dim 128) at B = 1 and 3, also with all four GEMMs on rpb_gemm3h; the native fsi shape through the shipped YAML; ``eval_attn_dropout`` with a fixed mask; the
+eval entry point.
+
+Measured on an MI355X (each test prints its figure; profiles/galerkin_arith_probe.txt holds the probe's output at the cylinder config):
+golden eval against the default path 3.2e-7, against the reference's vector 3.5e-7 (default path 2.9e-7); after the in-place weight changes
+3.5e-7 / 3.4e-7; reduced cylinder mesh 5.7e-7 (B = 1) / 5.8e-7 (B = 3), with all four GEMMs on rpb_gemm3h 6.3e-7 / 6.4e-7; native fsi
+shape 1.7e-7; with the fixed attention-dropout mask 4.9e-7."""
+import os
+
+import pytest
+import torch
+import yaml
+
+from conftest import ROOT, galerkin_golden, rel_l2
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+BOUND = 5e-6
+
+
+def _model_from_golden(g, **extra):
+    from realpdebench_amd.model.galerkin_transformer import GalerkinTransformer3d
+    sd = g["sd"]
+    T, H, W, Cin = g["x"].shape[1:]
+    cfg = dict(n_hidden=256, n_head=4, dim_feedforward=sd["encoder_layers.0.ff.lr1.weight"].shape[0],
+               freq_dim=sd["regressor.fc.weight"].shape[0], fourier_modes_t=g["modes"][0], fourier_modes_x=g["modes"][1],
+               fourier_modes_y=g["modes"][2], norm_eps=1e-7, node_feats=Cin, n_targets=g["shape_out"][-1],
+               shape_in=(T, H, W, Cin), shape_out=g["shape_out"], encoder_dropout=0.05, ffn_dropout=0.05)
+    cfg.update(extra)
+    m = GalerkinTransformer3d(**cfg).cuda()
+    m.load_state_dict(sd)
+    return m
+
+
+class One(torch.utils.data.Dataset):
+    """A one-sample dataset of the given shapes: what ``load_model`` reads its shapes from."""
+
+    def __init__(self, shape_in, shape_out):
+        self.s = (torch.zeros(*shape_in), torch.zeros(*shape_out))
+
+    def __len__(self):
+        return 1
+
+    def __getitem__(self, i):
+        return self.s
+
+
+def test_golden_eval_f16x2_matches_reference_and_default():
+    g = galerkin_golden()
+    m = _model_from_golden(g).eval()
+    x = g["x"].cuda()
+    assert m.arith == "f32"
+    with torch.no_grad():
+        out0 = m(x)
+        assert m.set_arith("f16x2") is m
+        out = m(x)
+        assert torch.equal(m(x), out), "two f16x2 calls must give bit-equal outputs"
+        assert torch.equal(m.set_arith("f32")(x), out0), "set_arith('f32') must reproduce the default output bit for bit"
+    e, e0, d = rel_l2(out.cpu(), g["y_eval"]), rel_l2(out0.cpu(), g["y_eval"]), rel_l2(out.cpu(), out0.cpu())
+    print(f"golden eval: f16x2 against the reference {e:.2e} (default path {e0:.2e}, tol 2e-5), against the default path {d:.2e} (bound 5e-6)")
+    assert out.shape == g["y_eval"].shape and bool(torch.isfinite(out).all())
+    assert not torch.equal(out, out0), "the switch must reach the kernels"
+    assert e < 2e-5
+    assert d < BOUND
+
+
+def test_planes_follow_an_in_place_weight_change():
+    g = galerkin_golden()
+    m = _model_from_golden(g).eval().set_arith("f16x2")
+    x = g["x"].cuda()
+    with torch.no_grad():
+        old = m(x)
+        m.encoder_layers[0].ff.lr2.weight.mul_(1.25)              # in place: same storage, new version
+        out = m(x)
+        want = m.set_arith("f32")(x)
+        m.set_arith("f16x2").encoder_layers[0].ff.lr1.weight.mul_(1.25)      # a weight whose planes are cached: they are rebuilt
+        out1 = m(x)
+        want1 = m.set_arith("f32")(x)
+    d, d1 = rel_l2(out.cpu(), want.cpu()), rel_l2(out1.cpu(), want1.cpu())
+    print(f"after lr2.weight.mul_(1.25): f16x2 against the default path {d:.2e}; after lr1.weight.mul_(1.25) {d1:.2e} (bound 5e-6)")
+    assert not torch.equal(out, old)
+    assert not torch.equal(out1, out), "the planes must be rebuilt when a weight changes in place"
+    assert d < BOUND and d1 < BOUND
+
+
+def test_load_state_dict_in_f16x2_mode_takes_effect():
+    g = galerkin_golden()
+    m = _model_from_golden(g).eval().set_arith("f16x2")
+    x = g["x"].cuda()
+    sd2 = {k: v.clone() for k, v in g["sd"].items()}
+    for k in ("encoder_layers.0.ff.lr1.weight", "encoder_layers.0.attn.linears.1.weight", "encoder_layers.0.attn.linears.2.bias"):
+        sd2[k] = sd2[k] * 0.75
+    with torch.no_grad():
+        old = m(x)
+        m.load_state_dict(sd2)
+        assert m.arith == "f16x2"
+        out = m(x)
+        want = _model_from_golden(dict(g, sd=sd2)).eval()(x)
+    d = rel_l2(out.cpu(), want.cpu())
+    print(f"after load_state_dict in f16x2 mode: against a default-path model of the new weights {d:.2e} (bound 5e-6)")
+    assert not torch.equal(out, old)
+    assert d < BOUND
+
+
+def test_training_step_is_untouched_by_set_arith():
+    g = galerkin_golden()
+    x, t = g["x"].cuda(), g["target"].cuda()
+    res = []
+    for arith in ("f32", "f16x2"):
+        m = _model_from_golden(g).train().set_arith(arith)
+        m._mask_override = {}
+        loss = m.train_loss(x, t).mean()
+        loss.backward()
+        res.append((loss.detach(), {n: p.grad for n, p in m.named_parameters()}))
+    (l0, g0), (l1, g1) = res
+    assert torch.equal(l0, l1)
+    assert sum(v is not None for v in g0.values()) > 10
+    for n in g0:
+        assert (g0[n] is None and g1[n] is None) or torch.equal(g0[n], g1[n]), n
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_reduced_cylinder_mesh(B):
+    """(T, H, W) = (4, 32, 40), modes (4, 16, 20), freq_dim 128: M = 5120 B rows"""
+    from realpdebench_amd.model.galerkin_transformer import GalerkinTransformer3d
+    torch.manual_seed(11)
+    T, H, W, Cin = 4, 32, 40, 3
+    cfg = dict(n_hidden=256, n_head=4, dim_feedforward=256, freq_dim=128, fourier_modes_t=4, fourier_modes_x=16,
+               fourier_modes_y=20, norm_eps=1e-7, node_feats=Cin, n_targets=3, shape_in=(T, H, W, Cin),
+               shape_out=(T, H, W, 3))
+    m = GalerkinTransformer3d(**cfg).cuda().eval()
+    with torch.no_grad():
+        for l in m.encoder_layers[0].attn.linears:
+            l.weight.add_(0.05 * torch.randn_like(l.weight))
+        x = torch.randn(B, T, H, W, Cin, device=DEV)
+        want = m(x)
+        out = m.set_arith("f16x2")(x)
+        assert set(m._f16x2_planes(B * T * H * W)) == {"qkv", "lr1"}          # the sites the kernel is faster on (F16X2_SITES)
+        m.F16X2_SITES = ("qkv", "lr1", "lr2", "fc")                            # on this instance: every wired site
+        assert set(m._f16x2_planes(B * T * H * W)) == {"qkv", "lr1", "lr2", "fc"}
+        out4 = m(x)
+    d, d4 = rel_l2(out.cpu(), want.cpu()), rel_l2(out4.cpu(), want.cpu())
+    print(f"reduced cylinder mesh, B = {B}: f16x2 against the default path {d:.2e}, with lr2 and fc on rpb_gemm3h as well {d4:.2e} (bound 5e-6)")
+    assert bool(torch.isfinite(out).all()) and not torch.equal(out, want)
+    assert bool(torch.isfinite(out4).all()) and not torch.equal(out4, out)
+    assert d < BOUND and d4 < BOUND
+
+
+def test_native_shape_through_yaml_f16x2():
+    """configs/fsi/galerkin_transformer.yaml at B = 1 (81920 token rows)"""
+    from realpdebench_amd.model import load_model
+    with open(os.path.join(ROOT, "realpdebench_amd", "configs", "fsi", "galerkin_transformer.yaml")) as fh:
+        cfg = yaml.safe_load(fh)
+    assert "eval_arith" not in cfg
+    shape_in, shape_out = tuple(cfg["shape_in"]), tuple(cfg["shape_out"])
+    torch.manual_seed(0)
+    m = load_model(One(shape_in, shape_out), device=DEV, **cfg).eval()
+    x = torch.randn(1, *shape_in, device=DEV)
+    with torch.no_grad():
+        want = m(x)
+        out = m.set_arith("f16x2")(x)
+    d = rel_l2(out.cpu(), want.cpu())
+    print(f"fsi, B = 1: f16x2 against the default path {d:.2e} (bound 5e-6)")
+    assert tuple(out.shape) == (1,) + shape_out and bool(torch.isfinite(out).all())
+    assert not torch.equal(out, want)
+    assert d < BOUND
+
+
+def test_eval_attn_dropout_with_a_fixed_mask():
+    g = galerkin_golden()
+    m = _model_from_golden(g).eval()
+    m.eval_attn_dropout = True
+    x = g["x"].cuda()
+    torch.manual_seed(3)
+    m._mask_override = {"attn": (torch.rand(x.shape[0], 4, 64, 64) >= 0.5).float().mul(2).cuda()}
+    with torch.no_grad():
+        want = m(x)
+        out = m.set_arith("f16x2")(x)
+        plain = _model_from_golden(g).eval()(x)
+    d = rel_l2(out.cpu(), want.cpu())
+    print(f"eval_attn_dropout with a fixed mask: f16x2 against the default path {d:.2e} (bound 5e-6)")
+    assert not torch.equal(want, plain), "the mask must reach the attention"
+    assert not torch.equal(out, want)
+    assert d < BOUND
+
+
+def test_eval_entrypoint_takes_eval_arith_galerkin(tmp_path):
+    """`python -m realpdebench_amd.eval` with `eval_arith: f16x2` on a small synthetic Galerkin YAML: the metrics agree with the default
+    arithmetic's to 1e-4 relative; a value the model rejects ends the run with its ValueError (a non-zero exit of the command)."""
+    from realpdebench_amd import eval as ev
+    from realpdebench_amd.model import load_model
+    with open(os.path.join(ROOT, "realpdebench_amd", "configs", "fsi", "galerkin_transformer.yaml")) as fh:
+        cfg = yaml.safe_load(fh)
+    shape = [4, 6, 8, 3]
+    cfg.update(exp_name="t", results_path=str(tmp_path), shape_in=shape, shape_out=shape, n_train=4, n_val=4, fourier_modes_t=2,
+               fourier_modes_x=3, fourier_modes_y=4, freq_dim=64, is_use_tb=None, train_batch_size=2, test_batch_size=2, num_update=100)
+    torch.manual_seed(0)
+    m = load_model(One(shape, shape), device="cpu", **cfg)
+    with torch.no_grad():
+        for l in m.encoder_layers[0].attn.linears:
+            l.weight.add_(0.05 * torch.randn_like(l.weight))
+    ck = str(tmp_path / "model_0.pth")
+    torch.save({"model_state_dict": {k: v.cpu() for k, v in m.state_dict().items()}, "train_losses": [1.0], "val_losses": {}, "iteration": 7,
+                "best_iteration": 7, "best_val_loss": 0.5}, ck)             # the reference's format (train.py)
+    path = tmp_path / "galerkin.yaml"
+    path.write_text(yaml.safe_dump(cfg))
+    base = ev.main(["--config", str(path), "--checkpoint_path", ck])
+    path2 = tmp_path / "galerkin_f16x2.yaml"
+    path2.write_text(yaml.safe_dump(dict(cfg, eval_arith="f16x2")))
+    fast = ev.main(["--config", str(path2), "--checkpoint_path", ck])
+    assert set(base) == set(fast)
+    n = 0
+    for k in base:
+        if not isinstance(base[k], (int, float)):
+            assert base[k] == fast[k]
+            continue
+        a, b = float(base[k]), float(fast[k])
+        if a == a and b == b:
+            assert abs(a - b) <= 1e-4 * max(abs(a), 1e-12), (k, a, b)
+            n += 1
+    assert n >= 5
+    path3 = tmp_path / "bad.yaml"
+    path3.write_text(yaml.safe_dump(dict(cfg, eval_arith="fp8")))
+    with pytest.raises((ValueError, SystemExit)) as exc:
+        ev.main(["--config", str(path3), "--checkpoint_path", ck])
+    assert not (isinstance(exc.value, SystemExit) and exc.value.code in (0, None))
