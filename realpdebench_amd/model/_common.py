@@ -1,6 +1,7 @@
 """Plumbing the models share between their parameter trees and the C ABI: the autograd glue (``HipFunction``), the weight-gradient
 finish (``wgrad``, ``colsum``, ``sum_rows``), the weight matrix of a padded 3x3x3 convolution (``padded_weight``), the cache of
-kernel-side layouts (``LayoutCache``) and the base of the models whose training step is not built (``EvalOnly``)."""
+kernel-side layouts (``LayoutCache``) and the base of the models that evaluate by default and train by opt-in (``EvalByDefault``: MWT3d,
+DeepONet, CNO3d)."""
 import torch
 
 from .. import ops
@@ -120,31 +121,91 @@ class LayoutCache:
         return hit[1]
 
 
-class EvalOnly:
-    """Mixin in front of ``Model`` for the models whose training step is not built (MWT3d, DeepONet): evaluation forward,
-    ``train_loss`` as a value, rollout and checkpoint I/O.  Every attempt to backpropagate raises ``NotImplementedError`` with
-    ``training_unavailable`` instead of returning tensors without a graph; ``trainer.make_trainer`` refuses at construction."""
+class EvalByDefault:
+    """Mixin in front of ``Model`` for MWT3d, DeepONet and CNO3d: evaluation by default, training by opt-in.
+
+    By default an instance covers the evaluation forward, ``train_loss`` as a value, the rollout and checkpoint I/O; every attempt to
+    backpropagate raises ``NotImplementedError`` with the class's ``training_unavailable`` instead of returning tensors without a
+    graph, and ``trainer.make_trainer`` refuses at construction.  ``enable_training()`` (``hip_training: true`` through ``load_model``)
+    opts ONE instance in -- the class and every other instance stay as they are: in ``train()`` mode ``forward`` / ``train_loss`` then
+    run through ``HipFunction``, ``eval()`` mode stays the evaluation forward and still refuses a graph.
+
+    A model provides ``training_unavailable`` (``TRAIN_MSG.format(family, class name)``), ``DP_MSG``, ``BATCH_STATISTICS``, ``ARITHS``,
+    ``check_input(shape)``, ``_forward_eval(x, ...)`` (runs under ``torch.no_grad()``) and ``_forward_hip`` / ``_backward_hip``."""
     TRAIN_MSG = ("the {} training step is not built yet: {} on MI355X covers the evaluation forward, train_loss as a value under "
                  "torch.no_grad(), the rollout and checkpoint I/O")
-    training_unavailable = None        # subclasses: TRAIN_MSG.format(family, class name)
+    training_unavailable = None        # the class's refusal; None on an enabled instance
+    hip_training = False               # enable_training() sets it on the instance
+    dp_unavailable = None              # enabled instances: why trainer.make_trainer refuses more than one rank (the class's DP_MSG)
+    DP_MSG = None                      # the class's reason
+    # The class's training step computes BatchNorm statistics over the batch: they couple the samples of a step, so an enabled instance
+    # stops declaring ``batch_independent`` (no micro-batching).
+    BATCH_STATISTICS = False
+    ARITHS = None                      # the class's tuple of what ``set_arith`` takes, two names or more
+
+    def set_arith(self, arith):
+        """Each class says in its own docstring what the switch moves."""
+        if arith not in self.ARITHS:
+            names = [repr(a) for a in self.ARITHS]
+            raise ValueError(f"arith must be {', '.join(names[:-1])} or {names[-1]}, got {arith!r}")
+        self.arith = arith
+        return self
+
+    def enable_training(self):
+        """Opt this instance into the HIP training step (``hip_training: true`` in a config)."""
+        self.hip_training = True
+        self.training_unavailable = None
+        if self.BATCH_STATISTICS:
+            self.batch_independent = False
+        self.dp_unavailable = self.DP_MSG
+        return self
 
     def _require_eval(self, x):
-        """First thing in ``forward``: never hand back a tensor that silently carries no graph.  Under grad mode anything that asks for
-        a gradient is refused (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with
-        requires_grad off)."""
+        """Never hand back a tensor that silently carries no graph.  Under grad mode anything that asks for a gradient is refused
+        (inference goes through torch.no_grad(), as rollout.py and eval.py do, or through parameters with requires_grad off).  The
+        message is the class's: an enabled instance refuses in ``eval()`` mode with the same words."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(self.training_unavailable)
+            raise NotImplementedError(type(self).training_unavailable)
 
     def _require_hip(self, x):
         if not x.is_cuda:
             raise RuntimeError(f"{type(self).__name__} runs on MI355X only: there is no CPU fallback (move the model and its input to "
                                "'cuda')")
 
+    def forward(self, x, **eval_args):
+        """One order of refusals for every mode: the input's shape, what cannot be differentiated, the device."""
+        self.check_input(tuple(x.shape))
+        if self.hip_training and self.training:      # the opt-in training step, through HipFunction
+            assert not eval_args, eval_args
+            if torch.is_grad_enabled() and x.requires_grad:
+                raise NotImplementedError(f"{type(self).__name__} training computes no input gradient (no trainer asks for one)")
+            self._require_hip(x)
+            if not torch.is_grad_enabled():
+                return self._forward_hip(x, None)
+            return HipFunction.apply(x, self, *self.parameters())
+        self._require_eval(x)
+        self._require_hip(x)
+        with torch.no_grad():
+            return self._forward_eval(x.contiguous().float(), **eval_args)
+
     def train_loss(self, input, target):
-        """Elementwise MSE (the reference's ``mse_loss(pred, target)``), as a value: under grad mode it raises."""
-        if torch.is_grad_enabled():
-            raise NotImplementedError(self.training_unavailable)
+        """Elementwise ``mse_loss(pred, target)`` (the reference's): with a graph on an enabled instance in ``train()`` mode, otherwise
+        as a value -- under grad mode it raises."""
+        if not (self.hip_training and self.training) and torch.is_grad_enabled():
+            raise NotImplementedError(type(self).training_unavailable)
         return super().train_loss(input, target)
+
+    def load_checkpoint(self, checkpoint_path, device="cpu"):
+        """The base class's loader (``model_state_dict`` + bookkeeping, realpdebench/model/model.py); a bare weights file gives the
+        bookkeeping entries of an untrained run (iteration 0, no losses).  (MWT3d matches keys and shapes instead, as its reference does.)"""
+        ck = torch.load(checkpoint_path, map_location="cpu")
+        if "model_state_dict" in ck:
+            meta = super().load_checkpoint(checkpoint_path, "cpu")
+        else:
+            self.load_state_dict(ck)
+            meta = self._bookkeeping({})
+        self.to(device)
+        return meta
 
     @staticmethod
     def _bookkeeping(book):

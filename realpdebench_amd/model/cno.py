@@ -6,12 +6,16 @@ model/load_model.py:60-75) for the reference's ``configs/*/cno.yaml``.
 at full resolution, each followed by an eval BatchNorm3d, LeakyReLU(0.2), a residual add or a channel concat.
 
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
-every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``), ``trainer.make_trainer`` refuses the model at
+every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``), ``trainer.make_trainer`` refuses the model at
 construction and BatchNorm3d uses its running statistics in every mode.  ``enable_training()`` (``hip_training: true`` through
 ``load_model``) opts an instance in: in ``train()`` mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction`` with
 batch-statistics BatchNorm (csrc/rpb_cno_train.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
 implicit GEMM for the seven ``EXACT_DGRAD`` layers) and the weight gradient is ``_common.wgrad``; ``eval()`` mode stays the code below,
 untouched.
+
+The data flow is stated once, as data: ``Schedule`` lists the 35 layer steps over buffer handles, and derives from that list where a
+buffer has its last producer, where it is read for the last time and whether anyone reads its fp32 rows.  Three executors walk it and
+supply only what differs: ``_eval_bf16x3``, ``_eval_f16x2`` and ``_train_rows`` (whose tape the backward pass walks).
 
 Pipeline (activations channels-last rows ``[B * T * H * W][C]``, mesh (T, H, W)):
   rpb_cno_pack      x [M][in_dim] -> bf16 planes P[3][M][64], columns in_dim..63 zero
@@ -31,19 +35,21 @@ Parameters carry the reference's names, shapes and dtypes (the same ``nn`` modul
 ``forward`` -- included), so ``state_dict`` / ``load_state_dict`` are the reference's; kernel layouts are derived tensors rebuilt when a
 parameter changed.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
 from .. import _lib
 from ..ops import Sub, _p, _stream, amax_exp_finish, conv3_f16x2_weights, conv3x_wprep, gemm_nt, split2h, split3
 from ..ops import add as ops_add
-from ._common import EvalOnly, HipFunction, padded_weight, wgrad
+from ._common import EvalByDefault, padded_weight, wgrad
 from .model import Model
 
 I16 = torch.int16
 N_LAYERS = 3
 MAX_CH = 64                    # widest first-layer input / last-layer output: one 64-channel tile
-N_WORDS = 32                   # activation buffers of one f16x2 forward (``_forward_rows_f16x2``): one amax / exponent word each
+ARITHS = ("f32", "f16x2")      # CNO3d.set_arith
 # Layers whose data gradient runs on the exact-fp32 implicit GEMM (rpb_gemm_nt) instead of the bf16x3 kernel: the ones that add into the
 # gradient of the neck's residual chain.  A BatchNorm shift gradient is a column sum of that gradient, which sees a per-channel bias of
 # the error sqrt(M) times stronger than its unbiased part; the bf16x3 kernel's error as a data gradient has such a bias (column mean 3-4
@@ -53,6 +59,72 @@ EXACT_DGRAD = frozenset(["ED_expansion.3"] + [f"res_nets.{i}.1" for i in range(3
 # reference defaults of every keyword load_model never passes (cno.py:240-256)
 DEFAULTS = dict(N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001, filter_size=6, lrelu_upsampling=2,
                 half_width_mult=0.8, radial=False, batch_norm=True, out_size=1, expand_input=False, latent_lift_proj_dim=64, add_inv=True)
+
+
+# ----------------------------------------------------------------------------------------------------------- the data flow, once
+Layer = namedtuple("Layer", "name src dst col act res")      # src / dst / res: indices into ``bufs``; dst None: the model output
+
+
+class Buf(namedtuple("Buf", "ld written")):
+    """An activation buffer, rows [M][ld]: its producers write columns 0..written-1."""
+
+    @property
+    def zero(self):
+        """The producers leave columns unwritten that a convolution reads: they must read as zero (zero weights do not cancel NaN)."""
+        return self.written < self.ld
+
+
+class Schedule:
+    """The 35 layers ``forward`` runs (cno.py:466-521), as plain data: no storage, no device.  ``bufs[0]`` is the packed input;
+    ``layers`` in launch order, each reading ``src`` whole and writing its ``Co`` channels at column ``col`` of ``dst`` after the affine,
+    LeakyReLU (``act``) and the residual add of ``res``; ``keep``: name -> buffer of the five tensors ``forward(x, keep=)`` hands out.
+    A concat is two producers writing column ranges of one buffer.  Derived from the list, for the executors:
+      last_write[b]   index of the last layer that writes b (``finish`` of the f16x2 path runs there, once per buffer)
+      last_read[b]    index of the last layer that reads b as ``src`` or ``res`` (the evaluation executors drop its storage there)
+      residuals       the buffers some later layer adds as ``res``
+      kept            ``keep`` the other way round: buffer -> name"""
+
+    def __init__(self, in_dim, ef=(16, 32, 64, 128)):
+        self.bufs, self.layers, self.keep = [], [], {}
+
+        def buf(width):
+            self.bufs.append(Buf(max(width, 64), width))
+            return len(self.bufs) - 1
+
+        def layer(name, src, dst=None, col=0, act=True, res=None):
+            self.layers.append(Layer(name, src, dst, col, act, res))
+            return dst
+
+        def res_block(i, x, width):
+            """res_nets[i]: x + BN(conv(L(BN(conv x))))"""
+            h, y = buf(width), buf(width)
+            layer(f"res_nets.{i}.1", x, h)
+            return layer(f"res_nets.{i}.2", h, y, act=False, res=x)
+
+        x = layer("lift.0", buf(in_dim), buf(64))
+        x = self.keep["lift"] = layer("lift.1", x, buf(ef[0]), act=False)
+        skip = []
+        for i in range(N_LAYERS):
+            skip.append(res_block(i, x, ef[i]))
+            self.keep[f"skip{i}"] = skip[i]
+            x = layer(f"encoder.{i}", x, buf(ef[i + 1]))
+        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
+            x = res_block(N_LAYERS + 5 - j, x, ef[3])
+        self.keep["neck"] = x
+        x, width = layer("ED_expansion.3", x, buf(ef[3])), ef[3]
+        for i in range(N_LAYERS):                                     # decoder: cat(x, ED_expansion(skip)) is two producers of one buffer
+            x = layer(f"decoder_inv.{i}", x, buf(width))              # 128, 128, 64 channels
+            w = ef[2 - i]                                             # 64, 32, 16: each producer's channels
+            cat, width = buf(2 * w), 2 * w                            # (2 * 16 = 32 of 64 columns: 32..63 stay zero)
+            layer(f"decoder.{i}", x, cat, col=0)
+            x = layer(f"ED_expansion.{2 - i}", skip[2 - i], cat, col=w)
+        x = layer("project.0", x, buf(64))
+        layer("project.1", x, act=False)
+
+        self.last_write = {L.dst: i for i, L in enumerate(self.layers) if L.dst is not None}
+        self.last_read = {b: i for i, L in enumerate(self.layers) for b in (L.src, L.res) if b is not None}
+        self.residuals = {L.res for L in self.layers} - {None}
+        self.kept = {b: name for name, b in self.keep.items()}
 
 
 # ----------------------------------------------------------------------------------------------------------- parameter tree
@@ -181,11 +253,14 @@ def _iptr(t):
     return _p(t, t.t.dtype) if isinstance(t, Sub) else _p(t, torch.int32)
 
 
-class CNO3d(EvalOnly, Model):
+class CNO3d(EvalByDefault, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
-    training_unavailable = EvalOnly.TRAIN_MSG.format("CNO", "CNO3d")
-    hip_training = False                            # enable_training() sets it on the instance
-    dp_unavailable = None                           # (enabled instances: why trainer.make_trainer refuses more than one rank)
+    training_unavailable = EvalByDefault.TRAIN_MSG.format("CNO", "CNO3d")
+    # An enabled instance computes batch statistics: they couple the samples of a step, so it stops declaring ``batch_independent`` (no
+    # micro-batching) and refuses more than one rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for CNO is not built).
+    BATCH_STATISTICS = True
+    DP_MSG = "CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
+    ARITHS = ARITHS
 
     def __init__(self, in_dim, in_size, N_layers, N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001,
                  filter_size=6, lrelu_upsampling=2, half_width_mult=0.8, radial=False, batch_norm=True, out_dim=1, out_dim_mult=1,
@@ -225,6 +300,7 @@ class CNO3d(EvalOnly, Model):
         self.decoder = nn.ModuleList([CNOBlock3d(dec_in[i], dec_out[i]) for i in range(N_LAYERS)])
         self.decoder_inv = nn.ModuleList([CNOBlock3d(inv[i], inv[i]) for i in range(N_LAYERS + 1)])                  # [3] is never used
         self.res_nets = nn.Sequential(*([ResidualBlock3d(ef[l]) for l in range(N_LAYERS)] + [ResidualBlock3d(ef[N_LAYERS]) for _ in range(6)]))
+        self.schedule = Schedule(self.in_dim, ef)
         self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
 
     def set_arith(self, arith):
@@ -232,39 +308,7 @@ class CNO3d(EvalOnly, Model):
         planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power of
         two, three products, dropped term <= 2^-22; csrc/rpb_cno3h.hip).  Only the evaluation forward changes:
         the opt-in training step (``enable_training()``) stays on its kernels under either setting."""
-        if arith not in ("f32", "f16x2"):
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
-
-    # ------------------------------------------------------------------ the opt-in training step
-    def enable_training(self):
-        """Opt this instance into the HIP training step (batch-statistics BatchNorm; ``hip_training: true`` in a config).  Batch statistics
-        couple the samples of a step, so the instance stops declaring ``batch_independent`` (no micro-batching) and refuses more than one
-        rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for CNO is not built)."""
-        self.hip_training = True
-        self.training_unavailable = None
-        self.batch_independent = False
-        self.dp_unavailable = ("CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, "
-                               "run it on one rank")
-        return self
-
-    def _require_eval(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(type(self).training_unavailable)
-
-    # ------------------------------------------------------------------ checkpoints
-    def load_checkpoint(self, checkpoint_path, device="cpu"):
-        """The base class's loader (``model_state_dict`` + bookkeeping, realpdebench/model/model.py); a bare weights file gives the
-        bookkeeping entries of an untrained run (iteration 0, no losses), as MWT3d and DeepONet do."""
-        ck = torch.load(checkpoint_path, map_location="cpu")
-        if "model_state_dict" in ck:
-            meta = super().load_checkpoint(checkpoint_path, "cpu")
-        else:
-            self.load_state_dict(ck)
-            meta = self._bookkeeping({})
-        self.to(device)
-        return meta
+        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _convs(self):
@@ -283,31 +327,19 @@ class CNO3d(EvalOnly, Model):
         return out
 
     def _prep(self, device):
-        tensors = list(self.parameters()) + list(self.buffers())
-        return self._layouts.get("prep", tensors, lambda: self._build_prep(device))
+        """The evaluation forward's layouts under the selected arithmetic (one cache entry per arithmetic, same invalidation rule)."""
+        tensors, arith = list(self.parameters()) + list(self.buffers()), self.arith
+        return self._layouts.get("prep_" + arith, tensors, lambda: self._build_prep(device, arith))
 
-    def _build_prep(self, device):
+    def _build_prep(self, device, arith):
+        """Per layer the folded affine and the weights: three bf16 planes (``"f32"``; ``ew`` None) or two scaled fp16 planes with their
+        exponent ``ew`` (``"f16x2"``; int32 [1] on the device)."""
         prep = {}
         for name, (conv, bn) in self._convs().items():
             Co, Ci = conv.weight.shape[:2]
             N, K = max(Co, 64), max(Ci, 64)
-            wz = self.k_wprep(padded_weight(conv, N, K).to(device), N, K)
-            sc, sh = fold_affine(conv, bn, N)
-            prep[name] = dict(wz=wz, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
-        return prep
-
-    def _prep_f16x2(self, device):
-        """``_prep`` for ``set_arith("f16x2")``: per layer the weights as two scaled fp16 planes with their exponent ``ew`` (int32 [1] on
-        the device) next to the same folded affine; same cache, same invalidation rule."""
-        tensors = list(self.parameters()) + list(self.buffers())
-        return self._layouts.get("prep_f16x2", tensors, lambda: self._build_prep_f16x2(device))
-
-    def _build_prep_f16x2(self, device):
-        prep = {}
-        for name, (conv, bn) in self._convs().items():
-            Co, Ci = conv.weight.shape[:2]
-            N, K = max(Co, 64), max(Ci, 64)
-            wz, ew = conv3_f16x2_weights(padded_weight(conv, N, K).to(device), N, K)
+            wm = padded_weight(conv, N, K).to(device)
+            wz, ew = conv3_f16x2_weights(wm, N, K) if arith == "f16x2" else (self.k_wprep(wm, N, K), None)
             sc, sh = fold_affine(conv, bn, N)
             prep[name] = dict(wz=wz, ew=ew, sc=sc.to(device), sh=sh.to(device), N=N, K=K, Co=Co)
         return prep
@@ -406,31 +438,35 @@ class CNO3d(EvalOnly, Model):
                   nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))
 
     # ------------------------------------------------------------------ the training step
-    def _train_rows(self, x, B, mesh, state):
-        """x [M][in_dim] fp32 -> [M][out_dim] fp32 with batch-statistics BatchNorm (the running statistics are updated).  The data flow is
-        ``_forward_rows``'s; a BatchNorm layer is the raw convolution (fp32 rows ``y``), the statistics and one row pass that writes fp32
-        rows and planes of ``v``.  ``state`` (a dict, or None) receives the tape the backward pass walks: per layer the buffers it read and
-        wrote, ``y`` and (a, b, mean, rstd)."""
-        dev, M = x.device, x.shape[0]
+    def _train_rows(self, x, mesh, state):
+        """x [M][in_dim] fp32 -> [M][out_dim] fp32 with batch-statistics BatchNorm (the running statistics are updated): the schedule on
+        ``_Act`` buffers, all of which stay (the tape holds them).  A BatchNorm layer is the raw convolution (fp32 rows ``y``), the
+        statistics and one row pass that writes fp32 rows and planes of ``v``.  ``state`` (a dict, or None) receives the tape the
+        backward pass walks: per layer the buffers it read and wrote, ``y`` and (a, b, mean, rstd)."""
+        dev, M, S = x.device, x.shape[0], self.schedule
         prep, convs, rows = self._prep_train(dev), self._convs(), self.k_bn_rows()
         tape, touched, counters = [], [], []
-
-        def buf(ld, written):
-            return _Act(M, ld, dev, zero=written < ld)
-
-        def layer(name, src, dst=None, col=0, act=True, res=None):
+        acts = {0: _Act(M, S.bufs[0].ld, dev, S.bufs[0].zero)}        # the input: rows zeroed and filled, the pack kernel writes the planes
+        acts[0].rows[:, :self.in_dim] = x
+        self.k_pack(x, acts[0].planes.t, M, self.in_dim)
+        out = None
+        for L in S.layers:
+            name, col, act = L.name, L.col, L.act
+            if L.dst is not None and L.dst not in acts:
+                acts[L.dst] = _Act(M, S.bufs[L.dst].ld, dev, S.bufs[L.dst].zero)
+            src, dst, res = acts[L.src], acts.get(L.dst), acts.get(L.res)
             s, (conv, bn) = prep[name], convs[name]
             N, K, Co = s["N"], s["K"], s["Co"]
             assert src.ld == K, name
             rec = dict(name=name, src=src, dst=dst, col=col, act=act, res=res, y=None, ab=None, out=None)
             tape.append(rec)
-            if bn is False:                                           # lift / project: today's fused launch
+            if bn is False:                                           # lift / project: the evaluation forward's fused launch
                 if dst is None:
-                    rec["out"] = torch.empty(M, Co, device=dev, dtype=torch.float32)
-                self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, Co, act, out=rec["out"] if dst is None else dst.at(col),
+                    out = rec["out"] = torch.empty(M, Co, device=dev, dtype=torch.float32)
+                self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, Co, act, out=out if dst is None else dst.at(col),
                             ldo=Co if dst is None else dst.ld, out_planes=None if dst is None else dst.planes.ptr(col),
                             ldp=0 if dst is None else dst.ld)
-                return rec["out"]
+                continue
             y = torch.empty(M, N, device=dev, dtype=torch.float32)
             self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, N, 0, out=y, ldo=N)
             part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
@@ -442,52 +478,6 @@ class CNO3d(EvalOnly, Model):
             rec["y"], rec["ab"] = y, ab
             touched.extend((bn.running_mean, bn.running_var))
             counters.append(bn.num_batches_tracked)
-
-        def res_block(i, xa, width):
-            """res_nets[i]: x + BN(conv(L(BN(conv x))))"""
-            ld = max(width, 64)
-            h, ya = buf(ld, width), buf(ld, width)
-            layer(f"res_nets.{i}.1", xa, h)
-            layer(f"res_nets.{i}.2", h, ya, act=False, res=xa)
-            return ya
-
-        ef = self.encoder_features
-        p0 = buf(64, self.in_dim)
-        p0.rows[:, :self.in_dim] = x
-        self.k_pack(x, p0.planes.t, M, self.in_dim)
-        p1 = buf(64, 64)
-        layer("lift.0", p0, p1)
-        xa = buf(64, ef[0])
-        layer("lift.1", p1, xa, act=False)
-        skip = []
-        for i in range(N_LAYERS):
-            skip.append(res_block(i, xa, ef[i]))
-            nxt = buf(max(ef[i + 1], 64), ef[i + 1])
-            layer(f"encoder.{i}", xa, nxt)
-            xa = nxt
-        n_res = len(self.res_nets)
-        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
-            xa = res_block(n_res - 1 - j, xa, ef[3])
-        a = buf(128, 128)
-        layer("ED_expansion.3", xa, a)
-        b = buf(128, 128)
-        layer("decoder_inv.0", a, b)
-        c1 = buf(128, 128)
-        layer("decoder.0", b, c1, col=0)
-        layer("ED_expansion.2", skip[2], c1, col=64)
-        b = buf(128, 128)
-        layer("decoder_inv.1", c1, b)
-        c2 = buf(64, 64)
-        layer("decoder.1", b, c2, col=0)
-        layer("ED_expansion.1", skip[1], c2, col=32)
-        b = buf(64, 64)
-        layer("decoder_inv.2", c2, b)
-        c3 = buf(64, 32)
-        layer("decoder.2", b, c3, col=0)
-        layer("ED_expansion.0", skip[0], c3, col=16)
-        d = buf(64, 64)
-        layer("project.0", c3, d)
-        out = layer("project.1", d, act=False)
         # the kernels wrote the running statistics through raw pointers: the layout cache is keyed on the version counters
         for t in touched:
             torch.autograd.graph.increment_version(t)
@@ -502,10 +492,7 @@ class CNO3d(EvalOnly, Model):
     def _forward_hip(self, x, state):
         x = x.contiguous().float()
         B, T, H, W, C = x.shape
-        out = self._train_rows(x.view(B * T * H * W, C), B, (T, H, W), state).view(B, T, H, W, self.out_dim)
-        if self.out_dim_mult > 1:                                     # (as in ``forward``: a view of the channels-last rows)
-            out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
-        return out
+        return self._shaped(self._train_rows(x.view(B * T * H * W, C), (T, H, W), state), x.shape)
 
     @torch.no_grad()
     def _backward_hip(self, state, g_out, need_gx=False):
@@ -568,164 +555,65 @@ class CNO3d(EvalOnly, Model):
         return grads
 
     # ------------------------------------------------------------------ forward
-    def _forward_rows(self, x, B, mesh, keep=None):
-        """x [M][in_dim] fp32 -> [M][out_dim] fp32.  ``keep`` (a dict) receives the fp32 rows of the lift output, ``skip[0..2]`` and the
-        neck output (tests); the extra fp32 stores do not change any value."""
-        if self.arith == "f16x2":
-            return self._forward_rows_f16x2(x, mesh, keep)
-        dev = x.device
-        M = x.shape[0]
-        prep = self._prep(dev)
-        want = keep is not None
+    def _eval_bf16x3(self, x, mesh, keep=None):
+        """x [M][in_dim] fp32 -> [M][out_dim] fp32: the schedule on ``_Planes`` buffers.  A layer also writes its fp32 rows [M][Co] where
+        someone reads them: a later residual, ``keep`` (a dict: the fp32 rows of the lift output, ``skip[0..2]`` and the neck output, for
+        tests; the extra fp32 stores do not change any value) or the caller.  A buffer's storage goes after its last reader."""
+        dev, M, S, prep = x.device, x.shape[0], self.schedule, self._prep(x.device)
+        wanted = S.residuals | (set(S.kept) if keep is not None else set())
+        planes, rows = {0: _Planes(M, 64, dev, zero=False)}, {}      # (the pack kernel writes the input's zero pad itself)
+        self.k_pack(x, planes[0].t, M, self.in_dim)
+        for i, L in enumerate(S.layers):
+            s, src, res = prep[L.name], planes[L.src], None if L.res is None else rows[L.res]     # (the residual's rows [M][width])
+            assert src.ld == s["K"], L.name
+            if L.dst is not None and L.dst not in planes:
+                planes[L.dst] = _Planes(M, S.bufs[L.dst].ld, dev, S.bufs[L.dst].zero)
+            dst = planes.get(L.dst)
+            out = torch.empty(M, s["Co"], device=dev, dtype=torch.float32) if dst is None or L.dst in wanted else None
+            self.k_conv(src.ptr(), s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, s["Co"], L.act, res=res,
+                        ldr=0 if res is None else res.shape[1], out=out, ldo=s["Co"], out_planes=None if dst is None else dst.ptr(L.col),
+                        ldp=0 if dst is None else dst.ld)
+            if dst is not None and out is not None:                   # (such a buffer has this one producer, at column 0)
+                rows[L.dst] = out
+                if keep is not None and L.dst in S.kept:
+                    keep[S.kept[L.dst]] = out
+            for b in (L.src, L.res):
+                if S.last_read.get(b) == i:
+                    planes.pop(b, None)
+                    rows.pop(b, None)
+        return out
 
-        def layer(name, src, dst=None, col=0, act=True, res=None, f32=False, nvalid=None):
-            """src: _Planes read whole; dst: _Planes written at column ``col``; returns the fp32 rows [M][nvalid] when asked for"""
-            s = prep[name]
-            assert src.ld == s["K"], name
-            nv = s["Co"] if nvalid is None else nvalid
-            out = torch.empty(M, nv, device=dev, dtype=torch.float32) if f32 else None
-            self.k_conv(src.ptr(), s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, nv, act, res=res, ldr=0 if res is None else res.shape[1],
-                        out=out, ldo=nv, out_planes=None if dst is None else dst.ptr(col), ldp=0 if dst is None else dst.ld)
-            return out
-
-        def planes(ld, written):
-            return _Planes(M, ld, dev, zero=written < ld)
-
-        def res_block(i, xp, xf, width, f32=False):
-            """res_nets[i] on (planes, fp32 rows) of its input -> (planes, fp32 rows or None) of x + BN(conv(L(BN(conv x))))"""
-            ld = max(width, 64)
-            hp, yp = planes(ld, width), planes(ld, width)
-            layer(f"res_nets.{i}.1", xp, hp)
-            yf = layer(f"res_nets.{i}.2", hp, yp, act=False, res=xf, f32=f32)
-            return yp, yf
-
-        ef = self.encoder_features
-        p0 = planes(64, 64)                                           # (the pack kernel writes the zero pad itself)
-        self.k_pack(x, p0.t, M, self.in_dim)
-        p1 = planes(64, 64)
-        layer("lift.0", p0, p1)
-        xp = planes(64, ef[0])
-        xf = layer("lift.1", p1, xp, act=False, f32=True)
-        if want:
-            keep["lift"] = xf
-        skip = []
-        for i in range(N_LAYERS):
-            sp, sf = res_block(i, xp, xf, ef[i], f32=want)
-            if want:
-                keep[f"skip{i}"] = sf
-            skip.append(sp)
-            nxt = planes(max(ef[i + 1], 64), ef[i + 1])
-            xf = layer(f"encoder.{i}", xp, nxt, f32=True)
-            xp = nxt
-        n_res = len(self.res_nets)
-        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
-            last = j == 5
-            xp, xf = res_block(n_res - 1 - j, xp, xf, ef[3], f32=not last or want)
-        if want:
-            keep["neck"] = xf
-        # decoder: cat(x, ED_expansion(skip)) is two producers of one plane buffer
-        a = planes(128, 128)
-        layer("ED_expansion.3", xp, a)
-        b = planes(128, 128)
-        layer("decoder_inv.0", a, b)
-        c1 = planes(128, 128)
-        layer("decoder.0", b, c1, col=0)                              # 64 channels -> columns 0..63
-        layer("ED_expansion.2", skip[2], c1, col=64)                  # 64 channels -> columns 64..127
-        b = planes(128, 128)
-        layer("decoder_inv.1", c1, b)
-        c2 = planes(64, 64)
-        layer("decoder.1", b, c2, col=0)                              # 32 -> columns 0..31
-        layer("ED_expansion.1", skip[1], c2, col=32)                  # 32 -> columns 32..63
-        b = planes(64, 64)
-        layer("decoder_inv.2", c2, b)
-        c3 = planes(64, 32)
-        layer("decoder.2", b, c3, col=0)                              # 16 -> columns 0..15
-        layer("ED_expansion.0", skip[0], c3, col=16)                  # 16 -> columns 16..31; 32..63 stay zero
-        d = planes(64, 64)
-        layer("project.0", c3, d)
-        return layer("project.1", d, act=False, f32=True)
-
-    def _forward_rows_f16x2(self, x, mesh, keep=None):
-        """``_forward_rows`` under ``set_arith("f16x2")``: the same data flow on ``_ActH`` buffers.  Every layer writes fp32 rows and maxes
-        into the word of its destination; when all producers of a buffer are done (two for a concat) ``finish`` turns the word into the
+    def _eval_f16x2(self, x, mesh, keep=None):
+        """``_eval_bf16x3`` under ``set_arith("f16x2")``: the schedule on ``_ActH`` buffers.  Every layer writes fp32 rows and maxes into
+        the word of its destination; when all producers of a buffer are done (two for a concat) ``finish`` turns the word into the
         exponent and splits the rows into planes -- one extra read and write of the activation per buffer, no host synchronisation
         (DESIGN.md section 17.2).  Residuals and ``keep`` read the fp32 rows, which always exist here."""
-        dev, M = x.device, x.shape[0]
-        prep = self._prep_f16x2(dev)
-        words = torch.zeros(N_WORDS, dtype=torch.int32, device=dev)  # one word per buffer, zeroed once
-        used = [0]
-
-        def buf(ld, written, rows=True):
-            used[0] += 1
-            return _ActH(M, ld, dev, written < ld, words, used[0] - 1, rows=rows)
-
-        def layer(name, src, dst=None, col=0, act=True, res=None):
-            """src: a finished _ActH read whole; dst: _ActH written at column ``col`` (None: the model output, no amax)"""
-            s = prep[name]
-            assert src.ld == s["K"] and src.ready, name
-            out = torch.empty(M, s["Co"], device=dev, dtype=torch.float32) if dst is None else None
-            self.k_conv_f16x2(src.planes, s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, s["Co"], act, src.word, s["ew"],
+        dev, M, S, prep = x.device, x.shape[0], self.schedule, self._prep(x.device)
+        words = torch.zeros(len(S.bufs), dtype=torch.int32, device=dev)      # one word per buffer, zeroed once
+        acts = {0: _ActH(M, 64, dev, False, words, 0, rows=False)}    # (the pack kernel writes the input's zero pad and the exponent itself)
+        self.k_pack_f16x2(x, acts[0].planes, M, self.in_dim, acts[0].word)
+        acts[0].ready = True
+        out = None
+        for i, L in enumerate(S.layers):
+            s, src, res = prep[L.name], acts[L.src], acts.get(L.res)
+            assert src.ld == s["K"] and src.ready, L.name
+            if L.dst is None:                                         # the model output: no amax
+                out = torch.empty(M, s["Co"], device=dev, dtype=torch.float32)
+            elif L.dst not in acts:
+                acts[L.dst] = _ActH(M, S.bufs[L.dst].ld, dev, S.bufs[L.dst].zero, words, L.dst)
+            dst = acts.get(L.dst)
+            self.k_conv_f16x2(src.planes, s["wz"], s["sc"], s["sh"], M, s["N"], s["K"], mesh, s["Co"], L.act, src.word, s["ew"],
                               res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
-                              out=out if dst is None else dst.at(col), ldo=s["Co"] if dst is None else dst.ld,
+                              out=out if dst is None else dst.at(L.col), ldo=s["Co"] if dst is None else dst.ld,
                               amax=None if dst is None else dst.word)
-            return out
-
-        def res_block(i, xa, width):
-            """res_nets[i]: x + BN(conv(L(BN(conv x))))"""
-            ld = max(width, 64)
-            h, ya = buf(ld, width), buf(ld, width)
-            layer(f"res_nets.{i}.1", xa, h)
-            layer(f"res_nets.{i}.2", h.finish(), ya, act=False, res=xa)
-            return ya.finish()
-
-        ef = self.encoder_features
-        p0 = buf(64, 64, rows=False)                                  # (the pack kernel writes the zero pad and the exponent itself)
-        self.k_pack_f16x2(x, p0.planes, M, self.in_dim, p0.word)
-        p0.ready = True
-        p1 = buf(64, 64)
-        layer("lift.0", p0, p1)
-        xa = buf(64, ef[0])
-        layer("lift.1", p1.finish(), xa, act=False)
-        xa.finish()
-
-        def kept(name, b, width):
-            if keep is not None:
-                keep[name] = b.rows[:, :width].contiguous()
-
-        kept("lift", xa, ef[0])
-        skip = []
-        for i in range(N_LAYERS):
-            skip.append(res_block(i, xa, ef[i]))
-            kept(f"skip{i}", skip[i], ef[i])
-            nxt = buf(max(ef[i + 1], 64), ef[i + 1])
-            layer(f"encoder.{i}", xa, nxt)
-            xa = nxt.finish()
-        n_res = len(self.res_nets)
-        for j in range(6):                                            # the neck, in REVERSE index order (cno.py:490-491)
-            xa = res_block(n_res - 1 - j, xa, ef[3])
-        kept("neck", xa, ef[3])
-        # decoder: cat(x, ED_expansion(skip)) is two producers of one row buffer and one word; finish runs once, after both
-        a = buf(128, 128)
-        layer("ED_expansion.3", xa, a)
-        b = buf(128, 128)
-        layer("decoder_inv.0", a.finish(), b)
-        c1 = buf(128, 128)
-        layer("decoder.0", b.finish(), c1, col=0)                     # 64 channels -> columns 0..63
-        layer("ED_expansion.2", skip[2], c1, col=64)                  # 64 channels -> columns 64..127
-        b = buf(128, 128)
-        layer("decoder_inv.1", c1.finish(), b)
-        c2 = buf(64, 64)
-        layer("decoder.1", b.finish(), c2, col=0)                     # 32 -> columns 0..31
-        layer("ED_expansion.1", skip[1], c2, col=32)                  # 32 -> columns 32..63
-        b = buf(64, 64)
-        layer("decoder_inv.2", c2.finish(), b)
-        c3 = buf(64, 32)
-        layer("decoder.2", b.finish(), c3, col=0)                     # 16 -> columns 0..15
-        layer("ED_expansion.0", skip[0], c3, col=16)                  # 16 -> columns 16..31; 32..63 stay zero
-        d = buf(64, 64)
-        layer("project.0", c3.finish(), d)
-        assert used[0] == N_WORDS
-        return layer("project.1", d.finish(), act=False)
+            if dst is not None and S.last_write[L.dst] == i:
+                dst.finish()
+                if keep is not None and L.dst in S.kept:
+                    keep[S.kept[L.dst]] = dst.rows[:, :S.bufs[L.dst].written].contiguous()
+            for b in (L.src, L.res):
+                if S.last_read.get(b) == i:
+                    acts.pop(b, None)
+        return out
 
     def check_input(self, shape):
         """The shapes ``forward`` takes: [B, T, H, W, in_dim] with in_dim < T."""
@@ -735,36 +623,26 @@ class CNO3d(EvalOnly, Model):
             raise ValueError(f"CNO3d: input {tuple(shape)} has C >= T.  The reference permutes to channels-first only when C < T "
                              "(cno.py:467) and otherwise convolves with T as the channel axis; this port requires C < T")
 
-    def forward(self, x, keep=None):
-        if self.hip_training and self.training:                       # the opt-in training step: batch statistics, through HipFunction
-            if keep is not None:
-                raise ValueError("keep= belongs to the evaluation forward")
-            self._require_hip(x)
-            self.check_input(tuple(x.shape))
-            if not torch.is_grad_enabled():
-                return self._forward_hip(x, None)
-            if x.requires_grad:
-                raise NotImplementedError("CNO3d training computes no input gradient (no trainer asks for one)")
-            return HipFunction.apply(x, self, *self.parameters())
-        self._require_eval(x)
-        self._require_hip(x)
-        self.check_input(tuple(x.shape))
-        with torch.no_grad():
-            x = x.contiguous().float()
-            B, T, H, W, C = x.shape
-            out = self._forward_rows(x.view(B * T * H * W, C), B, (T, H, W), keep=keep)
-            if keep is not None:
-                for k in keep:
-                    keep[k] = keep[k].view(B, T, H, W, -1)
-            out = out.view(B, T, H, W, self.out_dim)
-            if self.out_dim_mult > 1:                                 # cno.py:519-520 on channels-last memory: a view, not a time-major split
-                out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
-            return out
+    def _shaped(self, out, shape):
+        """rows [M][out_dim] -> [B, T * out_dim_mult, H, W, out_dim / out_dim_mult]"""
+        B, T, H, W, _ = shape
+        out = out.view(B, T, H, W, self.out_dim)
+        if self.out_dim_mult > 1:                                     # cno.py:519-520 on channels-last memory: a view, not a time-major split
+            out = out.reshape(B, -1, H, W, self.out_dim // self.out_dim_mult)
+        return out
 
-    def train_loss(self, input, target):
-        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
+    def forward(self, x, keep=None):
+        if keep is None:
+            return super().forward(x)
         if self.hip_training and self.training:
-            return Model.train_loss(self, input, target)
-        if torch.is_grad_enabled():
-            raise NotImplementedError(type(self).training_unavailable)
-        return Model.train_loss(self, input, target)
+            raise ValueError("keep= belongs to the evaluation forward")
+        return super().forward(x, keep=keep)
+
+    def _forward_eval(self, x, keep=None):
+        B, T, H, W, C = x.shape
+        run = self._eval_f16x2 if self.arith == "f16x2" else self._eval_bf16x3
+        out = run(x.view(B * T * H * W, C), (T, H, W), keep=keep)
+        if keep is not None:
+            for k in keep:
+                keep[k] = keep[k].view(B, T, H, W, -1)
+        return self._shaped(out, x.shape)

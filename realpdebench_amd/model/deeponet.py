@@ -2,7 +2,7 @@
 ``load_model`` like model/load_model.py:132-143) for the reference's ``configs/*/deeponet.yaml`` (p = 64 / 128 / 256).
 
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
-every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph,
+every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``) instead of returning tensors without a graph,
 ``trainer.make_trainer`` refuses the model at construction, dropout is the identity and BatchNorm3d uses its running statistics in
 every mode.  ``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
 ``train_loss`` then run through ``_common.HipFunction`` with batch-statistics BatchNorm and active dropout (``_forward_hip`` /
@@ -34,7 +34,7 @@ import torch.nn as nn
 from .. import _lib
 from ..ops import Sub, _p, _stream, amax_exp, conv3_f16x2_weights, conv3x, conv3x_f16x2, conv3x_wprep, reduce_partials, split2h, split3
 from ..ops import add as ops_add
-from ._common import EvalOnly, HipFunction, padded_weight, wgrad
+from ._common import EvalByDefault, padded_weight, wgrad
 from .cno import flipped_weight, weight_grad_view
 from .model import Model
 
@@ -167,11 +167,12 @@ def drop_seed(base, step, layer, chunk):
     return (int(base) + (int(step) << 24) + (layer << 22) + chunk) % (1 << 62)
 
 
-class DeepONet(EvalOnly, Model):
+class DeepONet(EvalByDefault, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
-    training_unavailable = EvalOnly.TRAIN_MSG.format("DeepONet", "DeepONet")
-    hip_training = False                            # enable_training() sets it on the instance
-    dp_unavailable = None                           # (enabled instances: why trainer.make_trainer refuses more than one rank)
+    training_unavailable = EvalByDefault.TRAIN_MSG.format("DeepONet", "DeepONet")
+    BATCH_STATISTICS = True                         # an enabled instance: see enable_training
+    DP_MSG = "DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
+    ARITHS = ARITHS
     _point_rows = _POINT_ROWS                       # (tests force several chunks by lowering it on an instance)
     f16x2_convs = True                              # set_arith("f16x2") also moves branch stages 2-4 (tools/deeponet_probe.py measures both)
 
@@ -206,10 +207,7 @@ class DeepONet(EvalOnly, Model):
         planes of the tensor scaled by a power of two -- one per point inside the output net --, three products, dropped term <= 2^-22;
         csrc/rpb_deeponet_h.hip).  Only the evaluation forward changes: the opt-in training step
         (``enable_training()``) stays on its kernels under either setting."""
-        if arith not in ARITHS:
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
+        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ the opt-in training step
     def enable_training(self, seed=None):
@@ -222,31 +220,9 @@ class DeepONet(EvalOnly, Model):
         ``no_grad`` forward in ``train()`` mode uses one up like a step with a graph, a forward that raises uses none.  It is not part of
         ``state_dict`` (the checkpoint stays the reference's), so a run resumed from a checkpoint under the same seed starts again at
         step 0 and redraws the masks of the first steps; a caller that minds sets ``model._drop_step`` to the resumed iteration."""
-        self.hip_training = True
-        self.training_unavailable = None
-        self.batch_independent = False
-        self.dp_unavailable = ("DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, "
-                               "run it on one rank")
         self.dropout_seed = int(torch.initial_seed() if seed is None else seed) % (1 << 62)
         self._drop_step = 0
-        return self
-
-    def _require_eval(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(type(self).training_unavailable)
-
-    # ------------------------------------------------------------------ checkpoints
-    def load_checkpoint(self, checkpoint_path, device="cpu"):
-        """The base class's loader (``model_state_dict`` + bookkeeping, realpdebench/model/model.py); a bare weights file gives the
-        bookkeeping entries of an untrained run (iteration 0, no losses), as MWT3d does."""
-        ck = torch.load(checkpoint_path, map_location="cpu")
-        if "model_state_dict" in ck:
-            meta = super().load_checkpoint(checkpoint_path, "cpu")
-        else:
-            self.load_state_dict(ck)
-            meta = self._bookkeeping({})
-        self.to(device)
-        return meta
+        return super().enable_training()
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _prep(self, device):
@@ -431,43 +407,22 @@ class DeepONet(EvalOnly, Model):
         z = self.k_gemm(h.view(B, 4096), *prep["fc0"], 512, relu=True)
         return self.k_gemm(z, *prep["fc3"], self.p, relu=False)
 
-    def check_input(self, x):
-        if x.dim() != 5 or x.shape[1] != self.shape_in[0] or x.shape[-1] != self.input_channels:
-            raise ValueError(f"DeepONet was built for inputs [B, {self.shape_in[0]}, H, W, {self.input_channels}], got {tuple(x.shape)}")
-        if min(pooled_extents(*x.shape[1:4])[3]) < 1:
-            raise ValueError(f"DeepONet: input {tuple(x.shape)} leaves an empty extent after three MaxPool3d(2)")
+    def check_input(self, shape):
+        if len(shape) != 5 or shape[1] != self.shape_in[0] or shape[-1] != self.input_channels:
+            raise ValueError(f"DeepONet was built for inputs [B, {self.shape_in[0]}, H, W, {self.input_channels}], got {tuple(shape)}")
+        if min(pooled_extents(*shape[1:4])[3]) < 1:
+            raise ValueError(f"DeepONet: input {tuple(shape)} leaves an empty extent after three MaxPool3d(2)")
 
-    def forward(self, x):
-        if self.hip_training and self.training:                       # the opt-in training step: batch statistics, through HipFunction
-            self._require_hip(x)
-            self.check_input(x)
-            if not torch.is_grad_enabled():
-                return self._forward_hip(x, None)
-            if x.requires_grad:
-                raise NotImplementedError("DeepONet training computes no input gradient (no trainer asks for one)")
-            return HipFunction.apply(x, self, *self.parameters())
-        self._require_eval(x)
-        self._require_hip(x)
-        self.check_input(x)
-        with torch.no_grad():
-            x = x.contiguous().float()
-            B, _, H, W, _ = x.shape                                   # T_out from shape_out, H and W from the input (deeponet.py:122-126)
-            T_out = self.shape_out[0]
-            prep = self._prep(x.device)
-            prep_h = self._prep_f16x2(x.device) if self.arith == "f16x2" else None
-            b = self.branch_forward(x, prep, prep_h=prep_h if self.f16x2_convs else None)
-            t = self._trunk(T_out, H, W, x.device)
-            if prep_h is not None:
-                return self.k_point_mlp_f16x2(t, b, prep_h["point"]).view(B, T_out, H, W, self.output_channels)
-            return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
-
-    def train_loss(self, input, target):
-        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
-        if self.hip_training and self.training:
-            return Model.train_loss(self, input, target)
-        if torch.is_grad_enabled():
-            raise NotImplementedError(type(self).training_unavailable)
-        return Model.train_loss(self, input, target)
+    def _forward_eval(self, x):
+        B, _, H, W, _ = x.shape                                       # T_out from shape_out, H and W from the input (deeponet.py:122-126)
+        T_out = self.shape_out[0]
+        prep = self._prep(x.device)
+        prep_h = self._prep_f16x2(x.device) if self.arith == "f16x2" else None
+        b = self.branch_forward(x, prep, prep_h=prep_h if self.f16x2_convs else None)
+        t = self._trunk(T_out, H, W, x.device)
+        if prep_h is not None:
+            return self.k_point_mlp_f16x2(t, b, prep_h["point"]).view(B, T_out, H, W, self.output_channels)
+        return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
 
     # ------------------------------------------------------------------ the training step (DESIGN.md section 16.1)
     def _prep_train(self, device):

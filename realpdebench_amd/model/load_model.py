@@ -10,6 +10,8 @@ def load_model(train_dataset, device="cpu", **kwargs):
     input_shape = tuple(input.shape)
     output_shape = tuple(target.shape)
     logging.info(f"Loading model {model_name} with input shape {input_shape} and output shape {output_shape}")
+    # opt-in of mwt, deeponet and cno to their HIP training step (``EvalByDefault.enable_training``); it never reaches a constructor
+    hip_training = model_name in ("mwt", "deeponet", "cno") and kwargs.pop("hip_training", False)
     if model_name == "fno":
         from .fno import FNO3d
         model = FNO3d(
@@ -52,16 +54,11 @@ def load_model(train_dataset, device="cpu", **kwargs):
         kwargs["shape_in"] = input_shape                      # load_model.py:93-107
         kwargs["shape_out"] = output_shape
         kwargs.pop("config", None)
-        hip_training = kwargs.pop("hip_training", False)
         model = MWT3d(**kwargs).to(device)
-        if hip_training:                                      # opt-in: the HIP training step
-            model.enable_training()
     elif model_name == "deeponet":
         from .deeponet import DeepONet
         model = DeepONet(shape_in=input_shape, shape_out=output_shape, input_channels=input_shape[-1],       # load_model.py:132-143
                          output_channels=output_shape[-1], p=kwargs["p"], dropout_rate=kwargs["dropout_rate"], device=device).to(device)
-        if kwargs.get("hip_training"):                        # opt-in: the HIP training step with batch-statistics BatchNorm and dropout
-            model.enable_training()
     elif model_name == "cno":
         from .cno import CNO3d
         if output_shape[0] > input_shape[0] and output_shape[0] % input_shape[0] == 0:                       # load_model.py:60-75
@@ -72,9 +69,9 @@ def load_model(train_dataset, device="cpu", **kwargs):
             raise ValueError(f"Output shape {output_shape[1]} is not a multiple of input shape {input_shape[1]}")
         model = CNO3d(in_dim=input_shape[-1], out_dim=output_shape[-1], out_dim_mult=out_dim_mult, in_size=input_shape[2],
                       N_layers=kwargs["N_layers"]).to(device)
-        if kwargs.get("hip_training"):                        # opt-in: the HIP training step with batch-statistics BatchNorm
-            model.enable_training()
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
                          "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno)")
+    if hip_training:
+        model.enable_training()
     return model

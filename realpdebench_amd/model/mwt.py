@@ -3,7 +3,7 @@ realpdebench/model/MWT_libs/models.py:498-790, built by ``load_model`` like mode
 the reference's ``configs/*/mwt.yaml``: ``k: 3, alpha: 5, c: 4, nCZ: 4, L: 0, base: legendre``.
 
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default every attempt to
-backpropagate raises ``NotImplementedError`` (``_common.EvalOnly``) instead of returning tensors without a graph.
+backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``) instead of returning tensors without a graph.
 ``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
 ``train_loss`` then run through ``_common.HipFunction``; the adjoints of the wavelet maps and of the DFT stages are the forward's own
 launches on transposed tables, the rest is ``csrc/rpb_mwt_train.hip``.
@@ -39,7 +39,7 @@ from numpy.polynomial import legendre as npleg
 from .. import _lib, ops
 from ..dft import _fwd_complex, _fwd_real, _inv_complex, _inv_real
 from ..ops import _p, _stream
-from ._common import EvalOnly, HipFunction
+from ._common import EvalByDefault
 from .model import Model
 
 I16, I32 = torch.int16, torch.int32
@@ -203,11 +203,13 @@ class _CZ(nn.Module):
             self.register_buffer(name, t)
 
 
-class MWT3d(EvalOnly, Model):
-    batch_independent = True      # no batch statistics are ever computed (BN is never called)
-    training_unavailable = EvalOnly.TRAIN_MSG.format("MWT", "MWT3d")
-    hip_training = False          # enable_training() sets it on the instance
-    dp_unavailable = None         # (enabled instances: why trainer.make_trainer refuses more than one rank)
+class MWT3d(EvalByDefault, Model):
+    batch_independent = True      # no batch statistics are ever computed (BN is never called): an enabled instance keeps declaring it
+    training_unavailable = EvalByDefault.TRAIN_MSG.format("MWT", "MWT3d")
+    # An enabled instance (``enable_training()``) runs the ``"f32"`` kernels whatever ``set_arith`` says;
+    # ``micro_batch`` works, more than one rank is refused.
+    DP_MSG = "MWT3d training has only been verified on one rank: data-parallel training is not built, run it on one rank"
+    ARITHS = ARITHS
 
     def __init__(self, k=3, alpha=2, c=1, nCZ=3, L=0, base="legendre", initializer=None, shape_in=None, shape_out=None, **kwargs):
         super().__init__()
@@ -255,33 +257,7 @@ class MWT3d(EvalOnly, Model):
         planes of the tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_mwt3x.hip).  Everything else in
         the forward is unchanged; training stays refused under every mode, and the opt-in training step (``enable_training()``) runs
         the ``"f32"`` kernels whatever is selected here."""
-        if arith not in ARITHS:
-            raise ValueError(f"arith must be 'f32', 'bf16x3' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
-
-    # ------------------------------------------------------------------ the opt-in training step
-    def enable_training(self):
-        """Opt this instance into the HIP training step (``hip_training: true`` in a config).  In ``train()``
-        mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction``, always on the ``"f32"`` kernels whatever
-        ``set_arith`` says.  No batch statistics exist (``BN.*`` is never called), so the instance keeps ``batch_independent`` and
-        ``micro_batch`` works; more than one rank is refused (the step has only been verified on one)."""
-        self.hip_training = True
-        self.training_unavailable = None
-        self.dp_unavailable = "MWT3d training has only been verified on one rank: data-parallel training is not built, run it on one rank"
-        return self
-
-    def _require_eval(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError(type(self).training_unavailable)
-
-    def train_loss(self, input, target):
-        """Elementwise ``mse_loss(pred, target)``: with a graph on an enabled instance in ``train()`` mode, otherwise as a value."""
-        if self.hip_training and self.training:
-            return Model.train_loss(self, input, target)
-        if torch.is_grad_enabled():
-            raise NotImplementedError(type(self).training_unavailable)
-        return Model.train_loss(self, input, target)
+        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ checkpoints (models.py:791-844)
     def state_dict(self, *args, **kwargs):
@@ -709,24 +685,13 @@ class MWT3d(EvalOnly, Model):
         grads[self.Lk.weight], grads[self.Lk.bias] = self.k_lift_wgrad(g, x)
         return grads
 
-    def forward(self, x):
-        if self.hip_training and self.training:      # the opt-in training step, through HipFunction; always the "f32" kernels
-            if tuple(x.shape[1:]) != self.shape_in:
-                raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(x.shape)}")
-            if torch.is_grad_enabled() and x.requires_grad:
-                raise NotImplementedError("MWT3d training computes no input gradient (no trainer asks for one)")
-            self._require_hip(x)
-            if not torch.is_grad_enabled():
-                return self._forward_hip(x, None)
-            return HipFunction.apply(x, self, *self.parameters())
-        self._require_eval(x)
-        self._require_hip(x)
-        if tuple(x.shape[1:]) != self.shape_in:
-            raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(x.shape)}")
-        with torch.no_grad():
-            x = x.contiguous().float()
-            p = self._prep(x.device)
-            h = self.k_lift(x, p["Lkw"], p["Lkb"])
-            for i, cz in enumerate(p["cz"]):
-                h = self._cz_forward(h, cz, relu=i < self.nCZ - 1)
-            return self.k_head(h, p["w0t"], p["b0"], p["w1"], p["b1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])
+    def check_input(self, shape):
+        if tuple(shape[1:]) != self.shape_in:
+            raise ValueError(f"MWT3d was built for inputs [B, {', '.join(map(str, self.shape_in))}], got {tuple(shape)}")
+
+    def _forward_eval(self, x):
+        p = self._prep(x.device)
+        h = self.k_lift(x, p["Lkw"], p["Lkb"])
+        for i, cz in enumerate(p["cz"]):
+            h = self._cz_forward(h, cz, relu=i < self.nCZ - 1)
+        return self.k_head(h, p["w0t"], p["b0"], p["w1"], p["b1"], self.shape_out[-1], self.shape_out[0] // self.shape_in[0])

@@ -63,6 +63,78 @@ def test_restatement_rollout_matches_reference(case):
     assert e < host_tol(case + "_roll")
 
 
+def _sd_names(m):
+    """schedule layer name -> (convolution, BatchNorm or None) as the state_dict names them"""
+    names = {mod: n for n, mod in m.named_modules()}
+    return {k: (names[conv], names[bn] if bn is not False else None) for k, (conv, bn) in m._convs().items()}
+
+
+@pytest.mark.parametrize("case", list(CC.CASES))
+def test_model_schedule_is_the_restatement(case):
+    """The model's own ``Schedule``, interpreted here in fp64 on zeroed [M][ld] buffers with ``fold`` and ``conv_layer`` of the
+    restatement, against ``cno_restatement.forward``: the same operations in the same order, so the expected difference is zero."""
+    shape_in, shape_out, _ = CC.CASES[case]
+    m, sd = new_model(case), sd_of(case)
+    S, names = m.schedule, _sd_names(m)
+    x = CC.case_inputs(case)[0].double()
+    B, T, H, W, C = x.shape
+    Mrows = B * T * H * W
+    ref_keep = {}
+    with torch.no_grad():
+        ref = R.forward(sd, x, shape_out, keep=ref_keep)
+        bufs = [torch.zeros(Mrows, b.ld, dtype=torch.float64) for b in S.bufs]
+        bufs[0][:, :C] = x.reshape(Mrows, C)
+        out = None
+        for L in S.layers:
+            conv, bn = names[L.name]
+            Co = sd[conv + ".weight"].shape[0]
+            wp, sc, sh, _ = R.fold(sd, conv, bn, max(Co, 64))
+            assert bufs[L.src].shape[1] == wp.shape[1], L.name
+            v = R.conv_layer(bufs[L.src], wp, sc, sh, B, (T, H, W), L.act, None if L.res is None else bufs[L.res])[:, :Co]
+            if L.dst is None:
+                out = v
+            else:
+                bufs[L.dst][:, L.col:L.col + Co] = v
+    out = out.reshape(B, T, H, W, -1).reshape(B, *shape_out)
+    e = rel(out, ref)
+    print(f"case {case}: schedule vs restatement, out Rel-L2 {e:.2e}")
+    assert e <= 1e-12
+    assert sorted(S.keep) == sorted(CC.INTERMEDIATES)
+    for k, b in S.keep.items():
+        ek = rel(bufs[b][:, :S.bufs[b].written].reshape(B, T, H, W, -1), ref_keep[k])
+        print(f"  {k}: {ek:.2e}")
+        assert ek <= 1e-12, k
+
+
+@pytest.mark.parametrize("case", list(CC.CASES))
+def test_schedule_invariants(case):
+    m = new_model(case)
+    S, convs = m.schedule, m._convs()
+    assert len(S.layers) == 35 and len({L.name for L in S.layers}) == 35 and {L.name for L in S.layers} == set(convs)
+    assert len(S.bufs) == 32
+    producers = {}
+    for i, L in enumerate(S.layers):
+        if L.dst is not None:
+            producers.setdefault(L.dst, []).append(i)
+    assert sorted(producers) == list(range(1, 32)), "buffer 0 is the packed input; every other buffer is written"
+    assert [L.dst for L in S.layers].count(None) == 1 and S.layers[-1].dst is None
+    for i, L in enumerate(S.layers):                                 # every buffer a layer reads is complete by then
+        for b in (L.src, L.res):
+            if b is not None and b != 0:
+                assert max(producers[b]) < i, (L.name, b)
+        assert S.bufs[L.src].ld == max(convs[L.name][0].in_channels, 64), L.name
+    for b, ps in producers.items():
+        spans = sorted((S.layers[i].col, S.layers[i].col + convs[S.layers[i].name][0].out_channels) for i in ps)
+        assert len(ps) in (1, 2), b
+        assert spans[0][0] == 0 and spans[-1][1] == S.bufs[b].written <= S.bufs[b].ld, (b, spans)
+        if len(ps) == 2:                                             # a concat: two producers, disjoint and adjacent column ranges
+            assert spans[0][1] == spans[1][0], (b, spans)
+        assert S.last_write[b] == max(ps)
+    assert sum(len(ps) == 2 for ps in producers.values()) == 3
+    for b in S.residuals | set(S.keep.values()):                     # fp32 rows are one layer's output
+        assert len(producers[b]) == 1 and S.layers[producers[b][0]].col == 0, b
+
+
 def test_folded_affine_and_padded_weights_are_the_restatements():
     """``fold_affine`` (float64, rounded once) and ``padded_weight`` of the model against ``fold`` of the restatement, for a layer with
     BatchNorm and pad channels (16 -> 16) and one without BatchNorm (64 -> 3)."""
