@@ -888,6 +888,31 @@ int rpb_gemm3h_wprep(const float* W, void* Wz, float* sc, int N, int K, void* st
 int rpb_gemm3h(const float* A, const void* Wz, const float* sc, const float* bias, const float* residual, float* out, long M, int N, int K,
                int lda, int ldo, int act, void* stream);
 
+/*
+ * DPOT on the opt-in "f16x2" eval arithmetic (DPOT.set_arith("f16x2"); csrc/rpb_gemm3hk.hip, csrc/rpb_dpot_h.hip; additions do not change
+ * RPB_ABI_VERSION).
+ *     rpb_gemm3hk: rpb_gemm3h's product for K above what fits resident: K % 64 == 0, K > 512, no upper limit (K is streamed in 64-column
+ *     chunks); N % 256 == 0; any M >= 1; lda >= K, ldo >= N, both % 4 == 0, A / bias / residual / out 16-byte aligned; epilogue = bias[N], act in {0 none, 1 GELU (rpb_gemm3x's
+ *     gelu), 3 ReLU}, residual[M][ldo].  Wz, sc: rpb_gemm3h_wprep's planes and weight scale, as they are.  Every row of A is scaled by a
+ *     power of two of its own from the exact maximum of its K values (into [2^14, 2^15), exponent capped at 62, an all-zero row
+ *     unscaled): a pre-pass of the same call (rpb_gemm3hk_rowexp, one extra read of A) writes the exponents to rowe, M ints of device
+ *     scratch; no host synchronisation.  rpb_gemm3hk_supported says without launching what the call takes; anything else is RPB_ERR_ARG.
+ *     Fixed summation order, no atomics: two calls are bit-equal.  Nothing is written outside out[m][0..N), m < M, and rowe[0..M).
+ *     rpb_afno_mlp_f16x2: rpb_afno_mlp's forward (mode 0, no mid) out = gelu(X Wa + ba) Wb + bb per (token tile, block) on rows
+ *     [ntok][2][nb * bs], from two-plane operands.  Waz / Wbz, sca / scb: rpb_afno_wprep_f16x2 of the complex weights w [2][nb][bs][bs]
+ *     -- the real composites of all blocks as fp16 (hi, lo) planes in B-operand order, 2 * nb * (2 bs)^2 fp16, one exponent per weight
+ *     tensor, sc[0] = 2^-ew (sc: TWO floats of device memory).  X and the hidden layer (after GELU) take one exponent per (token, block)
+ *     from their exact maxima inside the launch; the hidden layer never leaves the CU.  bs % 16 == 0, bs <= 128
+ *     (rpb_afno_mlp_f16x2_supported).  No atomics, two calls are bit-equal.  Non-finite inputs are outside the contract of all of these. */
+int rpb_gemm3hk_supported(long M, int N, int K, int lda, int ldo);
+int rpb_gemm3hk_rowexp(const float* A, int* rowe, long M, int K, int lda, void* stream);
+int rpb_gemm3hk(const float* A, const void* Wz, const float* sc, const float* bias, const float* residual, float* out, int* rowe, long M,
+                int N, int K, int lda, int ldo, int act, void* stream);
+int rpb_afno_mlp_f16x2_supported(int nb, int bs);
+int rpb_afno_wprep_f16x2(const float* w, void* Wz, float* sc, int nb, int bs, void* stream);
+int rpb_afno_mlp_f16x2(const float* X, const void* Waz, const float* sca, const float* ba, const void* Wbz, const float* scb,
+                       const float* bb, float* out, long ntok, int nb, int bs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

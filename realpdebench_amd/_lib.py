@@ -239,6 +239,12 @@ SIGNATURES = {
     "rpb_gemm3h_supported": (_I, "liiii"),
     "rpb_gemm3h_wprep": (_I, "ppp" + "ii" + "p"),
     "rpb_gemm3h": (_I, "pppppp" + "liiii" + "i" + "p"),
+    "rpb_gemm3hk_supported": (_I, "liiii"),
+    "rpb_gemm3hk_rowexp": (_I, "pp" + "lii" + "p"),
+    "rpb_gemm3hk": (_I, "ppppppp" + "liiii" + "i" + "p"),
+    "rpb_afno_mlp_f16x2_supported": (_I, "ii"),
+    "rpb_afno_wprep_f16x2": (_I, "ppp" + "ii" + "p"),
+    "rpb_afno_mlp_f16x2": (_I, "pppppppp" + "lii" + "p"),
 }
 
 _lib = None

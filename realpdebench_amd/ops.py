@@ -551,6 +551,30 @@ def gemm_nt_f16x2(A, wz, out, M, N, K, bias=None, residual=None, act=0, lda=None
               _stream(), label=f"gemm3h[N{N},K{K}]", nbytes=4 * (M * lda + M * N) + 4 * N * K, flops=2 * M * N * K)
 
 
+def gemm3hk_supported(M, N, K, lda=None, ldo=None):
+    """True when ``gemm_nt_f16x2k`` takes the product (csrc/rpb_gemm3hk.hip: K % 64 == 0 above 512 without an upper limit, N % 256 == 0, leading
+    dimensions % 4)."""
+    return bool(_lib.load().rpb_gemm3hk_supported(M, N, K, K if lda is None else lda, N if ldo is None else ldo))
+
+
+def gemm3hk_rowexp(A, rowe, M, K, lda=None):
+    """rowe[M] (int32) = the row exponents ``gemm_nt_f16x2k`` forms itself: the pre-pass alone, for measuring it."""
+    _lib.call("rpb_gemm3hk_rowexp", _p(A), _p(rowe, torch.int32), M, K, K if lda is None else lda, _stream(), label=f"gemm3hk_rowexp[K{K}]",
+              nbytes=4 * M * K)
+
+
+def gemm_nt_f16x2k(A, wz, out, M, N, K, bias=None, residual=None, act=0, lda=None, ldo=None):
+    """``gemm_nt_f16x2`` for K above what its kernel holds resident (csrc/rpb_gemm3hk.hip): the same planes ``wz = gemm3h_wprep(W)``, K
+    streamed in 64-column chunks, one power-of-two scale per row of A from a pre-pass of the same call (M ints of scratch are allocated
+    here).  act: 0 none, 1 GELU, 3 ReLU.  A shape ``gemm3hk_supported`` refuses is an error here: the caller chooses the path."""
+    planes, sc = wz
+    lda = K if lda is None else lda
+    ldo = N if ldo is None else ldo
+    rowe = torch.empty(max(int(M), 1), dtype=torch.int32, device=(out.t if isinstance(out, Sub) else out).device)
+    _lib.call("rpb_gemm3hk", _p(A), _p(planes, torch.int16), _p(sc), _p(bias), _p(residual), _p(out), _p(rowe, torch.int32), M, N, K, lda,
+              ldo, int(act), _stream(), label=f"gemm3hk[N{N},K{K}]", nbytes=4 * (2 * M * lda + M * N) + 4 * N * K, flops=2 * M * N * K)
+
+
 def gemm_tn_split_bf16(M, N, K, ldg=None, lda=None):
     """True when the plain weight-gradient GEMM runs on the bf16 matrix pipe from split operands (csrc/rpb_gemm3x_tn.hip)."""
     return bool(_lib.query("rpb_gemm3x_tn_supported", M, N, K, N if ldg is None else ldg, K if lda is None else lda))
@@ -1109,6 +1133,27 @@ def gn_tokens_bwd(x, x2, gamma, stat, gy, gadd, gx, pg, pb, B, P, C, G):
 
 def afno_wprep(w, Wc, nb, bs, transpose):
     _lib.call("rpb_afno_wprep", _p(w), _p(Wc), nb, bs, bs, int(transpose), _stream(), label="afno_wprep", nbytes=24 * nb * bs * bs)
+
+
+def afno_f16x2_supported(nb, bs):
+    """True when ``afno_mlp_f16x2`` takes the block shape (csrc/rpb_dpot_h.hip: bs % 16 == 0, bs <= 128)."""
+    return bool(_lib.load().rpb_afno_mlp_f16x2_supported(nb, bs))
+
+
+def afno_wprep_f16x2(w, nb, bs):
+    """The operand of ``afno_mlp_f16x2`` for complex AFNO weights w [2][nb][bs][bs]: ``(planes, sc)`` -- the real composites of all blocks
+    as fp16 (hi, lo) planes in MFMA B-operand order (int16 storage) and two floats, sc[0] = 2^-ew; the exponent stays on the device."""
+    wz = torch.empty(2 * nb * 4 * bs * bs, dtype=torch.int16, device=w.device)
+    sc = torch.empty(2, dtype=F32, device=w.device)
+    _lib.call("rpb_afno_wprep_f16x2", _p(w), _p(wz, torch.int16), _p(sc), nb, bs, _stream(), label="afno_wprep_f16x2", nbytes=24 * nb * bs * bs)
+    return wz, sc
+
+
+def afno_mlp_f16x2(X, waz, ba, wbz, bb, out, ntok, nb, bs):
+    """``afno_mlp`` mode 0 without ``mid`` on the opt-in "f16x2" eval arithmetic (csrc/rpb_dpot_h.hip); ``waz`` / ``wbz`` from
+    ``afno_wprep_f16x2``.  A block shape ``afno_f16x2_supported`` refuses is an error here."""
+    _lib.call("rpb_afno_mlp_f16x2", _p(X), _p(waz[0], torch.int16), _p(waz[1]), _p(ba), _p(wbz[0], torch.int16), _p(wbz[1]), _p(bb), _p(out),
+              ntok, nb, bs, _stream(), label="afno_mlp_f16x2", nbytes=4 * ntok * 2 * nb * bs * 2, flops=2 * 2 * ntok * nb * (2 * bs) ** 2)
 
 
 def afno_mlp(X, Wa, ba, Wb, bb, aux, mid, out, ntok, nb, bs, mode):
