@@ -52,15 +52,13 @@ def main(argv=None):
         meta = model.load_checkpoint(args.checkpoint_path, device)                     # eval.py:284
         logging.info(f"Checkpoint {args.checkpoint_path} loaded (iteration {meta['iteration']}).")
     # optional YAML keys (not in the reference; both default to the parity path): `eval_storage: bf16` stores the activations between
-    # kernels as bf16 (FNO3d at width 64; BASELINE.json configs[4]), `eval_arith: f16x2` runs the eval launches on two fp16 planes
-    # (FNO3d at width 64: cell_mix + head; Transolver, Unet3d, MWT3d and CNO3d: the 3x3x3 convolutions; MWT3d also takes `bf16x3`;
-    # DeepONet: the output net and the convolutions of branch stages 2-4; GalerkinTransformer3d: the Q|K|V and lr1 token GEMMs; DPOT: the
-    # token GEMMs and the AFNO block MLP named by DPOT.F16X2_SITES)
+    # kernels as bf16 (FNO3d at width 64; BASELINE.json configs[4]), `eval_arith:` is `Model.set_arith` (every model has it; the class
+    # docstring of each says what it moves)
     for key, setter in (("eval_storage", "set_storage"), ("eval_arith", "set_arith")):
         val = getattr(args, key, None)
         if val:
             if not hasattr(model, setter):
-                raise SystemExit(f"{key}: {type(model).__name__} has no {setter} ({'FNO3d only' if setter == 'set_storage' else 'FNO3d, Transolver, Unet3d, MWT3d, CNO3d, DeepONet, GalerkinTransformer3d and DPOT only'})")
+                raise SystemExit(f"{key}: {type(model).__name__} has no {setter} (FNO3d only)")
             getattr(model, setter)(str(val))
             logging.info(f"{key} = {val}")
     results, _, _ = evaluate(model, loader, normalizer, int(args.N_autoregressive), args.test_batch_size)

@@ -130,7 +130,7 @@ class EvalByDefault:
     opts ONE instance in -- the class and every other instance stay as they are: in ``train()`` mode ``forward`` / ``train_loss`` then
     run through ``HipFunction``, ``eval()`` mode stays the evaluation forward and still refuses a graph.
 
-    A model provides ``training_unavailable`` (``TRAIN_MSG.format(family, class name)``), ``DP_MSG``, ``BATCH_STATISTICS``, ``ARITHS``,
+    A model provides ``training_unavailable`` (``TRAIN_MSG.format(family, class name)``), ``DP_MSG``, ``BATCH_STATISTICS``,
     ``check_input(shape)``, ``_forward_eval(x, ...)`` (runs under ``torch.no_grad()``) and ``_forward_hip`` / ``_backward_hip``."""
     TRAIN_MSG = ("the {} training step is not built yet: {} on MI355X covers the evaluation forward, train_loss as a value under "
                  "torch.no_grad(), the rollout and checkpoint I/O")
@@ -141,15 +141,6 @@ class EvalByDefault:
     # The class's training step computes BatchNorm statistics over the batch: they couple the samples of a step, so an enabled instance
     # stops declaring ``batch_independent`` (no micro-batching).
     BATCH_STATISTICS = False
-    ARITHS = None                      # the class's tuple of what ``set_arith`` takes, two names or more
-
-    def set_arith(self, arith):
-        """Each class says in its own docstring what the switch moves."""
-        if arith not in self.ARITHS:
-            names = [repr(a) for a in self.ARITHS]
-            raise ValueError(f"arith must be {', '.join(names[:-1])} or {names[-1]}, got {arith!r}")
-        self.arith = arith
-        return self
 
     def enable_training(self):
         """Opt this instance into the HIP training step (``hip_training: true`` in a config)."""

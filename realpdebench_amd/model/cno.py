@@ -49,7 +49,6 @@ from .model import Model
 I16 = torch.int16
 N_LAYERS = 3
 MAX_CH = 64                    # widest first-layer input / last-layer output: one 64-channel tile
-ARITHS = ("f32", "f16x2")      # CNO3d.set_arith
 # Layers whose data gradient runs on the exact-fp32 implicit GEMM (rpb_gemm_nt) instead of the bf16x3 kernel: the ones that add into the
 # gradient of the neck's residual chain.  A BatchNorm shift gradient is a column sum of that gradient, which sees a per-channel bias of
 # the error sqrt(M) times stronger than its unbiased part; the bf16x3 kernel's error as a data gradient has such a bias (column mean 3-4
@@ -254,13 +253,16 @@ def _iptr(t):
 
 
 class CNO3d(EvalByDefault, Model):
-    batch_independent = True                        # BatchNorm runs on its running statistics only
+    """``set_arith`` selects the arithmetic of the evaluation / rollout forward's 35 convolutions: ``"f32"`` (default, the parity path:
+    operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor
+    scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_cno3h.hip).  Only the evaluation
+    forward changes: the opt-in training step (``enable_training()``) stays on its kernels under either setting."""
+    batch_independent = True                       # BatchNorm runs on its running statistics only
     training_unavailable = EvalByDefault.TRAIN_MSG.format("CNO", "CNO3d")
     # An enabled instance computes batch statistics: they couple the samples of a step, so it stops declaring ``batch_independent`` (no
     # micro-batching) and refuses more than one rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for CNO is not built).
     BATCH_STATISTICS = True
     DP_MSG = "CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
-    ARITHS = ARITHS
 
     def __init__(self, in_dim, in_size, N_layers, N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001,
                  filter_size=6, lrelu_upsampling=2, half_width_mult=0.8, radial=False, batch_norm=True, out_dim=1, out_dim_mult=1,
@@ -301,14 +303,6 @@ class CNO3d(EvalByDefault, Model):
         self.decoder_inv = nn.ModuleList([CNOBlock3d(inv[i], inv[i]) for i in range(N_LAYERS + 1)])                  # [3] is never used
         self.res_nets = nn.Sequential(*([ResidualBlock3d(ef[l]) for l in range(N_LAYERS)] + [ResidualBlock3d(ef[N_LAYERS]) for _ in range(6)]))
         self.schedule = Schedule(self.in_dim, ef)
-        self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
-
-    def set_arith(self, arith):
-        """Arithmetic of the evaluation / rollout forward's 35 convolutions: ``"f32"`` (default, the parity path: operands as three bf16
-        planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power of
-        two, three products, dropped term <= 2^-22; csrc/rpb_cno3h.hip).  Only the evaluation forward changes:
-        the opt-in training step (``enable_training()``) stays on its kernels under either setting."""
-        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _convs(self):

@@ -40,7 +40,6 @@ from .model import Model
 
 I16 = torch.int16
 P_SUPPORTED = (64, 128, 256)
-ARITHS = ("f32", "f16x2")      # DeepONet.set_arith
 _COL_FLOATS = 1 << 28          # stage-1 im2col buffer bound (1 GiB): larger batches run the first stage in chunks of samples
 _POINT_ROWS = 1 << 16          # training step: (sample, point) rows per chunk of the output net (its 512-wide rows: 128 MiB per buffer)
 
@@ -168,13 +167,18 @@ def drop_seed(base, step, layer, chunk):
 
 
 class DeepONet(EvalByDefault, Model):
+    """``set_arith`` selects the arithmetic of the evaluation / rollout forward's output net and of the convolutions of branch stages
+    2-4: ``"f32"`` (default, the parity path: operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in:
+    operands as two fp16 planes of the tensor scaled by a power of two -- one per point inside the output net --, three products,
+    dropped term <= 2^-22; csrc/rpb_deeponet_h.hip).  Only the evaluation forward changes: the opt-in training
+    step (``enable_training()``) stays on its kernels under either setting."""
     batch_independent = True                        # BatchNorm runs on its running statistics only
     training_unavailable = EvalByDefault.TRAIN_MSG.format("DeepONet", "DeepONet")
     BATCH_STATISTICS = True                         # an enabled instance: see enable_training
     DP_MSG = "DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
-    ARITHS = ARITHS
     _point_rows = _POINT_ROWS                       # (tests force several chunks by lowering it on an instance)
-    f16x2_convs = True                              # set_arith("f16x2") also moves branch stages 2-4 (tools/deeponet_probe.py measures both)
+    # what set_arith("f16x2") moves: the output net ("point") and branch stages 2-4 ("convs"; tools/deeponet_probe.py measures both)
+    ALL_F16X2_SITES = F16X2_SITES = ("point", "convs")
 
     def __init__(self, shape_in, shape_out, input_channels, output_channels, p, dropout_rate=0.1, device="cuda"):
         super().__init__()
@@ -199,15 +203,6 @@ class DeepONet(EvalByDefault, Model):
                                         nn.Dropout(dropout_rate), nn.Linear(128, self.output_channels))
         self.dropout_rate = float(dropout_rate)
         self.dropout_seed, self._drop_step, self._mask_override = 0, 0, None      # the opt-in training step, see enable_training / drop_seed
-        self.arith = "f32"              # arithmetic of the eval / rollout forward's output net and branch stages 2-4, see set_arith
-
-    def set_arith(self, arith):
-        """Arithmetic of the evaluation / rollout forward's output net and of the convolutions of branch stages 2-4: ``"f32"`` (default,
-        the parity path: operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16
-        planes of the tensor scaled by a power of two -- one per point inside the output net --, three products, dropped term <= 2^-22;
-        csrc/rpb_deeponet_h.hip).  Only the evaluation forward changes: the opt-in training step
-        (``enable_training()``) stays on its kernels under either setting."""
-        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ the opt-in training step
     def enable_training(self, seed=None):
@@ -418,9 +413,12 @@ class DeepONet(EvalByDefault, Model):
         T_out = self.shape_out[0]
         prep = self._prep(x.device)
         prep_h = self._prep_f16x2(x.device) if self.arith == "f16x2" else None
-        b = self.branch_forward(x, prep, prep_h=prep_h if self.f16x2_convs else None)
+        sites = () if prep_h is None else self.F16X2_SITES
+        b = self.branch_forward(x, prep, prep_h=prep_h if "convs" in sites else None)
         t = self._trunk(T_out, H, W, x.device)
         if prep_h is not None:
+            self.f16x2_ran = tuple(s for s in self.ALL_F16X2_SITES if s in sites)
+        if "point" in sites:
             return self.k_point_mlp_f16x2(t, b, prep_h["point"]).view(B, T_out, H, W, self.output_channels)
         return self.k_point_mlp(t, b, prep["point"]).view(B, T_out, H, W, self.output_channels)
 

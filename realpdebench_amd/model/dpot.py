@@ -31,9 +31,6 @@ from ._common import HipFunction, colsum, sum_rows, wgrad
 from .model import Model as _ModelBase
 
 
-ARITHS = ("f32", "f16x2")
-
-
 def _rup(v, m):
     return (v + m - 1) // m * m
 
@@ -100,6 +97,17 @@ class _DPOTNet(nn.Module):
 
 
 class DPOT(_ModelBase):
+    """``set_arith`` selects the arithmetic of the evaluation / rollout forward's dense products: ``"f32"`` (default, the parity path:
+    token GEMMs from three bf16 planes with six products per fp32 product, the AFNO block MLP on the fp32 MFMA) or ``"f16x2"`` (opt-in:
+    operands as two fp16 planes, three products, dropped term <= 2^-22; one power-of-two scale per weight tensor, one per token row for
+    the GEMMs and one per (token, block) for the AFNO MLP, all formed on the device; csrc/rpb_gemm3hk.hip, csrc/rpb_dpot_h.hip, DESIGN.md
+    section 14.1).  ``F16X2_SITES`` names the products that move; one whose shape ``rpb_gemm3hk_supported`` /
+    ``rpb_afno_mlp_f16x2_supported`` refuses (``out2`` at K = 32, the narrow last layer) stays on the default kernel, and so does
+    every other kernel of the model (DFT stages, GroupNorm, PatchEmbed's first GEMM, the spectral resize).  Only ``_forward_hip``
+    without saved activations changes -- eval and rollout, every window of the sliding-window path included; the training step is
+    the same under either setting.  The fp16 planes live in the derived-weight cache and cost 4 bytes per weight element of the
+    moved sites: about the size of the fp32 weights themselves (about 2.5 GB with every site on at dpot_l: 1.8 GB FeedForward, 0.6 GB
+    out0, 0.1 GB AFNO composites)."""
     batch_independent = True      # no batch statistics (GroupNorm / LayerNorm): a step may run in micro-batches (trainer.ArenaTrainer)
     # The products set_arith("f16x2") can move: FeedForward "mlp0" (bias + GELU, K = E) and "mlp2" (bias + residual, K = hidden), the
     # out layer's "out0" (bias + GELU, N = ps^2 OD) and "out2" (bias + GELU, K = OD), the TimeAggregator's "tagg" (H1 . WcT, K = T E1p)
@@ -110,6 +118,7 @@ class DPOT(_ModelBase):
     # 7.91 -> 6.51 ms (dpot_s, B = 64) and 197.3 -> 106.3 ms (dpot_l, B = 64).
     ALL_F16X2_SITES = ("mlp0", "mlp2", "out0", "out2", "tagg", "afno")
     F16X2_SITES = ALL_F16X2_SITES
+    F16X2_GEMM = ("gemm3hk_supported", "gemm_nt_f16x2k")
 
     def __init__(self, shape_in, shape_out, img_size=128, in_channels=4, out_channels=4, in_timesteps=1, out_timesteps=1,
                  patch_size=8, embed_dim=512, depth=12, n_blocks=8, modes=32, mlp_ratio=4, out_layer_dim=32, normalize=False,
@@ -160,38 +169,8 @@ class DPOT(_ModelBase):
         self.dpot_model = _DPOTNet(img_size, patch_size, in_channels, out_channels, in_timesteps, out_timesteps, n_blocks, embed_dim,
                                    out_layer_dim, depth, mlp_ratio, n_cls, time_agg)
         self._plan = None
-        self.arith = "f32"              # arithmetic of the eval / rollout forward's dense products, see set_arith
-        self.f16x2_ran = ()             # the sites of F16X2_SITES the last eval forward ran on the two-plane kernels
         if checkpoint_path is not None:
             self.load_checkpoint(checkpoint_path)
-
-    def set_arith(self, arith):
-        """Arithmetic of the evaluation / rollout forward's dense products: ``"f32"`` (default, the parity path: token GEMMs from three
-        bf16 planes with six products per fp32 product, the AFNO block MLP on the fp32 MFMA) or ``"f16x2"`` (opt-in: operands as two
-        fp16 planes, three products, dropped term <= 2^-22; one power-of-two scale per weight tensor, one per token row for the GEMMs
-        and one per (token, block) for the AFNO MLP, all formed on the device; csrc/rpb_gemm3hk.hip, csrc/rpb_dpot_h.hip, DESIGN.md
-        section 14.1).  ``F16X2_SITES`` names the products that move; one whose shape ``rpb_gemm3hk_supported`` /
-        ``rpb_afno_mlp_f16x2_supported`` refuses (``out2`` at K = 32, the narrow last layer) stays on the default kernel, and so does
-        every other kernel of the model (DFT stages, GroupNorm, PatchEmbed's first GEMM, the spectral resize).  Only ``_forward_hip``
-        without saved activations changes -- eval and rollout, every window of the sliding-window path included; the training step is
-        the same under either setting.  The fp16 planes live in the derived-weight cache and cost 4 bytes per weight element of the
-        moved sites: about the size of the fp32 weights themselves (about 2.5 GB with every site on at dpot_l: 1.8 GB FeedForward, 0.6 GB out0, 0.1 GB AFNO composites)."""
-        if arith not in ARITHS:
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
-
-    def _h_gemm(self, ran, site, key, sources, weight, A, out, M, N, K, **epilogue):
-        """The token GEMM of ``site`` on rpb_gemm3hk if the f16x2 eval forward is running (``ran`` is its list of moved sites), the site
-        is in ``F16X2_SITES`` and the kernel takes the shape; False if the caller has to run the default kernel.  The weight's fp16
-        planes come from the derived-weight cache: rebuilt when a source tensor changes in place or is rebound, and after
-        ``load_state_dict``."""
-        if ran is None or site not in self.F16X2_SITES or not ops.gemm3hk_supported(M, N, K):
-            return False
-        wz = self._layouts.get("f16x2_" + key, sources, lambda: ops.gemm3h_wprep(weight()))
-        ops.gemm_nt_f16x2k(A, wz, out, M, N, K, **epilogue)
-        ran.append(site)
-        return True
 
     # ------------------------------------------------------------------ checkpoints (model/dpot.py:291-400)
     def load_checkpoint(self, checkpoint_path, device="cpu"):
@@ -376,8 +355,7 @@ class DPOT(_ModelBase):
         WcT = new(E, T * E1p)                                              # rows (j, t) of Wf x W2^T: one GEMM, M = E * T
         ops.gemm_nt(Wf, W2pT, WcT, E * T, E1p, E)
         tsrc = [pe2.weight, ta.w] + ([ta.gamma] if self.time_agg == "exp_mlp" else [])      # what WcT is made of
-        if not self._h_gemm(ran, "tagg", "tagg", tsrc, lambda: WcT, H1, X, Mt, E, T * E1p):
-            ops.gemm_nt(H1, WcT, X, Mt, E, T * E1p)
+        self._dense(ran, "tagg", "tagg", tsrc, WcT, H1, X, Mt, E, T * E1p)
         WsumT = new(E, E)                                                  # [j][i] = sum_t Wb[(t, i)][j]
         ops.reduce_partials_batched(Wf, E, T, E, WsumT)
         posb = pos + pe2.bias.data                                         # [n^2][E]: parameter-sized
@@ -417,13 +395,11 @@ class DPOT(_ModelBase):
             hid = self.hidden
             Hh = new(Mt, hid)
             Hpre = new(Mt, hid) if training else None
-            if not self._h_gemm(ran, "mlp0", f"mlp0_{bi}", [m0.weight], lambda: m0.weight.data.view(hid, E), Y2, Hh, Mt, hid, E,
-                                bias=m0.bias.data, act=1):
-                ops.gemm_nt(Y2, m0.weight.data.view(hid, E), Hh, Mt, hid, E, bias=m0.bias.data, act=1, pre_out=Hpre)
+            self._dense(ran, "mlp0", f"mlp0_{bi}", [m0.weight], m0.weight.data.view(hid, E), Y2, Hh, Mt, hid, E, bias=m0.bias.data,
+                        act=1, pre_out=Hpre)
             Xn = new(Mt, E)
-            if not self._h_gemm(ran, "mlp2", f"mlp2_{bi}", [m2.weight], lambda: m2.weight.data.view(E, hid), Hh, Xn, Mt, E, hid,
-                                bias=m2.bias.data, residual=X):
-                ops.gemm_nt(Hh, m2.weight.data.view(E, hid), Xn, Mt, E, hid, bias=m2.bias.data, residual=X)
+            self._dense(ran, "mlp2", f"mlp2_{bi}", [m2.weight], m2.weight.data.view(E, hid), Hh, Xn, Mt, E, hid, bias=m2.bias.data,
+                        residual=X)
             if training:
                 tapes.append(dict(X=X, Y1=Y1, st1=st1, S=S, Hs=Hs, Fo=Fo, st2=st2, Y2=Y2, Hh=Hh, Hpre=Hpre))
             X = Xn
@@ -435,16 +411,12 @@ class DPOT(_ModelBase):
         bt = ol0.bias.data.repeat(ps * ps)
         U = new(Mt, NU)
         Upre = new(Mt, NU) if training else None
-        Wt = None
-        if not self._h_gemm(ran, "out0", "out0", [ol0.weight], wt, X, U, Mt, NU, E, bias=bt, act=1):      # (the planes are of the permuted Wt)
-            Wt = wt()
-            ops.gemm_nt(X, Wt, U, Mt, NU, E, bias=bt, act=1, pre_out=Upre)
+        Wt = self._dense(ran, "out0", "out0", [ol0.weight], wt, X, U, Mt, NU, E, bias=bt, act=1, pre_out=Upre)      # (planes of the permuted Wt)
         Mp = Mt * ps * ps
         V = new(Mp, OD)
         Vpre = new(Mp, OD) if training else None
-        if not self._h_gemm(ran, "out2", "out2", [ol2.weight], lambda: ol2.weight.data.view(OD, OD), U, V, Mp, OD, OD,
-                            bias=ol2.bias.data, act=1):
-            ops.gemm_nt(U, ol2.weight.data.view(OD, OD), V, Mp, OD, OD, bias=ol2.bias.data, act=1, pre_out=Vpre)
+        self._dense(ran, "out2", "out2", [ol2.weight], ol2.weight.data.view(OD, OD), U, V, Mp, OD, OD, bias=ol2.bias.data, act=1,
+                    pre_out=Vpre)
         NO = To * Co
         NOp = _out_cols(NO)
         W3p, b3p = torch.zeros(NOp, OD, **f), torch.zeros(NOp, **f)

@@ -246,7 +246,6 @@ class FNO3d(Model):
         self._dev_cache = None
         self.dp = None            # set by realpdebench_amd.dp.DataParallel (RCCL)
         self.storage = "f32"      # activation storage of the eval / rollout forward, see set_storage
-        self.arith = "f32"        # arithmetic of the eval / rollout forward's fused launches, see set_arith
 
     # ------------------------------------------------------------------ parameters
     def reset_parameters(self):
@@ -360,11 +359,11 @@ class FNO3d(Model):
         BatchNorm stay fp32).  Training always stores fp32.  bf16 needs width 64 and 2 * modes3 <= 32 (the bf16-pipe kernels)."""
         if storage not in ("f32", "bf16"):
             raise ValueError(f"storage must be 'f32' or 'bf16', got {storage!r}")
-        if storage == "bf16" and (self.width != 64 or 2 * self.modes3 > 32 or type(self)._lift_fwd is not FNO3d._lift_fwd):
+        if storage == "bf16" and not self._eval_variants_built():
             raise NotImplementedError("bf16 activation storage is built for FNO3d at width 64 with modes3 <= 16")
         if storage != self.storage:
             self.storage = storage
-            self._ws = {k: v for k, v in self._ws.items() if k[1]}       # drop the eval workspaces (dtype changed)
+            self._drop_eval_workspaces()                                 # (dtype changed)
         return self
 
     def set_arith(self, arith):
@@ -373,14 +372,20 @@ class FNO3d(Model):
         unit in the last place --, three products, dropped term <= 2^-22: the grade of 3xTF32, half the matrix-pipe time).  ``"f16x2"``
         covers the eval ``cell_mix`` launches and the projection head at width 64; activations must stay inside fp16's range (they are
         BatchNorm outputs; the spectra and the inverse-stage matrix are rescaled by exact powers of two).  Training is not affected."""
-        if arith not in ("f32", "f16x2"):
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        if arith == "f16x2" and (self.width != 64 or 2 * self.modes3 > 32 or type(self)._lift_fwd is not FNO3d._lift_fwd):
+        if arith == "f16x2" and not self._eval_variants_built():         # (a known name: an unknown one gets its ValueError below)
             raise NotImplementedError("the f16x2 eval arithmetic is built for FNO3d at width 64 with modes3 <= 16")
-        if arith != self.arith:
-            self.arith = arith
-            self._ws = {k: v for k, v in self._ws.items() if k[1]}       # drop the eval workspaces (they hold the old arithmetic)
+        old = self.arith
+        super().set_arith(arith)
+        if arith != old:
+            self._drop_eval_workspaces()                                 # (they hold the old arithmetic)
         return self
+
+    def _eval_variants_built(self):
+        """The shape the bf16-storage and f16x2 eval kernels are built for: width 64, modes3 <= 16, the unmodified lift."""
+        return self.width == 64 and 2 * self.modes3 <= 32 and type(self)._lift_fwd is FNO3d._lift_fwd
+
+    def _drop_eval_workspaces(self):
+        self._ws = {k: v for k, v in self._ws.items() if k[1]}
 
     # ------------------------------------------------------------------ device-side constants
     def _consts(self, device):

@@ -29,7 +29,6 @@ from .fno import FNO3d
 from .model import Model as _ModelBase
 
 _DK = 64          # head width the HIP kernels are built for (n_hidden 256 / n_head 4 in every reference YAML)
-ARITHS = ("f32", "f16x2")      # GalerkinTransformer3d.set_arith
 
 
 class _Lin(nn.Module):
@@ -94,7 +93,7 @@ class _RegressorCore(FNO3d):
     arena, workspace and forward / backward pipelines; only the lift differs: its input is the 256-wide token tensor,
     hence a token GEMM plus the grid / bias / zero-pad scatter instead of the small-C_in lift kernel."""
     proj_act = 1           # SiLU, model.py:631-632
-    _lift_wz = None        # the fc weight's fp16 planes (ops.gemm3h_wprep) while an "f16x2" eval forward of the owning model runs
+    _lift_wz = None        # the fc weight's fp16 planes while an "f16x2" eval forward of the owning model runs its "fc" site on them
 
     def _wsplit(self):
         Ch = self.dim_in
@@ -145,10 +144,19 @@ _REG_RENAME = (("regressor.fc0.", "regressor.fc."), ("regressor.spectral_convs."
 
 
 class GalerkinTransformer3d(_ModelBase):
-    # The token GEMMs set_arith("f16x2") moves to rpb_gemm3h, of "qkv", "lr1", "lr2", "fc".  Measured at M = 2.6 M rows
-    # (profiles/galerkin_arith_probe.txt): Q|K|V 6.36 -> 5.11 ms and lr1 2.06 -> 1.95 ms are faster; lr2 (residual
-    # epilogue, 2.31 -> 4.70 ms) and fc (N = 128, 1.34 -> 1.69 ms) are not and stay on the default kernel.
+    """``set_arith`` selects the arithmetic of the evaluation / rollout forward's dense token GEMMs: ``"f32"`` (default, the parity path:
+    operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes, three products,
+    dropped term <= 2^-22; one power-of-two scale per weight and one per token row, formed inside the launch; csrc/rpb_gemm3h.hip,
+    DESIGN.md section 13.3).  ``F16X2_SITES`` names the GEMMs that move: Q|K|V and FeedForward lr1, the two the kernel is faster on; lr2
+    and the regressor's fc are wired but measured slower and stay on the default kernel.  Only the forward without saved activations
+    (eval mode under ``torch.no_grad()``) changes; a product whose shape ``rpb_gemm3h_supported`` refuses stays on the default
+    kernel, and so does every other kernel of the model.  The training step is the same under either setting."""
+    # The token GEMMs set_arith("f16x2") can move to rpb_gemm3h.  Measured at M = 2.6 M rows (profiles/galerkin_arith_probe.txt,
+    # DESIGN.md section 13.3): Q|K|V 6.36 -> 5.11 ms and lr1 2.06 -> 1.95 ms are faster; lr2 (residual epilogue, 2.31 -> 4.70 ms) and
+    # fc (N = 128, 1.34 -> 1.69 ms) are not and stay on the default kernel.
+    ALL_F16X2_SITES = ("qkv", "lr1", "lr2", "fc")
     F16X2_SITES = ("qkv", "lr1")
+    F16X2_GEMM = ("gemm3h_supported", "gemm_nt_f16x2")
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -197,39 +205,7 @@ class GalerkinTransformer3d(_ModelBase):
         self.regressor = _RegressorCore(int(g("fourier_modes_t", 4)), int(g("fourier_modes_x", 4)),
                                         int(g("fourier_modes_y", 4)), 1, freq, (T, H, W, C), self.shape_out)
         self._mask_override = None      # tests: dict(attn=[B,4,64,64], d1=[M,C], ffn=[M,ff], d2=[M,C]), already scaled
-        self.arith = "f32"              # arithmetic of the eval / rollout forward's four token GEMMs, see set_arith
         self.__name__ = "GalerkinTransformer3D"
-
-    def set_arith(self, arith):
-        """Arithmetic of the evaluation / rollout forward's dense token GEMMs: ``"f32"`` (default, the parity path: operands as three
-        bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes, three products, dropped term
-        <= 2^-22; one power-of-two scale per weight and one per token row, formed inside the launch; csrc/rpb_gemm3h.hip, DESIGN.md
-        section 13.3).  ``F16X2_SITES`` names the GEMMs that move: Q|K|V and FeedForward lr1, the two the kernel is faster on; lr2 and
-        the regressor's fc are wired but measured slower and stay on the default kernel.  Only the forward without saved activations
-        (eval mode under ``torch.no_grad()``) changes; a product whose shape ``rpb_gemm3h_supported`` refuses stays on the default
-        kernel, and so does every other kernel of the model.  The training step is the same under either setting."""
-        if arith not in ARITHS:
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
-
-    def _f16x2_planes(self, M):
-        """The operands of the f16x2 eval forward from the derived-weight cache (rebuilt when a source tensor changes in place or is
-        rebound, and after ``load_state_dict``): per site of ``F16X2_SITES`` whose shape rpb_gemm3h takes, the weight's fp16 planes;
-        for "qkv" the concatenated weight's, with the concatenated bias."""
-        C, Fh, at, ff, reg = self.n_hidden, self.dim_ff, self.encoder_layers[0].attn, self.encoder_layers[0].ff, self.regressor
-        out = {}
-        if "qkv" in self.F16X2_SITES and ops.gemm3h_supported(M, 3 * C, C):
-            src = [l.weight for l in at.linears] + [l.bias for l in at.linears]
-            out["qkv"] = self._layouts.get("f16x2_qkv", src, lambda: (ops.gemm3h_wprep(torch.cat([l.weight.data for l in at.linears], 0)),
-                                                                       torch.cat([l.bias.data for l in at.linears], 0)))
-        if "lr1" in self.F16X2_SITES and ops.gemm3h_supported(M, Fh, C):
-            out["lr1"] = self._layouts.get("f16x2_lr1", [ff.lr1.weight], lambda: ops.gemm3h_wprep(ff.lr1.weight.data))
-        if "lr2" in self.F16X2_SITES and ops.gemm3h_supported(M, C, Fh):
-            out["lr2"] = self._layouts.get("f16x2_lr2", [ff.lr2.weight], lambda: ops.gemm3h_wprep(ff.lr2.weight.data))
-        if "fc" in self.F16X2_SITES and ops.gemm3h_supported(M, reg.width, C):
-            out["fc"] = self._layouts.get("f16x2_fc", [reg.flat], lambda: ops.gemm3h_wprep(reg._wsplit()[0]))
-        return out
 
     # ------------------------------------------------------------------ reference-compatible state dict
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
@@ -351,15 +327,13 @@ class GalerkinTransformer3d(_ModelBase):
         X0 = new(M, C)
         ops.tokens_lift(x2, self.downscaler.id.weight.data, self.downscaler.id.bias.data, X0, M, Cin, C, False)
         # ---- attention (layers.py:829-899): fused Q|K|V projection, per-head LayerNorm of K and V
-        hz = self._f16x2_planes(M) if (self.arith == "f16x2" and save is None) else {}      # set_arith: the eval forward only
+        ran = [] if self.arith == "f16x2" and save is None else None      # the f16x2 eval forward: the sites it moved
         QKV = new(M, 3 * C)
-        if "qkv" in hz:
-            ops.gemm_nt_f16x2(X0, hz["qkv"][0], QKV, M, 3 * C, C, bias=hz["qkv"][1])
-            Wqkv = None
-        else:
-            Wqkv = torch.cat([l.weight.data for l in at.linears], 0)
-            bqkv = torch.cat([l.bias.data for l in at.linears], 0)
-            ops.gemm_nt(X0, Wqkv, QKV, M, 3 * C, C, bias=bqkv)
+        cat_b = lambda: torch.cat([l.bias.data for l in at.linears], 0)
+        # (the f16x2 eval forward caches the concatenated bias like the weight's planes: a routed Q|K|V forms no concatenation per call)
+        bqkv = cat_b() if ran is None else self._layouts.get("f16x2_qkv_bias", [l.bias for l in at.linears], cat_b)
+        Wqkv = self._dense(ran, "qkv", "qkv", [l.weight for l in at.linears], lambda: torch.cat([l.weight.data for l in at.linears], 0),
+                           X0, QKV, M, 3 * C, C, bias=bqkv)
         gK, bK = torch.cat([m.weight.data for m in at.norm_K]), torch.cat([m.bias.data for m in at.norm_K])
         gV, bV = torch.cat([m.weight.data for m in at.norm_V]), torch.cat([m.bias.data for m in at.norm_V])
         KVn = new(M, 2 * C)
@@ -373,27 +347,26 @@ class GalerkinTransformer3d(_ModelBase):
         # ---- x2 = x1 + drop(lr2(drop(relu(lr1(x1)))))  (layers.py:979-987, model.py:120-121)
         Hh = new(M, Fh)
         mf, drf = self._site(mk, "ffn")
-        if "lr1" in hz and mf is None and drf is None:                  # (a dropout site set through _mask_override keeps its kernel)
-            ops.gemm_nt_f16x2(X1, hz["lr1"], Hh, M, Fh, C, bias=enc.ff.lr1.bias.data, act=3)
-        else:
-            ops.gemm_nt(X1, enc.ff.lr1.weight.data, Hh, M, Fh, C, bias=enc.ff.lr1.bias.data, act=3, mask=mf, drop=drf)
+        lr1, lr2 = enc.ff.lr1, enc.ff.lr2                               # (a dropout site set through _mask_override keeps its kernel)
+        self._dense(ran, "lr1", "lr1", [lr1.weight], lr1.weight.data, X1, Hh, M, Fh, C, bias=lr1.bias.data, act=3, mask=mf, drop=drf)
         X2 = new(M, C)
         m2, dr2 = self._site(mk, "d2")
-        if "lr2" in hz and m2 is None and dr2 is None:
-            ops.gemm_nt_f16x2(Hh, hz["lr2"], X2, M, C, Fh, bias=enc.ff.lr2.bias.data, residual=X1)
-        else:
-            ops.gemm_nt(Hh, enc.ff.lr2.weight.data, X2, M, C, Fh, bias=enc.ff.lr2.bias.data, residual=X1, mask=m2, drop=dr2)
+        self._dense(ran, "lr2", "lr2", [lr2.weight], lr2.weight.data, Hh, X2, M, C, Fh, bias=lr2.bias.data, residual=X1, mask=m2, drop=dr2)
         # ---- spectral regressor (model.py:600-638)
         reg = self.regressor
         training = save is not None
         ws = reg._workspace(B, training, x.device)
         # FNO3d._forward_impl is the pipeline every FNO3d subclass and the trainers share and it calls _lift_fwd(x, ws) with that fixed
         # signature, so the fc planes travel as an attribute of the regressor for the duration of this call only (cleared on any exit)
-        reg._lift_wz = hz.get("fc")
+        reg._lift_wz = self._routed_planes(ran, "fc", "fc", [reg.flat], lambda: reg._wsplit()[0], M, reg.width, C)
         try:
             out = reg._forward_impl(X2, ws, training=training)
+            if reg._lift_wz is not None:
+                ran.append("fc")
         finally:
             reg._lift_wz = None
+        if ran is not None:
+            self.f16x2_ran = tuple(s for s in self.ALL_F16X2_SITES if s in ran)
         if save is not None:
             save.update(x2=x2, X0=X0, QKV=QKV, KVn=KVn, P=P, X1=X1, Hh=Hh, X2=X2, mk=mk, ws=ws, B=B, n=n, M=M,
                         Wqkv=Wqkv, gK=gK, gV=gV)

@@ -44,7 +44,6 @@ from .model import Model
 
 I16, I32 = torch.int16, torch.int32
 
-ARITHS = ("f32", "bf16x3", "f16x2")      # MWT3d.set_arith
 _PLANES = {"bf16x3": 3, "f16x2": 2}      # 16-bit planes per operand of rpb_mwt_conv3x
 
 
@@ -204,12 +203,18 @@ class _CZ(nn.Module):
 
 
 class MWT3d(EvalByDefault, Model):
-    batch_independent = True      # no batch statistics are ever computed (BN is never called): an enabled instance keeps declaring it
+    """``set_arith`` selects the arithmetic of the ``sparseKernel3d`` convolutions (kernels B and C of every CZ block and level) in the
+    evaluation / rollout forward: ``"f32"`` (default, the parity path: ``rpb_mwt_conv3`` on the fp32 MFMA), ``"bf16x3"`` (opt-in:
+    operands as three bf16 planes, ``hi + mid + lo`` exact, six products per fp32 product, fp32 accumulation) or ``"f16x2"`` (opt-in:
+    operands as two fp16 planes of the tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_mwt3x.hip).
+    Everything else in the forward is unchanged; training stays refused under every mode, and the opt-in training step
+    (``enable_training()``) runs the ``"f32"`` kernels whatever is selected here."""
+    batch_independent = True     # no batch statistics are ever computed (BN is never called): an enabled instance keeps declaring it
     training_unavailable = EvalByDefault.TRAIN_MSG.format("MWT", "MWT3d")
     # An enabled instance (``enable_training()``; DESIGN.md section 15.1) runs the ``"f32"`` kernels whatever ``set_arith`` says;
     # ``micro_batch`` works, more than one rank is refused.
     DP_MSG = "MWT3d training has only been verified on one rank: data-parallel training is not built, run it on one rank"
-    ARITHS = ARITHS
+    ARITHS = ("f32", "bf16x3", "f16x2")
 
     def __init__(self, k=3, alpha=2, c=1, nCZ=3, L=0, base="legendre", initializer=None, shape_in=None, shape_out=None, **kwargs):
         super().__init__()
@@ -248,16 +253,6 @@ class MWT3d(EvalByDefault, Model):
             initializer(self.Lc0.weight)
             initializer(self.Lc1.weight)
         self._plans = {}
-        self.arith = "f32"
-
-    def set_arith(self, arith):
-        """Arithmetic of the ``sparseKernel3d`` convolutions (kernels B and C of every CZ block and level) in the evaluation / rollout
-        forward: ``"f32"`` (default, the parity path: ``rpb_mwt_conv3`` on the fp32 MFMA), ``"bf16x3"`` (opt-in: operands as three bf16
-        planes, ``hi + mid + lo`` exact, six products per fp32 product, fp32 accumulation) or ``"f16x2"`` (opt-in: operands as two fp16
-        planes of the tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_mwt3x.hip).  Everything else in
-        the forward is unchanged; training stays refused under every mode, and the opt-in training step (``enable_training()``) runs
-        the ``"f32"`` kernels whatever is selected here."""
-        return super().set_arith(arith)
 
     # ------------------------------------------------------------------ checkpoints (models.py:791-844)
     def state_dict(self, *args, **kwargs):

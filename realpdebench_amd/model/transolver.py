@@ -75,7 +75,12 @@ class _Block(nn.Module):
 
 
 class Transolver(_ModelBase):
+    """``set_arith`` selects the arithmetic of the evaluation / rollout forward's 3x3x3 convolutions: ``"f32"`` (default, the parity
+    path: operands as three bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the
+    tensor scaled by a power of two, three products, dropped term <= 2^-22; csrc/rpb_conv3h.hip).  Only the forward that records no
+    backward changes: training forwards, data gradients and weight gradients stay on the default arithmetic."""
     batch_independent = True      # no batch statistics (GroupNorm / LayerNorm): a step may run in micro-batches (trainer.ArenaTrainer)
+
     def __init__(self, space_dim=1, n_layers=5, n_hidden=256, dropout=0.0, n_head=8, Time_Input=False, act="gelu",
                  mlp_ratio=1, fun_dim=1, out_dim=1, slice_num=32, ref=8, unified_pos=False, H=32, W=32, D=32):
         super().__init__()
@@ -95,7 +100,6 @@ class Transolver(_ModelBase):
         self.blocks = nn.ModuleList([_Block(n_hidden, n_head, mlp_ratio, slice_num, i == n_layers - 1, out_dim)
                                      for i in range(n_layers)])
         self.placeholder = nn.Parameter((1.0 / n_hidden) * torch.rand(n_hidden))
-        self.arith = "f32"              # arithmetic of the eval / rollout forward's convolutions, see set_arith
         self._mask_override = None      # tests: list of (attn_mask [B,h,G,G], out_mask [M,C]) per block, already scaled
 
     # fused, re-laid-out weight of the two convolutions: rows 0..C-1 = in_project_fx, C..2C-1 = in_project_x;
@@ -117,16 +121,6 @@ class Transolver(_ModelBase):
         a = self.blocks[i].Attn
         return self._layouts.get(("conv_cat_f16x2", i), (a.in_project_fx.weight, a.in_project_x.weight),
                                  lambda: ops.conv3_f16x2_weights(self._conv_cat(i)[0], 2 * self.n_hidden, self.n_hidden))
-
-    def set_arith(self, arith):
-        """Arithmetic of the evaluation / rollout forward's 3x3x3 convolutions: ``"f32"`` (default, the parity path: operands as three
-        bf16 planes, six products per fp32 product) or ``"f16x2"`` (opt-in: operands as two fp16 planes of the tensor scaled by a power
-        of two, three products, dropped term <= 2^-22; csrc/rpb_conv3h.hip).  Only the forward that records no backward changes:
-        training forwards, data gradients and weight gradients stay on the default arithmetic."""
-        if arith not in ("f32", "f16x2"):
-            raise ValueError(f"arith must be 'f32' or 'f16x2', got {arith!r}")
-        self.arith = arith
-        return self
 
     # ------------------------------------------------------------------ forward (optionally saving for backward)
     @torch.no_grad()

@@ -29,7 +29,7 @@ def _new(case="a"):
 
 def test_set_arith_surface():
     m = _new()
-    assert m.arith == "f32" and M.ARITHS == ("f32", "f16x2")
+    assert m.arith == "f32" and M.DeepONet.ARITHS == ("f32", "f16x2")
     assert m.set_arith("f16x2") is m and m.arith == "f16x2"
     for bad in ("fp8", "bf16x3", "", None):
         with pytest.raises(ValueError, match="arith must be"):

@@ -165,7 +165,7 @@ def test_opt_in_plumbing(monkeypatch):
         m.train()(x.clone().requires_grad_())
     with pytest.raises(RuntimeError, match="MI355X only"):          # train(): the HIP path, which has no CPU fallback
         m.train()(x)
-    for arith in M.ARITHS:                                          # the arithmetic switch changes none of this
+    for arith in M.MWT3d.ARITHS:                                        # the arithmetic switch changes none of this
         m.set_arith(arith)
         with pytest.raises(RuntimeError, match="MI355X only"):
             m.train().train_loss(x, y)

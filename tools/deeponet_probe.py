@@ -2,7 +2,7 @@
 the YAML's test_batch_size), a per-family kernel table from HIP events (algorithmic bytes and FLOPs of each launch are the bookkeeping
 of model/deeponet.py) and the point-MLP kernel's issued bf16 MFMA rate against the rate rpb_mfma_probe measures in the same run.
 Launches under ~100 us are dominated by the event overhead in this table.
-``--arith f16x2`` measures DeepONet.set_arith("f16x2") instead: the default arithmetic, the f16x2 output net alone (``f16x2_convs`` off) and
+``--arith f16x2`` measures DeepONet.set_arith("f16x2") instead: the default arithmetic, the f16x2 output net alone (``F16X2_SITES = ("point",)``) and
 the f16x2 output net with branch stages 2-4 on the f16x2 convolution, alternately in this process on the same seeded input (the default
 path is the comparison; the spread is what repeating one configuration gives), the HIP-event table of each, the point kernel's issued
 fp16 MFMA rate (three products per fp32 product) and the Rel-L2 of the f16x2 output against the default's.
@@ -44,7 +44,7 @@ def family(label):
     return label
 
 
-CONFIGS = (("f32", "f32", True), ("f16x2 point", "f16x2", False), ("f16x2 point+conv", "f16x2", True))
+CONFIGS = (("f32", "f32", ("point", "convs")), ("f16x2 point", "f16x2", ("point",)), ("f16x2 point+conv", "f16x2", ("point", "convs")))
 
 
 def median_ms(fn, runs, warm=3):
@@ -93,7 +93,7 @@ def arith_compare(m, B, runs, repeats, sustained, lines):
 
     def select(cfg):
         m.set_arith(cfg[1])
-        m.f16x2_convs = cfg[2]
+        m.F16X2_SITES = cfg[2]
         return m
 
     meds = {c[0]: [] for c in CONFIGS}
@@ -131,7 +131,7 @@ def arith_compare(m, B, runs, repeats, sustained, lines):
                      f"{products}x useful) = {issued:.0f} TFLOP/s issued = {issued / sustained:.2f} of the sustained rate of this run "
                      f"({sustained:.0f} TFLOP/s, rpb_mfma_probe, bf16); fp32-grade {v['flops'] / (v['ms'] * 1e-3) / 1e12:.1f} TFLOP/s delivered")
     select(CONFIGS[0])
-    del m.f16x2_convs
+    del m.F16X2_SITES
     del x
     torch.cuda.empty_cache()
 

@@ -133,7 +133,6 @@ def gemm_compare(_lib, ops, B, runs, repeats, sustained, lines):
 
 def forward_compare(_lib, m, B, shape, runs, repeats, default_only, lines):
     x = torch.randn(B, *shape, device="cuda:0", generator=torch.Generator(device="cuda:0").manual_seed(B))
-    ALL = ("qkv", "lr1", "lr2", "fc")
     ariths = ("f32",) if default_only else ("f32", "f16x2", "f16x2 all four")
 
     def select(a):
@@ -141,7 +140,7 @@ def forward_compare(_lib, m, B, shape, runs, repeats, default_only, lines):
             return m
         m.__dict__.pop("F16X2_SITES", None)                            # back to the class's routing
         if a == "f16x2 all four":
-            m.F16X2_SITES = ALL
+            m.F16X2_SITES = type(m).ALL_F16X2_SITES
         return m.set_arith("f32" if a == "f32" else "f16x2")
 
     meds = {a: [] for a in ariths}
