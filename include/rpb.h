@@ -428,7 +428,10 @@ int rpb_cell_mix_feat(const float* phi, const float* Wcomp, const float* bias, c
                       float* stats_part, long ncell, int FW, int K2, int Wp, const float* oxf_mean, const float* oxf_invstd,
                       const float* oxf_gamma, const float* oxf_beta, int oxf_gelu, void* stream);
 /*     rpb_bn_bwd_row_feat with gs == NULL: the BatchNorm-backward tensor itself is not stored (layer 0 of the fused trainer: its data
- *     gradient is never formed, so nothing reads gs_0; Y1 and the field moments are all that leaves the kernel). */
+ *     gradient is never formed, so nothing reads gs_0; Y1 and the field moments are all that leaves the kernel).
+ *     part[rpb_bn_bwd_row_slots(G)][64*64 + 64]: row o of a 64 x 64 block holds the field moments sum_cells gs[o] phi[f] in its columns
+ *     f < FW and zeros up to column 31; columns 32 .. 63 of the block's rows are NOT written (the caller reads columns < FW only);
+ *     [64] sum gs follows the block as in rpb_bn_bwd_row. */
 int rpb_bn_bwd_row_feat(const float* s, const float* gy, const float* phi, float* gs, const float* mean, const float* invstd,
                         const float* gamma, const float* beta, const float* sums, double count, int gelu, const float* GWt,
                         float* Y1, float* part, int G, int Wp, int C, int K2, int FW, void* stream);
@@ -436,7 +439,9 @@ int rpb_bn_bwd_row_feat(const float* s, const float* gy, const float* phi, float
 /*     Width 128 (configs/fsi/fno.yaml; the Galerkin SpectralRegressor): BatchNorm3d(+GELU) backward apply + adjoint W stage in one pass,
  *     run as the C = 64 row kernel on each 64-channel half of the 512-byte rows (autograd of fno.py:117-119 and of the last inverse
  *     stage, fno.py:63).  s, gy, gs: [G*Wp][128] (gs may alias gy); per-channel vectors [128]; sums [2*128]; Y1 [G][K2][128];
- *     part: scratch of 2 * rpb_bn_bwd_row_slots(G) rows of 64*64+64 floats.  No weight gradient (rpb_cell_wgrad).  Added in round 5
+ *     part: scratch of 2 * rpb_bn_bwd_row_slots(G) rows of 64*64+64 floats, one set of rows per 64-channel half: as for rpb_bn_bwd_row with
+ *     x == NULL the 64*64 block of the kernel's own rows stays unwritten, [64] sum gs of the half follows it, and rows beyond the
+ *     kernel's waves are cleared whole.  No weight gradient (rpb_cell_wgrad).  Added in round 5
  *     (additions do not change RPB_ABI_VERSION). */
 int rpb_bn_bwd_row_c128_supported(int Wp, int K2);
 int rpb_bn_bwd_row_c128(const float* s, const float* gy, float* gs, const float* mean, const float* invstd, const float* gamma,

@@ -78,7 +78,7 @@ def test_cell_mix_spectral_conv_stats(ops, C, Wp, rows, K2):
     ref = torch.einsum("wk,gkc->gwc", GW, z2).reshape(ncell, C) + x @ Wc.t() + bias
     out = torch.empty(ncell, C, device="cuda")
     nrows = ops.cell_mix_stat_rows(ncell, C, C, K2, Wp, True)
-    part = torch.zeros(nrows, 2, C, device="cuda")
+    part = torch.full((nrows, 2, C), float("nan"), device="cuda")
     ops.cell_mix(dev(x), dev(Wc), dev(bias), dev(z2), dev(GW.t()), out, part, ncell, C, C, K2, Wp)
     assert rel_l2(out.cpu(), ref) < TOL
     s = part.double().sum(0).cpu()
@@ -147,7 +147,7 @@ def test_cell_wgrad_crop(ops):
     ref = torch.einsum("bthwo,bthwi->oi", gs, xp[:, :T, :H, :W])
     ncrop = B * T * H * W
     slots = ops.cell_wgrad_slots(ncrop, CO, CI)
-    part = torch.zeros(slots, CO * CI + CO, device="cuda")
+    part = torch.full((slots, CO * CI + CO), float("nan"), device="cuda")
     ops.cell_wgrad(dev(gs).view(-1, CO), dev(xp).view(-1, CI), part, ncrop, CO, CI, crop=True, crop6=(T, H, W, Tp, Hp, Wp))
     assert rel_l2(part.double().sum(0).cpu()[:CO * CI].view(CO, CI), ref) < TOL
 
@@ -170,7 +170,7 @@ def test_cell_wgrad_crop_c128(ops, W, gelu):
     ref = torch.einsum("bthwo,bthwi->oi", gs, a[:, :T, :H, :W])
     ncrop = B * T * H * W
     slots = ops.cell_wgrad_slots(ncrop, C, C)
-    part = torch.zeros(slots, C * C + C, device="cuda")
+    part = torch.full((slots, C * C + C), float("nan"), device="cuda")
     xf = (dev(mean), dev(invstd), dev(gamma), dev(beta), gelu)
     ops.cell_wgrad(dev(gs).view(-1, C), dev(xp).view(-1, C), part, ncrop, C, C, crop=True, crop6=(T, H, W, Tp, Hp, Wp), xf=xf)
     got = part.double().sum(0).cpu()
@@ -499,7 +499,7 @@ def test_cell_mix_bf16_pipe_all_modes(ops, Wp, rows, K2, C):
         ref = spec + a @ Wc.t() + bias
         out = torch.full((ncell, C), float("nan"), device="cuda")
         nrows = ops.cell_mix_stat_rows(ncell, C, C, K2, Wp, True)
-        part = torch.zeros(nrows, 2, C, device="cuda")
+        part = torch.full((nrows, 2, C), float("nan"), device="cuda")
         ops.cell_mix(dev(s), dev(Wc), dev(bias), dev(z2), dev(GW.t()), out, part, ncell, C, C, K2, Wp, xf=xf)
         assert rel_l2(out.cpu(), ref) < 2e-6
         tot = part.double().sum(0).cpu()
@@ -521,7 +521,7 @@ def test_cell_mix_bf16_pipe_all_modes(ops, Wp, rows, K2, C):
         else:
             gz = ref2
         nb = ops.cell_mix_stat_rows(ncell, C, C, K2, Wp, True, True)
-        part2 = torch.zeros(nb, 2, C, device="cuda")
+        part2 = torch.full((nb, 2, C), float("nan"), device="cuda")
         ops.cell_mix(dev(g), dev(Wc), None, dev(z2), dev(GW.t()), out, part2, ncell, C, C, K2, Wp, transpose_w=True,
                      bnb=(dev(s),) + xf)
         assert rel_l2(out.cpu(), ref2) < 2e-6
