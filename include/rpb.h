@@ -40,8 +40,11 @@ extern "C" {
  *      and lost its b1, w2, gout and act arguments
  *   4  the MWT3d training step: rpb_mwt_conv3_keep, rpb_mwt_spec_out_keep, rpb_mwt_lo_bwd(_rows), rpb_mwt_conv3_dgrad,
  *      rpb_mwt_conv3_wgrad(_splits), rpb_mwt_modes_bwd, rpb_mwt_head_bwd(_rows), rpb_mwt_lift_wgrad(_rows) added (additions only; the
- *      number moves so that a binding that expects them refuses a library without them) */
-#define RPB_ABI_VERSION 4
+ *      number moves so that a binding that expects them refuses a library without them)
+ *   5  row BatchNorm, one family for CNO3d and DeepONet: rpb_cno_bn_rows / _stats / _finish / _act_fwd / _act_bwd_stats / _act_bwd_apply and
+ *      rpb_cno_sum64 renamed rpb_rowbn_* (rpb_rowbn_sum64, rpb_rowbn_act_bwd_apply take C up to 256; the apply takes Cpad % 4 == 0 for rows);
+ *      rpb_don_train_rows, rpb_don_sum64, rpb_don_bn_bwd_apply removed (rpb_rowbn_rows, rpb_rowbn_sum64, rpb_rowbn_act_bwd_apply) */
+#define RPB_ABI_VERSION 5
 const char* rpb_last_error(void);
 int rpb_abi_version(void);
 /* bf16 activation STORAGE (BASELINE.json configs[4]; the opt-in rollout path): how many bf16 planes of the fp32 constants (conv / fc1 weights,
@@ -806,57 +809,56 @@ int rpb_cno_conv3x_f16x2(const void* planes, const void* Wz, const float* sc, co
 int rpb_amax_exp_finish(int* e, void* stream);
 int rpb_cno_pack_f16x2(const float* x, void* planes, long M, int Cin, int* e, void* stream);
 /*
- * CNO3d training step (opt-in: CNO3d.enable_training()) -- batch-statistics BatchNorm3d + LeakyReLU(0.2) + residual on rows [M][C],
- * forward and backward (csrc/rpb_cno_train.hip; additions do not change RPB_ABI_VERSION).  C in {16, 32, 64, 128}; every row pointer arrives
- * at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed summation order (two calls are bit-equal).
- *     rpb_cno_bn_stats: part[rpb_cno_bn_rows()][2 C] (fp64) = per-workgroup (sum y, sum y^2) per channel of y [M][ld].
- *     rpb_cno_bn_finish: the partials -> mean, rstd = 1 / sqrt(var + eps) (biased var), a = gamma rstd, b = beta - mean a, formed in fp64 and
+ * Row BatchNorm (csrc/rpb_rowbn.hip) -- batch-statistics BatchNorm3d + LeakyReLU(0.2) + residual on channels-last rows [M][C], forward and
+ * backward: the row passes of the opt-in training steps of CNO3d (CNO3d.enable_training()) and DeepONet
+ * (DeepONet.enable_training(); section 16.1).  C in {16, 32, 64, 128} unless stated; every row pointer arrives at its first column,
+ * 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed summation order (two calls are bit-equal).
+ *     rpb_rowbn_stats: part[rpb_rowbn_rows()][2 C] (fp64) = per-workgroup (sum y, sum y^2) per channel of y [M][ld].
+ *     rpb_rowbn_finish: the partials -> mean, rstd = 1 / sqrt(var + eps) (biased var), a = gamma rstd, b = beta - mean a, formed in fp64 and
  *     rounded once; running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var M / (M - 1), in place.
- *     rpb_cno_bn_act_fwd: v = fmaf(y, a, b); if (act) v = v > 0 ? v : 0.2 v; if (res) v += res[m * ldr + c] -> fp32 rows out[m * ldo + c]
+ *     rpb_rowbn_act_fwd: v = fmaf(y, a, b); if (act) v = v > 0 ? v : 0.2 v; if (res) v += res[m * ldr + c] -> fp32 rows out[m * ldo + c]
  *     and / or the three bf16 planes out_planes[pl * M * ldp + m * ldp + c] (bit-equal to rpb_split3 of v; ldp % 8 == 0).
- *     rpb_cno_bn_act_bwd_stats: fp64 partials (as rpb_cno_bn_stats) of (sum dz, sum dz xhat), dz = gv (z > 0 ? 1 : 0.2) (gv without act),
- *     z = fmaf(y, a, b) recomputed, xhat = (y - mean) rstd.  rpb_cno_sum64: sums[2 C] = the partials' rows added in a fixed order.
- *     rpb_cno_bn_act_bwd_apply: dy = a (dz - sums[c] / M - xhat sums[C + c] / M) as fp32 rows dy[m * ldd + c] and / or bf16 planes, columns
+ *     rpb_rowbn_act_bwd_stats: fp64 partials (as rpb_rowbn_stats) of (sum dz, sum dz xhat), dz = gv (z > 0 ? 1 : 0.2) (gv without act),
+ *     z = fmaf(y, a, b) recomputed, xhat = (y - mean) rstd.
+ *     rpb_rowbn_sum64: sums[2 C] = the rows of part[rows][2 C] added in a fixed order: eight sums over the rows g, g + 8, ... ascending, then
+ *     those in index order.  C in {16, 32, 64, 128, 256}.
+ *     rpb_rowbn_act_bwd_apply: dy = a (dz - sums[c] / M - xhat sums[C + c] / M) as fp32 rows dy[m * ldd + c] and / or bf16 planes, columns
  *     C..Cpad-1 written as zero; dbeta[c] = sums[c], dgamma[c] = sums[C + c] (may be null).  has_bn = 0: dy = dz with the gate taken from the
- *     sign of y itself (the saved LeakyReLU output); a, b, mean, rstd, sums unused. */
-int rpb_cno_bn_rows(void);
-int rpb_cno_bn_stats(const float* y, int ld, long M, int C, double* part, void* stream);
-int rpb_cno_bn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
-                      float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd, void* stream);
-int rpb_cno_bn_act_fwd(const float* y, int ldy, const float* a, const float* b, const float* res, int ldr, float* out, int ldo,
-                       void* out_planes, int ldp, long M, int C, int act, void* stream);
-int rpb_cno_bn_act_bwd_stats(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
-                             const float* rstd, long M, int C, int act, double* part, void* stream);
-int rpb_cno_sum64(const double* part, int rows, int C, double* sums, void* stream);
-int rpb_cno_bn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
-                             const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy, int ldd,
-                             void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
+ *     sign of y itself (the saved LeakyReLU output); a, b, mean, rstd, sums unused.  C in {16, 32, 64, 128, 256}, Cpad % 4 == 0; plane
+ *     output needs Cpad % 8 == 0.  `dy` may alias `gv` element for element (same address, ldd == ldg): a thread reads all its elements of
+ *     a row and then writes them, nobody else touches those elements.  The DeepONet step applies in place on its pooling gradient. */
+int rpb_rowbn_rows(void);
+int rpb_rowbn_stats(const float* y, int ld, long M, int C, double* part, void* stream);
+int rpb_rowbn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
+                     float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd, void* stream);
+int rpb_rowbn_act_fwd(const float* y, int ldy, const float* a, const float* b, const float* res, int ldr, float* out, int ldo,
+                      void* out_planes, int ldp, long M, int C, int act, void* stream);
+int rpb_rowbn_act_bwd_stats(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                            const float* rstd, long M, int C, int act, double* part, void* stream);
+int rpb_rowbn_sum64(const double* part, int rows, int C, double* sums, void* stream);
+int rpb_rowbn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                            const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy, int ldd,
+                            void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
 
 /*
  * DeepONet training step (opt-in: DeepONet.enable_training()) -- the row passes of the backward pass and of the chunked output net
- * (csrc/rpb_deeponet_train.hip; additions do not change RPB_ABI_VERSION).  The forward batch statistics are
- * rpb_cno_bn_stats / rpb_cno_bn_finish, the forward pooling is rpb_don_bn_relu_pool with (a, b) of the batch statistics.  C in {32, 64, 128,
- * 256}; every row pointer arrives at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed
+ * (csrc/rpb_deeponet_train.hip).  The batch statistics, the sum of the backward partials and the BatchNorm
+ * backward apply are the row BatchNorm family above, the forward pooling is rpb_don_bn_relu_pool with (a, b) of the batch statistics.  C in
+ * {32, 64, 128, 256}; every row pointer arrives at its first column, 16-byte aligned, with a leading dimension % 4 == 0; no atomics and a fixed
  * summation order (two calls are bit-equal).
  *     rpb_don_pool_bwd: y [B][T][H][W][ldy] (the saved convolution output), v = relu(fmaf(y, a, b)).  mode 0, MaxPool3d(2): g [B][T/2][H/2]
  *     [W/2][ldg]; gz [cell] = g [window] at the first maximum of v in (t, h, w) scan order of the window if that maximum is > 0, else 0; 0 on
  *     the trailing frame / row / column the flooring pool drops.  mode 1, AdaptiveAvgPool3d((1, 4, 4)): g [B][4][4][ldg]; gz [cell] = (v > 0)
  *     sum over the bins (i, j) containing (h, w) of g[i][j] / (T |bin_i| |bin_j|), bins as rpb_don_bn_relu_pool.  gz [B][T][H][W][ldz], columns
- *     0..C-1.  part[rpb_don_train_rows()][2 C] (fp64) = per-workgroup (sum gz, sum gz xhat), xhat = (y - mean) rstd.
- *     rpb_don_sum64: sums[L] = the rows of part[rows][L] added in a fixed order.
- *     rpb_don_bn_bwd_apply: dy[m * ldd + c] = a (gz - sums[c] / M - xhat sums[C + c] / M), columns C..Cpad-1 written as zero; dy may be gz
- *     itself (ldd == ldz); dbeta[c] = sums[c], dgamma[c] = sums[C + c] (may be null).
+ *     0..C-1.  part[rpb_rowbn_rows()][2 C] (fp64) = per-workgroup (sum gz, sum gz xhat), xhat = (y - mean) rstd, for rpb_rowbn_sum64 and
+ *     rpb_rowbn_act_bwd_apply (has_bn = 1, act = 0).
  *     rpb_don_point_mul: x[r][j] = b[s][j] t[n][j] for the R points q = q0 + r of the B N (sample, point) pairs, s = q / N, n = q % N; t [N][p],
  *     b [B][p], x [R][p] (a chunk may end inside a sample).  p in {64, 128, 256}.
  *     rpb_don_point_mul_bwd: gx [R][p] = the rows of points n0..n0+R-1 of ONE sample whose branch vector is b [p]: gt[n0 + r] += gx[r] (.) b
- *     (the caller zeroes gt and visits the samples in order on one stream) and part[rpb_don_train_rows()][p] = per-workgroup sums (formed in
+ *     (the caller zeroes gt and visits the samples in order on one stream) and part[rpb_rowbn_rows()][p] = per-workgroup sums (formed in
  *     fp64) of gx[r] (.) t[n0 + r]; rpb_reduce_partials (accumulate = 1) adds them into gb[s]. */
-int rpb_don_train_rows(void);
 int rpb_don_pool_bwd(const float* y, int ldy, const float* g, int ldg, const float* a, const float* b, const float* mean, const float* rstd,
                      float* gz, int ldz, int B, int T, int H, int W, int C, int mode, double* part, void* stream);
-int rpb_don_sum64(const double* part, int rows, int L, double* sums, void* stream);
-int rpb_don_bn_bwd_apply(const float* gz, int ldz, const float* y, int ldy, const float* a, const float* mean, const float* rstd,
-                         const double* sums, long M, int C, int Cpad, float* dy, int ldd, float* dgamma, float* dbeta, void* stream);
 int rpb_don_point_mul(const float* t, const float* b, float* x, long q0, long R, int B, long N, int p, void* stream);
 int rpb_don_point_mul_bwd(const float* gx, const float* t, const float* b, float* gt, float* part, long n0, long R, long N, int p,
                           void* stream);

@@ -7,7 +7,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 4         # RPB_ABI_VERSION of include/rpb.h
+ABI_VERSION = 5         # RPB_ABI_VERSION of include/rpb.h
 LIB_PATH = os.environ.get("RPB_LIB_PATH") or os.path.join(_HERE, "csrc", "librpb_hip.so")     # RPB_LIB_PATH: an instrumented build (tools/dbg)
 
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
@@ -223,17 +223,14 @@ SIGNATURES = {
     "rpb_cno_conv3x_f16x2": (_I, "ppppppp" + "l" + "iiiiii" + "iii" + "pp" + "p"),
     "rpb_amax_exp_finish": (_I, "p" + "p"),
     "rpb_cno_pack_f16x2": (_I, "pp" + "li" + "p" + "p"),
-    "rpb_cno_bn_rows": (_I, ""),
-    "rpb_cno_bn_stats": (_I, "p" + "ili" + "p" + "p"),
-    "rpb_cno_bn_finish": (_I, "p" + "ili" + "pppp" + "dd" + "pppp" + "p"),
-    "rpb_cno_bn_act_fwd": (_I, "pi" + "pp" + "pi" + "pi" + "pi" + "lii" + "p"),
-    "rpb_cno_bn_act_bwd_stats": (_I, "pi" + "pi" + "pppp" + "lii" + "p" + "p"),
-    "rpb_cno_sum64": (_I, "p" + "ii" + "p" + "p"),
-    "rpb_cno_bn_act_bwd_apply": (_I, "pi" + "pi" + "pppp" + "p" + "liiii" + "pi" + "pi" + "pp" + "p"),
-    "rpb_don_train_rows": (_I, ""),
+    "rpb_rowbn_rows": (_I, ""),
+    "rpb_rowbn_stats": (_I, "p" + "ili" + "p" + "p"),
+    "rpb_rowbn_finish": (_I, "p" + "ili" + "pppp" + "dd" + "pppp" + "p"),
+    "rpb_rowbn_act_fwd": (_I, "pi" + "pp" + "pi" + "pi" + "pi" + "lii" + "p"),
+    "rpb_rowbn_act_bwd_stats": (_I, "pi" + "pi" + "pppp" + "lii" + "p" + "p"),
+    "rpb_rowbn_sum64": (_I, "p" + "ii" + "p" + "p"),
+    "rpb_rowbn_act_bwd_apply": (_I, "pi" + "pi" + "pppp" + "p" + "liiii" + "pi" + "pi" + "pp" + "p"),
     "rpb_don_pool_bwd": (_I, "pi" + "pi" + "pppp" + "pi" + "iiiiii" + "p" + "p"),
-    "rpb_don_sum64": (_I, "p" + "ii" + "p" + "p"),
-    "rpb_don_bn_bwd_apply": (_I, "pi" + "pi" + "ppp" + "p" + "lii" + "pi" + "pp" + "p"),
     "rpb_don_point_mul": (_I, "ppp" + "ll" + "il" + "i" + "p"),
     "rpb_don_point_mul_bwd": (_I, "ppppp" + "lll" + "i" + "p"),
     "rpb_gemm3h_supported": (_I, "liiii"),

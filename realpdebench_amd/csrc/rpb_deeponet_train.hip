@@ -1,8 +1,8 @@
 // DeepONet training step (realpdebench/model/deeponet.py in train() mode; opt-in: DeepONet.enable_training()).  The convolutions and
 // Linear layers stay rpb_im2col / rpb_gemm3x / rpb_split3 / rpb_conv3x (data gradients: the same kernels on transposed / flipped weights),
-// the weight gradients stay rpb_gemm_tn / rpb_gemm3x_tn / rpb_conv3x_wgrad, the forward batch statistics are rpb_cno_bn_stats /
-// rpb_cno_bn_finish (C = 256 as two column halves) and the forward pooling is rpb_don_bn_relu_pool with (a, b) of the batch statistics.
-// New here are the memory-bound row passes of the backward pass and of the chunked output net:
+// the weight gradients stay rpb_gemm_tn / rpb_gemm3x_tn / rpb_conv3x_wgrad, the batch statistics and the BatchNorm backward apply are the
+// rpb_rowbn_* family (rpb_rowbn.hip; the forward statistics at C = 256 as two column halves) and the forward pooling is
+// rpb_don_bn_relu_pool with (a, b) of the batch statistics.  Here are the memory-bound row passes that are DeepONet's own:
 //
 //   rpb_don_pool_bwd        gz = d loss / d (y a + b) from the gradient of the pooled stage output, y = the saved convolution output:
 //                           mode 0  MaxPool3d(2): one window per output cell; the gradient goes to the FIRST maximum in (t, h, w) scan order of
@@ -10,29 +10,15 @@
 //                                   the flooring pool drops;
 //                           mode 1  AdaptiveAvgPool3d((1, 4, 4)): gather form, a cell adds g_bin / |bin| over the (overlapping or replicated)
 //                                   bins that contain it, gated by v > 0.
-//                           The same launch leaves fp64 partials of (sum gz, sum gz xhat), xhat = (y - mean) rstd, per workgroup.
-//   rpb_don_sum64           the partials' rows added in a fixed order -> sums[L] (fp64)
-//   rpb_don_bn_bwd_apply    dy = a (gz - sums[c] / M - xhat sums[C + c] / M), columns C..Cpad-1 zero; dbeta = sums[c], dgamma = sums[C + c]
+//                           The same launch leaves fp64 partials of (sum gz, sum gz xhat), xhat = (y - mean) rstd, per workgroup, for
+//                           rpb_rowbn_sum64 and rpb_rowbn_act_bwd_apply (has_bn = 1, act = 0, in place on gz).
 //   rpb_don_point_mul       x[r] = b[s] (.) t[n] for the points q = q0 + r, s = q / N, n = q % N of one chunk of the output net
 //   rpb_don_point_mul_bwd   one sample's rows of a chunk: gt[n] += gx (.) b[s] and fp32 partials (summed in fp64) of gb[s] = sum_n gx (.) t[n]
 //
 // Every kernel is grid-stride with 16-byte accesses, fp64 only in the partial sums, no atomics and a fixed summation order: two calls
 // are bit-equal.  The ReLU gate and the arg-max are recomputed from fmaf(y, a, b) -- the expression rpb_don_bn_relu_pool evaluates -- so
 // neither a mask nor an index tensor is stored.
-#include "rpb_mma.h"
-#include <stdint.h>
-
-#define DT_THREADS 256
-
-static bool dt_chan_ok(int C) { return C == 32 || C == 64 || C == 128 || C == 256; }
-static bool dt_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
-static unsigned dt_grid(long total) {
-    long grid = (total + DT_THREADS - 1) / DT_THREADS;
-    const long cap = (long)rpb_num_cus() * 16;
-    return (unsigned)(grid > cap ? cap : (grid < 1 ? 1 : grid));
-}
-
-extern "C" int rpb_don_train_rows(void) { return rpb_num_cus() * 4; }
+#include "rpb_rowbn.h"
 
 // ---------------------------------------------------------------------------------- pooling backward + BatchNorm backward sums
 // A thread owns 4 channels and every nsub-th item of its workgroup's share (item = one 2 x 2 x 2 window, or one cell in mode 1); the nsub
@@ -46,10 +32,10 @@ struct DtPoolArgs {
     int B, T, H, W, C, ldy, ldg, ldz, mode;
 };
 
-__global__ __launch_bounds__(DT_THREADS) void dt_pool_bwd_kernel(DtPoolArgs p) {
-    __shared__ double red[DT_THREADS * 8];                              // [nsub][2 C] = 256 / (C / 4) * 2 C doubles = 16 KB
+__global__ __launch_bounds__(ROWBN_THREADS) void dt_pool_bwd_kernel(DtPoolArgs p) {
+    __shared__ double red[ROWBN_THREADS * 8];                           // [nsub][2 C] = 256 / (C / 4) * 2 C doubles = 16 KB
     const int c4n = p.C >> 2;
-    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = DT_THREADS / c4n;
+    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = ROWBN_THREADS / c4n;
     const int c0 = 4 * c4;
     const f32x4 a4 = *reinterpret_cast<const f32x4*>(p.a + c0), b4 = *reinterpret_cast<const f32x4*>(p.b + c0);
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -139,113 +125,26 @@ __global__ __launch_bounds__(DT_THREADS) void dt_pool_bwd_kernel(DtPoolArgs p) {
             *reinterpret_cast<f32x4*>(p.gz + it * p.ldz + c0) = gz4;
         }
     }
-    double* mine = red + (long)sub * 2 * p.C;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        mine[c0 + i] = s0[i];
-        mine[p.C + c0 + i] = s1[i];
-    }
-    __syncthreads();
-    for (int n = threadIdx.x; n < 2 * p.C; n += DT_THREADS) {
-        double s = 0.;
-        for (int k = 0; k < nsub; ++k) s += red[(long)k * 2 * p.C + n];
-        p.part[(long)blockIdx.x * 2 * p.C + n] = s;
-    }
+    rowbn_block_sums<2>(red, s0, s1, p.C, c0, sub, nsub, p.part);
 }
 
 extern "C" int rpb_don_pool_bwd(const float* y, int ldy, const float* g, int ldg, const float* a, const float* b, const float* mean,
                                 const float* rstd, float* gz, int ldz, int B, int T, int H, int W, int C, int mode, double* part,
                                 void* stream) {
-    RPB_REQUIRE(y && g && a && b && mean && rstd && gz && part && B > 0 && T > 0 && H > 0 && W > 0 && dt_chan_ok(C) && (mode == 0 || mode == 1),
+    RPB_REQUIRE(y && g && a && b && mean && rstd && gz && part && B > 0 && T > 0 && H > 0 && W > 0 && rowbn_chan_ok(C, 32, 256) && (mode == 0 || mode == 1),
                 "don_pool_bwd: bad arguments (B=%d T=%d H=%d W=%d C=%d mode=%d; C in {32, 64, 128, 256})", B, T, H, W, C, mode);
     RPB_REQUIRE((long)B * T * H * W < (1L << 31), "don_pool_bwd: B T H W = %ld cells (< 2^31)", (long)B * T * H * W);
     RPB_REQUIRE(mode == 1 || (T >= 2 && H >= 2 && W >= 2), "don_pool_bwd: MaxPool3d(2) needs extents >= 2 (T=%d H=%d W=%d)", T, H, W);
-    RPB_REQUIRE(ldy >= C && ldy % 4 == 0 && ldg >= C && ldg % 4 == 0 && ldz >= C && ldz % 4 == 0 && dt_al16(y) && dt_al16(g) && dt_al16(gz) &&
-                    dt_al16(a) && dt_al16(b),
+    RPB_REQUIRE(ldy >= C && ldy % 4 == 0 && ldg >= C && ldg % 4 == 0 && ldz >= C && ldz % 4 == 0 && rowbn_al16(y) && rowbn_al16(g) && rowbn_al16(gz) &&
+                    rowbn_al16(a) && rowbn_al16(b),
                 "don_pool_bwd: ldy=%d ldg=%d ldz=%d must be >= C and %% 4 == 0, y / g / gz / a / b 16-byte aligned", ldy, ldg, ldz);
     DtPoolArgs p{y, g, a, b, mean, rstd, gz, part, B, T, H, W, C, ldy, ldg, ldz, mode};
-    hipLaunchKernelGGL(dt_pool_bwd_kernel, dim3(rpb_don_train_rows()), dim3(DT_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dt_pool_bwd_kernel, dim3(rowbn_rows()), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
     RPB_CHECK_LAUNCH("don_pool_bwd");
 }
 
-// ---------------------------------------------------------------------------------- the partials' fixed-order sum
-// One workgroup per 16 columns: thread = (row group g of 16, column c of 16) adds rows g, g + 16, ...; the groups are added in index order.
-__global__ __launch_bounds__(DT_THREADS) void dt_sum64_kernel(const double* __restrict__ part, int rows, int L, double* __restrict__ sums) {
-    __shared__ double red[16][16];
-    const int c = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int col = blockIdx.x * 16 + c;
-    double s = 0.;
-    if (col < L)
-        for (int r = g; r < rows; r += 16) s += part[(long)r * L + col];
-    red[g][c] = s;
-    __syncthreads();
-    if (threadIdx.x >= 16 || col >= L) return;
-    double t = 0.;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][c];
-    sums[col] = t;
-}
-
-extern "C" int rpb_don_sum64(const double* part, int rows, int L, double* sums, void* stream) {
-    RPB_REQUIRE(part && sums && rows > 0 && L > 0, "don_sum64: bad arguments (rows=%d L=%d)", rows, L);
-    hipLaunchKernelGGL(dt_sum64_kernel, dim3((L + 15) / 16), dim3(DT_THREADS), 0, (hipStream_t)stream, part, rows, L, sums);
-    RPB_CHECK_LAUNCH("don_sum64");
-}
-
-// ---------------------------------------------------------------------------------- BatchNorm backward apply
-// One thread = 4 channels of one row.  dy may be gz itself (a lane reads its element, then writes it).
-struct DtApplyArgs {
-    const float *gz, *y, *a, *mean, *rstd;
-    const double* sums;    // [2 C]: (sum gz, sum gz xhat)
-    float *dy, *dgamma, *dbeta;
-    long M;
-    int C, Cpad, ldz, ldy, ldd;
-};
-
-__global__ __launch_bounds__(DT_THREADS) void dt_bn_bwd_apply_kernel(DtApplyArgs p) {
-    const int c4n = p.Cpad >> 2;
-    const long total = p.M * c4n;
-    if (p.dgamma && blockIdx.x == 0)
-        for (int c = threadIdx.x; c < p.C; c += DT_THREADS) {
-            p.dbeta[c] = (float)p.sums[c];
-            p.dgamma[c] = (float)p.sums[p.C + c];
-        }
-    const double inv_m = 1.0 / (double)p.M;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long m = idx / c4n;
-        const int c = (int)(idx - m * c4n) * 4;
-        f32x4 d = {0.f, 0.f, 0.f, 0.f};
-        if (c < p.C) {                                                  // C % 4 == 0: a run of 4 is inside or outside
-            const f32x4 g4 = RPB_SLD4(p.gz + m * p.ldz + c), y4 = RPB_SLD4(p.y + m * p.ldy + c);
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(p.a + c), mu = *reinterpret_cast<const f32x4*>(p.mean + c);
-            const f32x4 rs = *reinterpret_cast<const f32x4*>(p.rstd + c);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float k1 = (float)(p.sums[c + i] * inv_m), k2 = (float)(p.sums[p.C + c + i] * inv_m);
-                const float xh = (y4[i] - mu[i]) * rs[i];
-                d[i] = a4[i] * (g4[i] - k1 - xh * k2);
-            }
-        }
-        *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c) = d;
-    }
-}
-
-extern "C" int rpb_don_bn_bwd_apply(const float* gz, int ldz, const float* y, int ldy, const float* a, const float* mean, const float* rstd,
-                                    const double* sums, long M, int C, int Cpad, float* dy, int ldd, float* dgamma, float* dbeta,
-                                    void* stream) {
-    RPB_REQUIRE(gz && y && a && mean && rstd && sums && dy && M > 0 && M < (1L << 31) && dt_chan_ok(C) && Cpad >= C && Cpad % 4 == 0 &&
-                    (!dgamma == !dbeta),
-                "don_bn_bwd_apply: bad arguments (M=%ld C=%d Cpad=%d; C in {32, 64, 128, 256}, Cpad >= C, dgamma and dbeta come together)", M, C, Cpad);
-    RPB_REQUIRE(ldz >= C && ldz % 4 == 0 && ldy >= C && ldy % 4 == 0 && ldd >= Cpad && ldd % 4 == 0 && dt_al16(gz) && dt_al16(y) && dt_al16(dy) &&
-                    dt_al16(a) && dt_al16(mean) && dt_al16(rstd),
-                "don_bn_bwd_apply: ldz=%d ldy=%d (>= C) ldd=%d (>= Cpad), all %% 4 == 0, every row pointer 16-byte aligned", ldz, ldy, ldd);
-    DtApplyArgs p{gz, y, a, mean, rstd, sums, dy, dgamma, dbeta, M, C, Cpad, ldz, ldy, ldd};
-    hipLaunchKernelGGL(dt_bn_bwd_apply_kernel, dim3(dt_grid(M * (Cpad / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("don_bn_bwd_apply");
-}
-
 // ---------------------------------------------------------------------------------- the output net's input and its backward
-__global__ __launch_bounds__(DT_THREADS) void dt_point_mul_kernel(const float* __restrict__ t, const float* __restrict__ b, float* __restrict__ x,
+__global__ __launch_bounds__(ROWBN_THREADS) void dt_point_mul_kernel(const float* __restrict__ t, const float* __restrict__ b, float* __restrict__ x,
                                                                   long q0, long R, long N, int p) {
     const int c4n = p >> 2;
     const long total = R * c4n;
@@ -259,21 +158,21 @@ __global__ __launch_bounds__(DT_THREADS) void dt_point_mul_kernel(const float* _
 }
 
 extern "C" int rpb_don_point_mul(const float* t, const float* b, float* x, long q0, long R, int B, long N, int p, void* stream) {
-    RPB_REQUIRE(t && b && x && q0 >= 0 && R > 0 && B > 0 && N > 0 && q0 + R <= (long)B * N && (p == 64 || p == 128 || p == 256) && dt_al16(t) &&
-                    dt_al16(b) && dt_al16(x),
+    RPB_REQUIRE(t && b && x && q0 >= 0 && R > 0 && B > 0 && N > 0 && q0 + R <= (long)B * N && (p == 64 || p == 128 || p == 256) && rowbn_al16(t) &&
+                    rowbn_al16(b) && rowbn_al16(x),
                 "don_point_mul: bad arguments (q0=%ld R=%ld B=%d N=%ld p=%d; q0 + R <= B N, p in {64, 128, 256}, 16-byte aligned)", q0, R, B, N, p);
-    hipLaunchKernelGGL(dt_point_mul_kernel, dim3(dt_grid(R * (p / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, t, b, x, q0, R, N, p);
+    hipLaunchKernelGGL(dt_point_mul_kernel, dim3(rowbn_grid(R * (p / 4))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, t, b, x, q0, R, N, p);
     RPB_CHECK_LAUNCH("don_point_mul");
 }
 
 // gx [R][p]: the rows of points n0 .. n0 + R - 1 of ONE sample (b: that sample's branch vector).  gt[n0 + r] += gx[r] (.) b; part[block][p] =
 // sum over the block's rows of gx[r] (.) t[n0 + r] (fp64 sums, stored as fp32; rpb_reduce_partials finishes them in fp64).
-__global__ __launch_bounds__(DT_THREADS) void dt_point_mul_bwd_kernel(const float* __restrict__ gx, const float* __restrict__ t,
+__global__ __launch_bounds__(ROWBN_THREADS) void dt_point_mul_bwd_kernel(const float* __restrict__ gx, const float* __restrict__ t,
                                                                       const float* __restrict__ b, float* gt, float* __restrict__ part,
                                                                       long n0, long R, int p) {
-    __shared__ double red[DT_THREADS * 4];                              // [nsub][p] = 256 / (p / 4) * p doubles = 8 KB
+    __shared__ double red[ROWBN_THREADS * 4];                           // [nsub][p] = 256 / (p / 4) * p doubles = 8 KB
     const int c4n = p >> 2;
-    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = DT_THREADS / c4n;
+    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = ROWBN_THREADS / c4n;
     const int c0 = 4 * c4;
     const f32x4 b4 = *reinterpret_cast<const f32x4*>(b + c0);
     double s[4] = {0., 0., 0., 0.};
@@ -285,21 +184,14 @@ __global__ __launch_bounds__(DT_THREADS) void dt_point_mul_bwd_kernel(const floa
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i] += (double)g4[i] * (double)t4[i];
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[(long)sub * p + c0 + i] = s[i];
-    __syncthreads();
-    for (int n = threadIdx.x; n < p; n += DT_THREADS) {
-        double v = 0.;
-        for (int k = 0; k < nsub; ++k) v += red[(long)k * p + n];
-        part[(long)blockIdx.x * p + n] = (float)v;
-    }
+    rowbn_block_sums<1>(red, s, nullptr, p, c0, sub, nsub, part);
 }
 
 extern "C" int rpb_don_point_mul_bwd(const float* gx, const float* t, const float* b, float* gt, float* part, long n0, long R, long N, int p,
                                      void* stream) {
-    RPB_REQUIRE(gx && t && b && gt && part && n0 >= 0 && R > 0 && n0 + R <= N && (p == 64 || p == 128 || p == 256) && dt_al16(gx) && dt_al16(t) &&
-                    dt_al16(b) && dt_al16(gt),
+    RPB_REQUIRE(gx && t && b && gt && part && n0 >= 0 && R > 0 && n0 + R <= N && (p == 64 || p == 128 || p == 256) && rowbn_al16(gx) && rowbn_al16(t) &&
+                    rowbn_al16(b) && rowbn_al16(gt),
                 "don_point_mul_bwd: bad arguments (n0=%ld R=%ld N=%ld p=%d; n0 + R <= N, p in {64, 128, 256}, 16-byte aligned)", n0, R, N, p);
-    hipLaunchKernelGGL(dt_point_mul_bwd_kernel, dim3(rpb_don_train_rows()), dim3(DT_THREADS), 0, (hipStream_t)stream, gx, t, b, gt, part, n0, R, p);
+    hipLaunchKernelGGL(dt_point_mul_bwd_kernel, dim3(rowbn_rows()), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, gx, t, b, gt, part, n0, R, p);
     RPB_CHECK_LAUNCH("don_point_mul_bwd");
 }

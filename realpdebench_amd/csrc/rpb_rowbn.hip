@@ -1,24 +1,19 @@
-// CNO3d training step (realpdebench/model/cno.py:96-100, 146-152, 222-231 in train() mode): batch-statistics BatchNorm3d on channels-last
-// rows [M][C], M = B * T * H * W, with LeakyReLU(0.2) and the residual add, forward and backward.  The convolutions themselves stay
-// rpb_cno_conv3x (forward with sc = 1, sh = bias, act = 0; data gradient with the flipped, transposed taps -- seven of the 34 on the
-// exact-fp32 rpb_gemm_nt, model/cno.py EXACT_DGRAD) and the weight gradient stays
-// rpb_gemm_tn / rpb_conv3x_wgrad: what is new here are the memory-bound row passes around them.
+// Batch-statistics BatchNorm on channels-last rows [M][ld], forward and backward, with the LeakyReLU(0.2) gate and the residual add of the
+// CNO3d layers: the memory-bound row passes of the opt-in training steps of CNO3d (model/cno.py; realpdebench/model/cno.py:96-100,
+// 146-152, 222-231 in train() mode) and DeepONet (model/deeponet.py; its pooling backward writes the backward partials itself,
+// rpb_deeponet_train.hip).  The convolutions, their data gradients and weight gradients are the callers'.
 //
-//   forward    y = conv(x) + bias                           (rpb_cno_conv3x)
-//              (sum y, sum y^2) per channel                 rpb_cno_bn_stats  -> fp64 partials
-//              mean, rstd, a = gamma rstd, b = beta - mean a; running statistics      rpb_cno_bn_finish
-//              z = y a + b;  v = act ? lrelu(z) : z;  v += res                        rpb_cno_bn_act_fwd  (fp32 rows and / or bf16 planes)
-//   backward   dz = gv (z > 0 ? 1 : 0.2);  (sum dz, sum dz xhat), xhat = (y - mean) rstd   rpb_cno_bn_act_bwd_stats -> fp64 partials
-//              fixed-order sum of the partials              rpb_cno_sum64
-//              dy = a (dz - dbeta / M - xhat dgamma / M);  dgamma, dbeta              rpb_cno_bn_act_bwd_apply (fp32 rows + bf16 planes)
+//   forward    (sum y, sum y^2) per channel                 rpb_rowbn_stats  -> fp64 partials
+//              mean, rstd, a = gamma rstd, b = beta - mean a; running statistics      rpb_rowbn_finish
+//              z = y a + b;  v = act ? lrelu(z) : z;  v += res                        rpb_rowbn_act_fwd  (fp32 rows and / or bf16 planes)
+//   backward   dz = gv (z > 0 ? 1 : 0.2);  (sum dz, sum dz xhat), xhat = (y - mean) rstd   rpb_rowbn_act_bwd_stats -> fp64 partials
+//              fixed-order sum of the partials              rpb_rowbn_sum64
+//              dy = a (dz - dbeta / M - xhat dgamma / M);  dgamma, dbeta              rpb_rowbn_act_bwd_apply (fp32 rows and / or bf16 planes)
 //
 // Every kernel is grid-stride with 16-byte accesses, uses no atomics and sums in a fixed order: two calls are bit-equal.  Every pointer
 // arrives at the first column the launch owns, with a leading dimension (producers own column ranges of shared buffers).  The gate of the
 // backward pass is recomputed from fmaf(y, a, b) -- the expression the forward pass evaluates -- so no mask is stored.
-#include "rpb_mma.h"
-#include <stdint.h>
-
-#define CT_THREADS 256
+#include "rpb_rowbn.h"
 
 __device__ __forceinline__ float ct_lrelu(float z) { return z > 0.f ? z : 0.2f * z; }
 
@@ -37,10 +32,10 @@ struct CtStatArgs {
 };
 
 template <int MODE>
-__global__ __launch_bounds__(CT_THREADS) void ct_stats_kernel(CtStatArgs p) {
-    __shared__ double red[CT_THREADS * 8];                              // [nsub][2 C] = 256 / (C / 4) * 2 C doubles = 16 KB
+__global__ __launch_bounds__(ROWBN_THREADS) void ct_stats_kernel(CtStatArgs p) {
+    __shared__ double red[ROWBN_THREADS * 8];                           // [nsub][2 C] = 256 / (C / 4) * 2 C doubles = 16 KB
     const int c4n = p.C >> 2;
-    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = CT_THREADS / c4n;
+    const int c4 = threadIdx.x % c4n, sub = threadIdx.x / c4n, nsub = ROWBN_THREADS / c4n;
     const int c0 = 4 * c4;
     double s0[4] = {0., 0., 0., 0.}, s1[4] = {0., 0., 0., 0.};
     f32x4 a4, b4;
@@ -74,42 +69,28 @@ __global__ __launch_bounds__(CT_THREADS) void ct_stats_kernel(CtStatArgs p) {
             }
         }
     }
-    double* mine = red + (long)sub * 2 * p.C;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        mine[c0 + i] = s0[i];
-        mine[p.C + c0 + i] = s1[i];
-    }
-    __syncthreads();
-    for (int n = threadIdx.x; n < 2 * p.C; n += CT_THREADS) {
-        double s = 0.;
-        for (int k = 0; k < nsub; ++k) s += red[(long)k * 2 * p.C + n];
-        p.part[(long)blockIdx.x * 2 * p.C + n] = s;
-    }
+    rowbn_block_sums<2>(red, s0, s1, p.C, c0, sub, nsub, p.part);
 }
 
-static bool ct_chan_ok(int C) { return C == 16 || C == 32 || C == 64 || C == 128; }
-static bool ct_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+extern "C" int rpb_rowbn_rows(void) { return rowbn_rows(); }
 
-extern "C" int rpb_cno_bn_rows(void) { return rpb_num_cus() * 4; }
-
-extern "C" int rpb_cno_bn_stats(const float* y, int ld, long M, int C, double* part, void* stream) {
-    RPB_REQUIRE(y && part && M > 0 && M < (1L << 31) && ct_chan_ok(C) && ld >= C && ld % 4 == 0 && ct_al16(y),
-                "cno_bn_stats: bad arguments (M=%ld C=%d ld=%d; C in {16, 32, 64, 128}, ld %% 4 == 0, y 16-byte aligned)", M, C, ld);
+extern "C" int rpb_rowbn_stats(const float* y, int ld, long M, int C, double* part, void* stream) {
+    RPB_REQUIRE(y && part && M > 0 && M < (1L << 31) && rowbn_chan_ok(C, 16, 128) && ld >= C && ld % 4 == 0 && rowbn_al16(y),
+                "rowbn_stats: bad arguments (M=%ld C=%d ld=%d; C in {16, 32, 64, 128}, ld %% 4 == 0, y 16-byte aligned)", M, C, ld);
     CtStatArgs p{y, nullptr, nullptr, nullptr, nullptr, nullptr, part, M, C, ld, 0, 0};
-    hipLaunchKernelGGL(ct_stats_kernel<0>, dim3(rpb_cno_bn_rows()), dim3(CT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("cno_bn_stats");
+    hipLaunchKernelGGL(ct_stats_kernel<0>, dim3(rowbn_rows()), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_stats");
 }
 
-extern "C" int rpb_cno_bn_act_bwd_stats(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
-                                        const float* rstd, long M, int C, int act, double* part, void* stream) {
-    RPB_REQUIRE(gv && y && a && b && mean && rstd && part && M > 0 && M < (1L << 31) && ct_chan_ok(C) && (act == 0 || act == 1),
-                "cno_bn_act_bwd_stats: bad arguments (M=%ld C=%d act=%d; C in {16, 32, 64, 128})", M, C, act);
-    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && ldy >= C && ldy % 4 == 0 && ct_al16(gv) && ct_al16(y) && ct_al16(a) && ct_al16(b),
-                "cno_bn_act_bwd_stats: ldg=%d ldy=%d must be >= C and %% 4 == 0, gv / y / a / b 16-byte aligned", ldg, ldy);
+extern "C" int rpb_rowbn_act_bwd_stats(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                                       const float* rstd, long M, int C, int act, double* part, void* stream) {
+    RPB_REQUIRE(gv && y && a && b && mean && rstd && part && M > 0 && M < (1L << 31) && rowbn_chan_ok(C, 16, 128) && (act == 0 || act == 1),
+                "rowbn_act_bwd_stats: bad arguments (M=%ld C=%d act=%d; C in {16, 32, 64, 128})", M, C, act);
+    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && ldy >= C && ldy % 4 == 0 && rowbn_al16(gv) && rowbn_al16(y) && rowbn_al16(a) && rowbn_al16(b),
+                "rowbn_act_bwd_stats: ldg=%d ldy=%d must be >= C and %% 4 == 0, gv / y / a / b 16-byte aligned", ldg, ldy);
     CtStatArgs p{y, gv, a, b, mean, rstd, part, M, C, ldy, ldg, act};
-    hipLaunchKernelGGL(ct_stats_kernel<1>, dim3(rpb_cno_bn_rows()), dim3(CT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("cno_bn_act_bwd_stats");
+    hipLaunchKernelGGL(ct_stats_kernel<1>, dim3(rowbn_rows()), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_act_bwd_stats");
 }
 
 // ---------------------------------------------------------------------------------- the partials' fixed-order sum, and the statistics
@@ -126,7 +107,7 @@ struct CtFinArgs {
 };
 
 template <bool FINISH>
-__global__ __launch_bounds__(CT_THREADS) void ct_sum_kernel(CtFinArgs p) {
+__global__ __launch_bounds__(ROWBN_THREADS) void ct_sum_kernel(CtFinArgs p) {
     __shared__ double red[8][32];
     const int ch = threadIdx.x & 15, st = (threadIdx.x >> 4) & 1, g = threadIdx.x >> 5;
     const int c = blockIdx.x * 16 + ch;
@@ -159,27 +140,27 @@ __global__ __launch_bounds__(CT_THREADS) void ct_sum_kernel(CtFinArgs p) {
     p.rvar[c] = (float)((1.0 - p.momentum) * (double)p.rvar[c] + p.momentum * var * (n / (n - 1.0)));
 }
 
-extern "C" int rpb_cno_bn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
-                                 float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd,
-                                 void* stream) {
-    RPB_REQUIRE(part && gamma && beta && running_mean && running_var && a && b && mean && rstd && rows > 0 && M > 1 && ct_chan_ok(C) &&
+extern "C" int rpb_rowbn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
+                                float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd,
+                                void* stream) {
+    RPB_REQUIRE(part && gamma && beta && running_mean && running_var && a && b && mean && rstd && rows > 0 && M > 1 && rowbn_chan_ok(C, 16, 128) &&
                     eps > 0. && momentum >= 0. && momentum <= 1.,
-                "cno_bn_finish: bad arguments (rows=%d M=%ld C=%d; M > 1, C in {16, 32, 64, 128})", rows, M, C);
+                "rowbn_finish: bad arguments (rows=%d M=%ld C=%d; M > 1, C in {16, 32, 64, 128})", rows, M, C);
     CtFinArgs p{part, nullptr, gamma, beta, running_mean, running_var, a, b, mean, rstd, M, rows, C, eps, momentum};
-    hipLaunchKernelGGL(ct_sum_kernel<true>, dim3(C / 16), dim3(CT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("cno_bn_finish");
+    hipLaunchKernelGGL(ct_sum_kernel<true>, dim3(C / 16), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_finish");
 }
 
-extern "C" int rpb_cno_sum64(const double* part, int rows, int C, double* sums, void* stream) {
-    RPB_REQUIRE(part && sums && rows > 0 && ct_chan_ok(C), "cno_sum64: bad arguments (rows=%d C=%d; C in {16, 32, 64, 128})", rows, C);
+extern "C" int rpb_rowbn_sum64(const double* part, int rows, int C, double* sums, void* stream) {
+    RPB_REQUIRE(part && sums && rows > 0 && rowbn_chan_ok(C, 16, 256), "rowbn_sum64: bad arguments (rows=%d C=%d; C in {16, 32, 64, 128, 256})", rows, C);
     CtFinArgs p{part, sums, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, rows, C, 0., 0.};
-    hipLaunchKernelGGL(ct_sum_kernel<false>, dim3(C / 16), dim3(CT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("cno_sum64");
+    hipLaunchKernelGGL(ct_sum_kernel<false>, dim3(C / 16), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_sum64");
 }
 
 // ---------------------------------------------------------------------------------- forward apply
 // v = fmaf(y, a, b); LeakyReLU; + res.  One thread = 8 channels of one token (2 x 16 B in, 2 x 16 B fp32 and 3 x 16 B bf16 out).
-__global__ __launch_bounds__(CT_THREADS) void ct_act_fwd_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ a,
+__global__ __launch_bounds__(ROWBN_THREADS) void ct_act_fwd_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ a,
                                                                 const float* __restrict__ b, const float* res, int ldr, float* out,
                                                                 int ldo, uint16_t* op, int ldp, long M, int C, int act) {
     const int c8n = C >> 3;
@@ -212,30 +193,26 @@ __global__ __launch_bounds__(CT_THREADS) void ct_act_fwd_kernel(const float* __r
     }
 }
 
-static unsigned ct_grid(long total) {
-    long grid = (total + CT_THREADS - 1) / CT_THREADS;
-    const long cap = (long)rpb_num_cus() * 16;
-    return (unsigned)(grid > cap ? cap : grid);
-}
-
-extern "C" int rpb_cno_bn_act_fwd(const float* y, int ldy, const float* a, const float* b, const float* res, int ldr, float* out, int ldo,
-                                  void* out_planes, int ldp, long M, int C, int act, void* stream) {
-    RPB_REQUIRE(y && a && b && (out || out_planes) && M > 0 && M < (1L << 31) && ct_chan_ok(C) && (act == 0 || act == 1),
-                "cno_bn_act_fwd: bad arguments (M=%ld C=%d act=%d; C in {16, 32, 64, 128})", M, C, act);
-    RPB_REQUIRE(ldy >= C && ldy % 4 == 0 && ct_al16(y) && ct_al16(a) && ct_al16(b), "cno_bn_act_fwd: ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", ldy);
-    RPB_REQUIRE(!res || (ldr >= C && ldr % 4 == 0 && ct_al16(res)), "cno_bn_act_fwd: ldr=%d (>= C, %% 4 == 0, 16-byte aligned)", ldr);
-    RPB_REQUIRE(!out || (ldo >= C && ldo % 4 == 0 && ct_al16(out)), "cno_bn_act_fwd: ldo=%d (>= C, %% 4 == 0, 16-byte aligned)", ldo);
-    RPB_REQUIRE(!out_planes || (ldp >= C && ldp % 8 == 0 && ct_al16(out_planes)),
-                "cno_bn_act_fwd: plane output needs a 16-byte aligned first column and ldp %% 8 == 0 (ldp=%d)", ldp);
-    hipLaunchKernelGGL(ct_act_fwd_kernel, dim3(ct_grid(M * (C / 8))), dim3(CT_THREADS), 0, (hipStream_t)stream, y, ldy, a, b, res, ldr, out,
+extern "C" int rpb_rowbn_act_fwd(const float* y, int ldy, const float* a, const float* b, const float* res, int ldr, float* out, int ldo,
+                                 void* out_planes, int ldp, long M, int C, int act, void* stream) {
+    RPB_REQUIRE(y && a && b && (out || out_planes) && M > 0 && M < (1L << 31) && rowbn_chan_ok(C, 16, 128) && (act == 0 || act == 1),
+                "rowbn_act_fwd: bad arguments (M=%ld C=%d act=%d; C in {16, 32, 64, 128})", M, C, act);
+    RPB_REQUIRE(ldy >= C && ldy % 4 == 0 && rowbn_al16(y) && rowbn_al16(a) && rowbn_al16(b), "rowbn_act_fwd: ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", ldy);
+    RPB_REQUIRE(!res || (ldr >= C && ldr % 4 == 0 && rowbn_al16(res)), "rowbn_act_fwd: ldr=%d (>= C, %% 4 == 0, 16-byte aligned)", ldr);
+    RPB_REQUIRE(!out || (ldo >= C && ldo % 4 == 0 && rowbn_al16(out)), "rowbn_act_fwd: ldo=%d (>= C, %% 4 == 0, 16-byte aligned)", ldo);
+    RPB_REQUIRE(!out_planes || (ldp >= C && ldp % 8 == 0 && rowbn_al16(out_planes)),
+                "rowbn_act_fwd: plane output needs a 16-byte aligned first column and ldp %% 8 == 0 (ldp=%d)", ldp);
+    hipLaunchKernelGGL(ct_act_fwd_kernel, dim3(rowbn_grid(M * (C / 8))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, y, ldy, a, b, res, ldr, out,
                        ldo, (uint16_t*)out_planes, ldp, M, C, act);
-    RPB_CHECK_LAUNCH("cno_bn_act_fwd");
+    RPB_CHECK_LAUNCH("rowbn_act_fwd");
 }
 
 // ---------------------------------------------------------------------------------- backward apply
 // has_bn:  dy = a (dz - dbeta / M - xhat dgamma / M),  dz = gv or 0.2 gv by the sign of fmaf(y, a, b)
 // else:    dy = dz, the gate from the sign of `y` itself (the saved LeakyReLU output, or conv + bias: same sign)
-// Columns C..Cpad-1 of the rows and planes are written as zero (the 64-wide operands of the narrow layers).
+// Columns C..Cpad-1 of the rows and planes are written as zero (the 64-wide operands of the narrow layers).  One thread = RUN channels
+// of one row: 8 (what a 16 B plane store takes) when Cpad % 8 == 0, else 4 (rows only); the expression per element is the same.  dy may
+// be gv itself (same address, ldd == ldg): a thread reads all its elements of a row before it writes them.
 struct CtBwdArgs {
     const float *gv, *y, *a, *b, *mean, *rstd;
     const double* sums;    // [2 C]: (sum dz, sum dz xhat)
@@ -246,23 +223,24 @@ struct CtBwdArgs {
     int C, Cpad, ldg, ldy, ldd, ldp, act, has_bn;
 };
 
-__global__ __launch_bounds__(CT_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) {
-    const int c8n = p.Cpad >> 3;
-    const long total = p.M * c8n, pstride = p.M * (long)p.ldp;
+template <int RUN>
+__global__ __launch_bounds__(ROWBN_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) {
+    const int runs = p.Cpad / RUN;
+    const long total = p.M * runs, pstride = p.M * (long)p.ldp;
     if (p.has_bn && p.dgamma && blockIdx.x == 0)
-        for (int c = threadIdx.x; c < p.C; c += CT_THREADS) {
+        for (int c = threadIdx.x; c < p.C; c += ROWBN_THREADS) {
             p.dbeta[c] = (float)p.sums[c];
             p.dgamma[c] = (float)p.sums[p.C + c];
         }
     const double inv_m = 1.0 / (double)p.M;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long m = idx / c8n;
-        const int c0 = (int)(idx - m * c8n) * 8;
+        const long m = idx / runs;
+        const int c0 = (int)(idx - m * runs) * RUN;
         f32x4 d[2] = {z4, z4};
-        if (c0 < p.C) {                                                 // C % 8 == 0: a run of 8 is inside or outside
+        if (c0 < p.C) {                                                 // C % 16 == 0, RUN <= 8: a run is inside C or outside
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < RUN / 4; ++h) {
                 const int c = c0 + 4 * h;
                 const f32x4 g4 = RPB_SLD4(p.gv + m * p.ldg + c);
                 f32x4 y4 = z4;
@@ -286,27 +264,30 @@ __global__ __launch_bounds__(CT_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) {
         }
         if (p.dy) {
             *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c0) = d[0];
-            *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c0 + 4) = d[1];
+            if (RUN == 8) *reinterpret_cast<f32x4*>(p.dy + m * p.ldd + c0 + 4) = d[1];
         }
-        if (p.dp) split3_store(p.dp, m * p.ldp + c0, pstride, d[0], d[1]);
+        if (RUN == 8 && p.dp) split3_store(p.dp, m * p.ldp + c0, pstride, d[0], d[1]);
     }
 }
 
-extern "C" int rpb_cno_bn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
-                                        const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy,
-                                        int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream) {
-    RPB_REQUIRE(gv && (dy || dy_planes) && M > 0 && M < (1L << 31) && ct_chan_ok(C) && Cpad >= C && Cpad % 8 == 0 && (act == 0 || act == 1) &&
+extern "C" int rpb_rowbn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                                       const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy,
+                                       int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream) {
+    RPB_REQUIRE(gv && (dy || dy_planes) && M > 0 && M < (1L << 31) && rowbn_chan_ok(C, 16, 256) && Cpad >= C && Cpad % 4 == 0 && (act == 0 || act == 1) &&
                     (has_bn == 0 || has_bn == 1),
-                "cno_bn_act_bwd_apply: bad arguments (M=%ld C=%d Cpad=%d act=%d has_bn=%d; C in {16, 32, 64, 128}, Cpad >= C, Cpad %% 8 == 0)",
+                "rowbn_act_bwd_apply: bad arguments (M=%ld C=%d Cpad=%d act=%d has_bn=%d; C in {16, 32, 64, 128, 256}, Cpad >= C, Cpad %% 4 == 0)",
                 M, C, Cpad, act, has_bn);
-    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && ct_al16(gv), "cno_bn_act_bwd_apply: ldg=%d (>= C, %% 4 == 0, gv 16-byte aligned)", ldg);
-    RPB_REQUIRE(!(has_bn || act) || (y && ldy >= C && ldy % 4 == 0 && ct_al16(y)), "cno_bn_act_bwd_apply: y / ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", ldy);
-    RPB_REQUIRE(!has_bn || (a && b && mean && rstd && sums && ct_al16(a) && ct_al16(b) && ct_al16(mean) && ct_al16(rstd) && (!dgamma == !dbeta)),
-                "cno_bn_act_bwd_apply: has_bn needs a, b, mean, rstd (16-byte aligned) and sums; dgamma and dbeta come together");
-    RPB_REQUIRE(!dy || (ldd >= Cpad && ldd % 4 == 0 && ct_al16(dy)), "cno_bn_act_bwd_apply: ldd=%d (>= Cpad, %% 4 == 0, dy 16-byte aligned)", ldd);
-    RPB_REQUIRE(!dy_planes || (ldp >= Cpad && ldp % 8 == 0 && ct_al16(dy_planes)),
-                "cno_bn_act_bwd_apply: plane output needs a 16-byte aligned first column and ldp %% 8 == 0 (ldp=%d)", ldp);
+    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && rowbn_al16(gv), "rowbn_act_bwd_apply: ldg=%d (>= C, %% 4 == 0, gv 16-byte aligned)", ldg);
+    RPB_REQUIRE(!(has_bn || act) || (y && ldy >= C && ldy % 4 == 0 && rowbn_al16(y)), "rowbn_act_bwd_apply: y / ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", ldy);
+    RPB_REQUIRE(!has_bn || (a && b && mean && rstd && sums && rowbn_al16(a) && rowbn_al16(b) && rowbn_al16(mean) && rowbn_al16(rstd) && (!dgamma == !dbeta)),
+                "rowbn_act_bwd_apply: has_bn needs a, b, mean, rstd (16-byte aligned) and sums; dgamma and dbeta come together");
+    RPB_REQUIRE(!dy || (ldd >= Cpad && ldd % 4 == 0 && rowbn_al16(dy)), "rowbn_act_bwd_apply: ldd=%d (>= Cpad, %% 4 == 0, dy 16-byte aligned)", ldd);
+    RPB_REQUIRE(!dy_planes || (Cpad % 8 == 0 && ldp >= Cpad && ldp % 8 == 0 && rowbn_al16(dy_planes)),
+                "rowbn_act_bwd_apply: plane output needs a 16-byte aligned first column, Cpad %% 8 == 0 and ldp %% 8 == 0 (Cpad=%d ldp=%d)", Cpad, ldp);
     CtBwdArgs p{gv, y, a, b, mean, rstd, sums, dy, (uint16_t*)dy_planes, dgamma, dbeta, M, C, Cpad, ldg, ldy, ldd, ldp, act, has_bn};
-    hipLaunchKernelGGL(ct_act_bwd_kernel, dim3(ct_grid(M * (Cpad / 8))), dim3(CT_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("cno_bn_act_bwd_apply");
+    if (Cpad % 8 == 0)
+        hipLaunchKernelGGL(ct_act_bwd_kernel<8>, dim3(rowbn_grid(M * (Cpad / 8))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(ct_act_bwd_kernel<4>, dim3(rowbn_grid(M * (Cpad / 4))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_act_bwd_apply");
 }

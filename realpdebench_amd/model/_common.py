@@ -1,5 +1,6 @@
 """Plumbing the models share between their parameter trees and the C ABI: the autograd glue (``HipFunction``), the weight-gradient
-finish (``wgrad``, ``colsum``, ``sum_rows``), the weight matrix of a padded 3x3x3 convolution (``padded_weight``), the cache of
+finish (``wgrad``, ``colsum``, ``sum_rows``), the weight matrices of a padded 3x3x3 convolution and of its data gradient (``padded_weight``,
+``flipped_weight``, ``weight_grad_view``), batch-statistics BatchNorm on rows (``batch_norm_rows``, ``batch_norm_rows_bwd``), the cache of
 kernel-side layouts (``LayoutCache``) and the base of the models that evaluate by default and train by opt-in (``EvalByDefault``: MWT3d,
 DeepONet, CNO3d)."""
 import torch
@@ -93,6 +94,56 @@ def padded_weight(conv, N, K):
     wm = torch.zeros(N, 27, K, dtype=torch.float32, device=w.device)
     wm[:Co, :, :Ci] = w.permute(0, 2, 3, 4, 1).reshape(Co, 27, Ci)
     return wm.reshape(N, 27 * K)
+
+
+def flipped_weight(conv, N, K):
+    """Data-gradient weights of a Conv3d(Ci, Co, 3, padding=1): the same convolution run from the Co side with flipped, transposed taps,
+    Wd[ci][(kt, kh, kw)][co] = W[co][ci][2 - kt][2 - kh][2 - kw] -> [K][27 * N] fp32 (K >= Ci output rows, N >= Co input channels, zero on
+    the pad channels): what ``padded_weight`` is to the forward convolution."""
+    w = conv.weight.detach()
+    Co, Ci = w.shape[:2]
+    wd = torch.zeros(K, 27, N, dtype=torch.float32, device=w.device)
+    wd[:Ci, :, :Co] = w.flip(2, 3, 4).permute(1, 2, 3, 4, 0).reshape(Ci, 27, Co)
+    return wd.reshape(K, 27 * N)
+
+
+def weight_grad_view(dW, Co, Ci, N, K):
+    """dW [N][27 * K] (tap-major rows, the layout of ``padded_weight``) -> the parameter's [Co][Ci][3][3][3]."""
+    return dW.view(N, 3, 3, 3, K)[:Co, :, :, :, :Ci].permute(0, 4, 1, 2, 3).contiguous()
+
+
+def batch_norm_rows(y, ld, M, C, bn, parts=None):
+    """Batch statistics of y [M][ld] (csrc/rpb_rowbn.hip) -> ab [4][C] = (a, b, mean, rstd), a = gamma rstd, b = beta - mean a; the running
+    statistics of ``bn`` are updated on the device (``num_batches_tracked`` is the caller's).  C = 256 runs as two column halves.
+    ``parts``: fp64 partials already accumulated (a forward in chunks of samples), [2 if C == 256 else 1][rows][2 Ch].
+    M < 2 raises torch's ValueError before anything is launched (CNO3d cannot get there: its input has T > in_dim >= 1, so M >= 2); the
+    version counters of the running statistics are bumped here, once per call."""
+    if M < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size [{M} cells, {C} channels]")
+    Ch, nh = min(C, 128), max(1, C // 128)
+    if parts is None:
+        parts = torch.empty(nh, ops.rowbn_rows(), 2 * Ch, device=y.device, dtype=torch.float64)
+        for h in range(nh):
+            ops.rowbn_stats(ops.Sub(y, h * Ch), ld, M, Ch, parts[h])
+    ab = torch.empty(4, C, device=y.device, dtype=torch.float32)
+    for h in range(nh):
+        o = h * Ch
+        ops.rowbn_finish(parts[h], parts.shape[1], M, Ch, ops.Sub(bn.weight.data, o), ops.Sub(bn.bias.data, o), ops.Sub(bn.running_mean, o),
+                         ops.Sub(bn.running_var, o), bn.eps, bn.momentum, *(ops.Sub(ab, k * C + o) for k in range(4)))
+    torch.autograd.graph.increment_version(bn.running_mean)           # written through raw pointers: the layout cache is keyed on these
+    torch.autograd.graph.increment_version(bn.running_var)
+    return ab
+
+
+def batch_norm_rows_bwd(part, gv, ldg, y, ldy, ab, M, C, Cpad, act, dy, ldd, dy_planes=None, ldp=0):
+    """The tail of a BatchNorm backward, from the fp64 partials ``part`` [rows][2 C] of (sum dz, sum dz xhat): their fixed-order sum, then
+    dy = a (dz - sum dz / M - xhat sum dz xhat / M) as fp32 rows (``dy`` may be ``gv``) and bf16 planes.  Returns (dgamma, dbeta)."""
+    sums = torch.empty(2 * C, device=part.device, dtype=torch.float64)
+    dgb = torch.empty(2, C, device=part.device, dtype=torch.float32)
+    ops.rowbn_sum64(part, part.shape[0], C, sums)
+    ops.rowbn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=y, ldy=ldy, a=ab[0], b=ab[1], mean=ab[2], rstd=ab[3], sums=sums, dy=dy, ldd=ldd,
+                            dy_planes=dy_planes, ldp=ldp, dgamma=dgb[0], dbeta=dgb[1])
+    return dgb[0], dgb[1]
 
 
 class LayoutCache:

@@ -9,7 +9,7 @@ Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and ch
 every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``), ``trainer.make_trainer`` refuses the model at
 construction and BatchNorm3d uses its running statistics in every mode.  ``enable_training()`` (``hip_training: true`` through
 ``load_model``) opts an instance in: in ``train()`` mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction`` with
-batch-statistics BatchNorm (csrc/rpb_cno_train.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
+batch-statistics BatchNorm (csrc/rpb_rowbn.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
 implicit GEMM for the seven ``EXACT_DGRAD`` layers) and the weight gradient is ``_common.wgrad``; ``eval()`` mode stays the code below,
 untouched.
 
@@ -41,9 +41,10 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..ops import Sub, _p, _stream, amax_exp_finish, conv3_f16x2_weights, conv3x_wprep, gemm_nt, split2h, split3
+from .. import ops
+from ..ops import Sub, _p, _ptr, _stream, amax_exp_finish, conv3_f16x2_weights, conv3x_wprep, gemm_nt, split2h, split3
 from ..ops import add as ops_add
-from ._common import EvalByDefault, padded_weight, wgrad
+from ._common import EvalByDefault, batch_norm_rows, batch_norm_rows_bwd, flipped_weight, padded_weight, weight_grad_view, wgrad
 from .model import Model
 
 I16 = torch.int16
@@ -174,22 +175,6 @@ def fold_affine(conv, bn, N):
     return sc, sh
 
 
-def flipped_weight(conv, N, K):
-    """Data-gradient weights of a Conv3d(Ci, Co, 3, padding=1): the same convolution run from the Co side with flipped, transposed taps,
-    Wd[ci][(kt, kh, kw)][co] = W[co][ci][2 - kt][2 - kh][2 - kw] -> [K][27 * N] fp32 (K >= Ci output rows, N >= Co input channels, zero on
-    the pad channels): what ``padded_weight`` is to the forward convolution."""
-    w = conv.weight.detach()
-    Co, Ci = w.shape[:2]
-    wd = torch.zeros(K, 27, N, dtype=torch.float32, device=w.device)
-    wd[:Ci, :, :Co] = w.flip(2, 3, 4).permute(1, 2, 3, 4, 0).reshape(Ci, 27, Co)
-    return wd.reshape(K, 27 * N)
-
-
-def weight_grad_view(dW, Co, Ci, N, K):
-    """dW [N][27 * K] (tap-major rows, the layout of ``padded_weight``) -> the parameter's [Co][Ci][3][3][3]."""
-    return dW.view(N, 3, 3, 3, K)[:Co, :, :, :, :Ci].permute(0, 4, 1, 2, 3).contiguous()
-
-
 class _Planes:
     """bf16 plane buffer P[3][M][ld] (int16 bit patterns).  ``zero``: the producers leave columns unwritten that a convolution reads."""
 
@@ -235,13 +220,6 @@ class _ActH:
         split2h(self.rows, self.planes, self.M, self.ld, self.word)
         self.ready = True
         return self
-
-
-def _ptr(t, dtype=torch.float32):
-    """address of a tensor of ``dtype``, of an ``ops.Sub`` (a block of an fp32 allocation, whatever it holds), or the address itself"""
-    if t is None or isinstance(t, int):
-        return t
-    return _p(t) if isinstance(t, Sub) else _p(t, dtype)
 
 
 def _iptr(t):
@@ -392,45 +370,6 @@ class CNO3d(EvalByDefault, Model):
                   nvalid, int(act), ldr, ldo, *mesh, _iptr(ea), _iptr(ew), _stream(), label=f"cno_conv3x_f16x2[N{N},Ci{Ci}]",
                   nbytes=4 * M * Ci + 4 * M * nvalid + (4 * M * nvalid if res is not None else 0), flops=2 * M * N * 27 * Ci)
 
-    # the row passes of the training step (csrc/rpb_cno_train.hip); row operands: fp32 tensors, ``ops.Sub`` or raw addresses at the first column
-    @staticmethod
-    def k_bn_rows():
-        return _lib.query("rpb_cno_bn_rows")
-
-    @staticmethod
-    def k_bn_stats(y, ld, M, C, part):
-        _lib.call("rpb_cno_bn_stats", _ptr(y), ld, M, C, _ptr(part, torch.float64), _stream(), label="cno_bn_stats", nbytes=4 * M * C)
-
-    @staticmethod
-    def k_bn_finish(part, rows, M, C, gamma, beta, rmean, rvar, eps, momentum, a, b, mean, rstd):
-        _lib.call("rpb_cno_bn_finish", _ptr(part, torch.float64), rows, M, C, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
-                  float(momentum), _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _stream(), label="cno_bn_finish", nbytes=16 * rows * C)
-
-    @staticmethod
-    def k_bn_act_fwd(y, ldy, a, b, M, C, act, res=None, ldr=0, out=None, ldo=0, out_planes=None, ldp=0):
-        _lib.call("rpb_cno_bn_act_fwd", _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(res), ldr, _ptr(out), ldo, _ptr(out_planes, I16), ldp, M, C,
-                  int(act), _stream(), label="cno_bn_act_fwd",
-                  nbytes=M * C * (4 + (4 if res is not None else 0) + (4 if out is not None else 0) + (6 if out_planes is not None else 0)))
-
-    @staticmethod
-    def k_bn_act_bwd_stats(gv, ldg, y, ldy, a, b, mean, rstd, M, C, act, part):
-        _lib.call("rpb_cno_bn_act_bwd_stats", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), M, C, int(act),
-                  _ptr(part, torch.float64), _stream(), label="cno_bn_act_bwd_stats", nbytes=8 * M * C)
-
-    @staticmethod
-    def k_sum64(part, rows, C, sums):
-        _lib.call("rpb_cno_sum64", _ptr(part, torch.float64), rows, C, _ptr(sums, torch.float64), _stream(), label="cno_sum64",
-                  nbytes=16 * rows * C)
-
-    @staticmethod
-    def k_bn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=None, ldy=0, a=None, b=None, mean=None, rstd=None, sums=None, dy=None, ldd=0,
-                           dy_planes=None, ldp=0, dgamma=None, dbeta=None):
-        """``sums`` given: the BatchNorm form; otherwise the gate-only form (``y``: the saved LeakyReLU output)."""
-        _lib.call("rpb_cno_bn_act_bwd_apply", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(sums, torch.float64),
-                  M, C, Cpad, int(act), int(sums is not None), _ptr(dy), ldd, _ptr(dy_planes, I16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(),
-                  label="cno_bn_act_bwd_apply",
-                  nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))
-
     # ------------------------------------------------------------------ the training step
     def _train_rows(self, x, mesh, state):
         """x [M][in_dim] fp32 -> [M][out_dim] fp32 with batch-statistics BatchNorm (the running statistics are updated): the schedule on
@@ -438,8 +377,8 @@ class CNO3d(EvalByDefault, Model):
         statistics and one row pass that writes fp32 rows and planes of ``v``.  ``state`` (a dict, or None) receives the tape the
         backward pass walks: per layer the buffers it read and wrote, ``y`` and (a, b, mean, rstd)."""
         dev, M, S = x.device, x.shape[0], self.schedule
-        prep, convs, rows = self._prep_train(dev), self._convs(), self.k_bn_rows()
-        tape, touched, counters = [], [], []
+        prep, convs = self._prep_train(dev), self._convs()
+        tape, counters = [], []
         acts = {0: _Act(M, S.bufs[0].ld, dev, S.bufs[0].zero)}        # the input: rows zeroed and filled, the pack kernel writes the planes
         acts[0].rows[:, :self.in_dim] = x
         self.k_pack(x, acts[0].planes.t, M, self.in_dim)
@@ -463,18 +402,11 @@ class CNO3d(EvalByDefault, Model):
                 continue
             y = torch.empty(M, N, device=dev, dtype=torch.float32)
             self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, N, 0, out=y, ldo=N)
-            part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
-            ab = torch.empty(4, Co, device=dev, dtype=torch.float32)  # a, b, mean, rstd
-            self.k_bn_stats(y, N, M, Co, part)
-            self.k_bn_finish(part, rows, M, Co, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, *ab)
-            self.k_bn_act_fwd(y, N, ab[0], ab[1], M, Co, act, res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
+            ab = batch_norm_rows(y, N, M, Co, bn)                     # a, b, mean, rstd
+            ops.rowbn_act_fwd(y, N, ab[0], ab[1], M, Co, act, res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
                               out=dst.at(col), ldo=dst.ld, out_planes=dst.planes.ptr(col), ldp=dst.ld)
             rec["y"], rec["ab"] = y, ab
-            touched.extend((bn.running_mean, bn.running_var))
             counters.append(bn.num_batches_tracked)
-        # the kernels wrote the running statistics through raw pointers: the layout cache is keyed on the version counters
-        for t in touched:
-            torch.autograd.graph.increment_version(t)
         torch._foreach_add_(counters, 1)
         if state is not None:
             for rec in tape:                                          # the backward pass reads fp32 rows only
@@ -500,7 +432,7 @@ class CNO3d(EvalByDefault, Model):
             raise NotImplementedError("CNO3d training computes no input gradient (no trainer asks for one)")
         tape, M, mesh = state["tape"], state["M"], state["mesh"]
         dev = g_out.device
-        prep, convs, rows = self._prep_train(dev), self._convs(), self.k_bn_rows()
+        prep, convs, rows = self._prep_train(dev), self._convs(), ops.rowbn_rows()
         g, grads = {}, {}                                             # id(_Act) -> fp32 [M][ld] gradient of that buffer
         gpad = torch.zeros(M, 64, device=dev, dtype=torch.float32)
         gpad[:, :self.out_dim] = g_out.reshape(M, self.out_dim)
@@ -516,19 +448,14 @@ class CNO3d(EvalByDefault, Model):
             need_dx, exact = s["wd"] is not None, name in EXACT_DGRAD
             dyp = torch.empty(3 * M * N, device=dev, dtype=I16) if need_dx and not exact else None
             if bn is not False:
-                y, (a, b, mean, rstd) = rec["y"], rec["ab"]
+                y, ab = rec["y"], rec["ab"]
                 part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
-                sums = torch.empty(2 * Co, device=dev, dtype=torch.float64)
-                dgb = torch.empty(2, Co, device=dev, dtype=torch.float32)
                 dy = torch.empty(M, N, device=dev, dtype=torch.float32)
-                self.k_bn_act_bwd_stats(gv, ldg, y, N, a, b, mean, rstd, M, Co, act, part)
-                self.k_sum64(part, rows, Co, sums)
-                self.k_bn_act_bwd_apply(gv, ldg, M, Co, N, act, y=y, ldy=N, a=a, b=b, mean=mean, rstd=rstd, sums=sums, dy=dy, ldd=N,
-                                        dy_planes=dyp, ldp=N, dgamma=dgb[0], dbeta=dgb[1])
-                grads[bn.weight], grads[bn.bias] = dgb[0], dgb[1]
+                ops.rowbn_act_bwd_stats(gv, ldg, y, N, *ab, M, Co, act, part)
+                grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part, gv, ldg, y, N, ab, M, Co, N, act, dy, N, dy_planes=dyp, ldp=N)
             elif act:                                                 # lift.0 / project.0: the gate from the sign of the saved v
                 dy = torch.empty(M, N, device=dev, dtype=torch.float32)
-                self.k_bn_act_bwd_apply(gv, ldg, M, Co, N, 1, y=dst.rows, ldy=dst.ld, dy=dy, ldd=N, dy_planes=dyp, ldp=N)
+                ops.rowbn_act_bwd_apply(gv, ldg, M, Co, N, 1, y=dst.rows, ldy=dst.ld, dy=dy, ldd=N, dy_planes=dyp, ldp=N)
             else:                                                     # lift.1 / project.1: dy = gv, a 64-wide buffer with zero pad columns
                 assert col == 0 and ldg == N, name
                 dy = gt

@@ -6,7 +6,8 @@ every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByD
 ``trainer.make_trainer`` refuses the model at construction, dropout is the identity and BatchNorm3d uses its running statistics in
 every mode.  ``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
 ``train_loss`` then run through ``_common.HipFunction`` with batch-statistics BatchNorm and active dropout (``_forward_hip`` /
-``_backward_hip`` below, csrc/rpb_deeponet_train.hip); ``eval()`` mode stays the pipeline below, untouched.
+``_backward_hip`` below, csrc/rpb_rowbn.hip and csrc/rpb_deeponet_train.hip); ``eval()`` mode stays the pipeline
+below, untouched.
 
 Pipeline (activations channels-last fp32 rows ``[B * T * H * W][C]``):
   branch  stage 1  rpb_im2col (27 C_in columns, zero-padded to a multiple of 64) + rpb_gemm3x (N = 32 zero-padded to 64)
@@ -31,11 +32,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, ops
 from ..ops import Sub, _p, _stream, amax_exp, conv3_f16x2_weights, conv3x, conv3x_f16x2, conv3x_wprep, reduce_partials, split2h, split3
 from ..ops import add as ops_add
-from ._common import EvalByDefault, padded_weight, wgrad
-from .cno import flipped_weight, weight_grad_view
+from ._common import EvalByDefault, batch_norm_rows, batch_norm_rows_bwd, flipped_weight, padded_weight, weight_grad_view, wgrad
 from .model import Model
 
 I16 = torch.int16
@@ -495,50 +495,12 @@ class DeepONet(EvalByDefault, Model):
                   nbytes=4 * (M * K + M * N) + 6 * N * K, flops=2 * M * N * K)
         return out
 
-    def _bn_batch(self, y, ld, M, C, bn, parts=None):
-        """Batch statistics of y [M][ld] -> ab [4][C] = (a, b, mean, rstd); the running statistics are updated on the device.  ``parts``:
-        fp64 partials already accumulated (stage 1's chunks), [2 if C == 256 else 1][rows][2 Ch]."""
-        if M < 2:
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size [{M} cells, {C} channels]")
-        rows, Ch, nh = _lib.query("rpb_cno_bn_rows"), min(C, 128), max(1, C // 128)
-        if parts is None:
-            parts = torch.empty(nh, rows, 2 * Ch, device=y.device, dtype=torch.float64)
-            for h in range(nh):                                           # C = 256: two column halves
-                self.k_bn_stats(Sub(y, h * Ch), ld, M, Ch, parts[h])
-        ab = torch.empty(4, C, device=y.device, dtype=torch.float32)
-        for h in range(nh):
-            o = h * Ch
-            _lib.call("rpb_cno_bn_finish", _p(parts[h], torch.float64), parts.shape[1], M, Ch, _p(Sub(bn.weight.data, o)), _p(Sub(bn.bias.data, o)),
-                      _p(Sub(bn.running_mean, o)), _p(Sub(bn.running_var, o)), float(bn.eps), float(bn.momentum), _p(Sub(ab, o)),
-                      _p(Sub(ab, C + o)), _p(Sub(ab, 2 * C + o)), _p(Sub(ab, 3 * C + o)), _stream(), label="don_bn_finish",
-                      nbytes=16 * parts.shape[1] * Ch)
-        torch.autograd.graph.increment_version(bn.running_mean)           # written through raw pointers: the layout cache is keyed on these
-        torch.autograd.graph.increment_version(bn.running_var)
-        bn.num_batches_tracked += 1
-        return ab
-
-    @staticmethod
-    def k_bn_stats(y, ld, M, C, part):
-        _lib.call("rpb_cno_bn_stats", _p(y), ld, M, C, _p(part, torch.float64), _stream(), label="don_bn_stats", nbytes=4 * M * C)
-
-    # the row passes of the training step (csrc/rpb_deeponet_train.hip); row operands: fp32 tensors or ``ops.Sub`` at the first column
-    @staticmethod
-    def k_train_rows():
-        return _lib.query("rpb_don_train_rows")
-
+    # the row passes of the training step that are DeepONet's own (csrc/rpb_deeponet_train.hip); row operands: fp32 tensors or ``ops.Sub`` at
+    # the first column
     @staticmethod
     def k_pool_bwd(y, ldy, g, ldg, ab, gz, ldz, B, T, H, W, C, mode, part):
         _lib.call("rpb_don_pool_bwd", _p(y), ldy, _p(g), ldg, _p(ab[0]), _p(ab[1]), _p(ab[2]), _p(ab[3]), _p(gz), ldz, B, T, H, W, C, mode,
                   _p(part, torch.float64), _stream(), label="don_pool_bwd", nbytes=8 * B * T * H * W * C)
-
-    @staticmethod
-    def k_sum64(part, rows, L, sums):
-        _lib.call("rpb_don_sum64", _p(part, torch.float64), rows, L, _p(sums, torch.float64), _stream(), label="don_sum64", nbytes=8 * rows * L)
-
-    @staticmethod
-    def k_bn_bwd_apply(gz, ldz, y, ldy, ab, sums, M, C, Cpad, dy, ldd, dgamma=None, dbeta=None):
-        _lib.call("rpb_don_bn_bwd_apply", _p(gz), ldz, _p(y), ldy, _p(ab[0]), _p(ab[2]), _p(ab[3]), _p(sums, torch.float64), M, C, Cpad, _p(dy),
-                  ldd, _p(dgamma), _p(dbeta), _stream(), label="don_bn_bwd_apply", nbytes=4 * M * (2 * C + Cpad))
 
     @staticmethod
     def k_point_mul(t, b, x, q0, R, B, N, p):
@@ -548,6 +510,13 @@ class DeepONet(EvalByDefault, Model):
     def k_point_mul_bwd(gx, t, b, gt, part, n0, R, N, p):
         _lib.call("rpb_don_point_mul_bwd", _p(gx), _p(t), _p(b), _p(gt), _p(part), n0, R, N, p, _stream(), label="don_point_mul_bwd",
                   nbytes=16 * R * p)
+
+    @staticmethod
+    def _bn_batch(y, ld, M, C, bn, parts=None):
+        """``batch_norm_rows`` and the stage's batch counter"""
+        ab = batch_norm_rows(y, ld, M, C, bn, parts)
+        bn.num_batches_tracked += 1
+        return ab
 
     def _drop(self, layer, chunk, step, row0=0):
         """The dropout argument of one GEMM launch: None (rate 0), the explicit mask's rows from ``row0`` (tests), or (seed, keep)."""
@@ -577,7 +546,7 @@ class DeepONet(EvalByDefault, Model):
         dev, f = x.device, dict(device=x.device, dtype=torch.float32)
         B, T, H, W, Cin = x.shape
         T_out, p, Cout = self.shape_out[0], self.p, self.output_channels
-        prep, ext, rows = self._prep_train(dev), pooled_extents(T, H, W), _lib.query("rpb_cno_bn_rows")
+        prep, ext, rows = self._prep_train(dev), pooled_extents(T, H, W), ops.rowbn_rows()
         for Ti, Hi, Wi in ext:                                        # before anything is launched: no statistic moves, no step is used up
             if B * Ti * Hi * Wi < 2:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, C, {Ti}, {Hi}, {Wi}]")
@@ -596,9 +565,8 @@ class DeepONet(EvalByDefault, Model):
             _lib.call("rpb_im2col", _p(x[b0:b0 + nbc]), _p(col), nbc, T, H, W, Cin, 3, s1["K"], _stream(), label="don_im2col",
                       nbytes=4 * nbc * cells * (Cin + s1["K"]))
             self._gemm(col, s1, Sub(y, b0 * cells * 64), nbc * cells)
-            self.k_bn_stats(Sub(y, b0 * cells * 64), 64, nbc * cells, 32, parts[0, k * rows:(k + 1) * rows])
-        bn = self.branch.conv1[1]
-        ab = self._bn_batch(y, 64, B * cells, 32, bn, parts)
+            ops.rowbn_stats(Sub(y, b0 * cells * 64), 64, nbc * cells, 32, parts[0, k * rows:(k + 1) * rows])
+        ab = self._bn_batch(y, 64, B * cells, 32, self.branch.conv1[1], parts)
         h = self.k_bn_relu_pool(y, ab[0], ab[1], B, T, H, W, 32, 64, 0)
         stages.append(dict(y=y, ab=ab, src=None))
         for i in (2, 3, 4):
@@ -642,7 +610,7 @@ class DeepONet(EvalByDefault, Model):
         dev, f = g_out.device, dict(device=g_out.device, dtype=torch.float32)
         B, T, H, W, T_out = state["shape"]
         p, Cout, N = self.p, self.output_channels, T_out * H * W
-        prep, rows = self._prep_train(dev), self.k_train_rows()
+        prep, rows = self._prep_train(dev), ops.rowbn_rows()
         t, b, step = state["t"], state["b"], state["step"]
         grads, acc = {}, {}
 
@@ -700,12 +668,8 @@ class DeepONet(EvalByDefault, Model):
             y, ab = st["y"], st["ab"]
             dy = torch.empty(M, Nw, **f)
             part64 = torch.empty(rows, 2 * C, device=dev, dtype=torch.float64)
-            sums = torch.empty(2 * C, device=dev, dtype=torch.float64)
-            dgb = torch.empty(2, C, **f)
             self.k_pool_bwd(y, Nw, g, ldg, ab, dy, Nw, B, Ti, Hi, Wi, C, 1 if i == 4 else 0, part64)
-            self.k_sum64(part64, rows, 2 * C, sums)
-            self.k_bn_bwd_apply(dy, Nw, y, Nw, ab, sums, M, C, Nw, dy, Nw, dgamma=dgb[0], dbeta=dgb[1])
-            grads[bn.weight], grads[bn.bias] = dgb[0], dgb[1]
+            grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part64, dy, Nw, y, Nw, ab, M, C, Nw, 0, dy, Nw)       # in place on dy
             if i == 1:                                                  # the im2col GEMM form, chunked like the forward
                 cells = Ti * Hi * Wi
                 nb = max(1, _COL_FLOATS // (cells * s["K"]))

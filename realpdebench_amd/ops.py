@@ -37,6 +37,13 @@ def _p(t, dtype=F32):
     return t.data_ptr()
 
 
+def _ptr(t, dtype=F32):
+    """address of a tensor of ``dtype``, of a ``Sub`` (a block of an fp32 allocation, whatever it holds), or the address itself"""
+    if t is None or isinstance(t, int):
+        return t
+    return _p(t) if isinstance(t, Sub) else _p(t, dtype)
+
+
 def _xf(xf, gelu_code=None):
     """Lazy-activation argument group: ``None`` or ``(mean, invstd, gamma, beta, gelu)`` -> 5 C arguments.
     ``gelu_code``: the integer passed instead of 1 when the GELU flag is set (cell_mix: 2 = "and store gz")."""
@@ -1178,3 +1185,44 @@ def dpot_unpatch(O, pred, B, T, H, W, Cd, Co, ps, ldo):
 def dpot_unpatch_bwd(gpred, gO, B, T, H, W, Cd, Co, ps, ldo):
     _lib.call("rpb_dpot_unpatch_bwd", _p(gpred), _p(gO), B, T, H, W, Cd, Co, ps, ldo, _stream(), label="dpot_unpatch_bwd",
               nbytes=4 * (gpred.numel() + gO.numel()))
+
+
+# ---- row BatchNorm (csrc/rpb_rowbn.hip): batch-statistics BatchNorm on rows [M][ld] for the CNO3d and DeepONet training steps.  Row
+# operands: fp32 tensors, ``Sub`` or raw addresses at the first column the launch owns; partials and sums: fp64.
+def rowbn_rows():
+    return _lib.query("rpb_rowbn_rows")
+
+
+def rowbn_stats(y, ld, M, C, part):
+    _lib.call("rpb_rowbn_stats", _ptr(y), ld, M, C, _ptr(part, torch.float64), _stream(), label="rowbn_stats", nbytes=4 * M * C)
+
+
+def rowbn_finish(part, rows, M, C, gamma, beta, rmean, rvar, eps, momentum, a, b, mean, rstd):
+    _lib.call("rpb_rowbn_finish", _ptr(part, torch.float64), rows, M, C, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
+              float(momentum), _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _stream(), label="rowbn_finish", nbytes=16 * rows * C)
+
+
+def rowbn_act_fwd(y, ldy, a, b, M, C, act, res=None, ldr=0, out=None, ldo=0, out_planes=None, ldp=0):
+    _lib.call("rpb_rowbn_act_fwd", _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(res), ldr, _ptr(out), ldo, _ptr(out_planes, torch.int16), ldp, M, C,
+              int(act), _stream(), label="rowbn_act_fwd",
+              nbytes=M * C * (4 + (4 if res is not None else 0) + (4 if out is not None else 0) + (6 if out_planes is not None else 0)))
+
+
+def rowbn_act_bwd_stats(gv, ldg, y, ldy, a, b, mean, rstd, M, C, act, part):
+    _lib.call("rpb_rowbn_act_bwd_stats", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), M, C, int(act),
+              _ptr(part, torch.float64), _stream(), label="rowbn_act_bwd_stats", nbytes=8 * M * C)
+
+
+def rowbn_sum64(part, rows, C, sums):
+    """sums [2 C] = the rows of part [rows][2 C], added in a fixed order"""
+    _lib.call("rpb_rowbn_sum64", _ptr(part, torch.float64), rows, C, _ptr(sums, torch.float64), _stream(), label="rowbn_sum64",
+              nbytes=16 * rows * C)
+
+
+def rowbn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=None, ldy=0, a=None, b=None, mean=None, rstd=None, sums=None, dy=None, ldd=0,
+                        dy_planes=None, ldp=0, dgamma=None, dbeta=None):
+    """``sums`` given: the BatchNorm form; otherwise the gate-only form (``y``: the saved LeakyReLU output).  ``dy`` may be ``gv``."""
+    _lib.call("rpb_rowbn_act_bwd_apply", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(sums, torch.float64),
+              M, C, Cpad, int(act), int(sums is not None), _ptr(dy), ldd, _ptr(dy_planes, torch.int16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(),
+              label="rowbn_act_bwd_apply",
+              nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))

@@ -75,7 +75,7 @@ def test_opt_in_plumbing():
 @pytest.mark.parametrize("Ci,Co", [(3, 64), (16, 32), (64, 128), (128, 64)])
 def test_flipped_weight_is_conv_transpose(Ci, Co):
     """``flipped_weight`` laid out as ``padded_weight`` lays out the forward weights: a convolution with it is the data gradient."""
-    from realpdebench_amd.model.cno import flipped_weight, padded_weight
+    from realpdebench_amd.model._common import flipped_weight, padded_weight
     g = torch.Generator().manual_seed(Ci * 1000 + Co)
     conv = torch.nn.Conv3d(Ci, Co, 3, padding=1).double()
     with torch.no_grad():

@@ -1,4 +1,4 @@
-"""The row kernels of the CNO3d training step (csrc/rpb_cno_train.hip) one by one, and the data gradient through rpb_cno_conv3x.
+"""The row kernels of the CNO3d training step (csrc/rpb_rowbn.hip, through the ``ops.rowbn_*`` wrappers) one by one, and the data gradient through rpb_cno_conv3x.
 
 Operands live in the guard-banded arena of tests/guarded.py (fp64 partials and sums in an fp64 arena of their own); references are fp64
 torch on the CPU, computed once per shape.  M = 720 = B 3 x mesh (5, 6, 8): five full 128-row tiles and a tail, more rows than one
@@ -26,7 +26,8 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import guarded                                    # noqa: E402
 from realpdebench_amd import ops                  # noqa: E402
-from realpdebench_amd.model.cno import CNO3d, flipped_weight      # noqa: E402
+from realpdebench_amd.model._common import flipped_weight      # noqa: E402
+from realpdebench_amd.model.cno import CNO3d      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -104,19 +105,19 @@ def _case(C, shifted=False):
 @pytest.mark.parametrize("C,ld,col,shifted", [(*l, False) for l in LAYOUTS] + [(64, 64, 0, True)])
 def test_bn_stats_and_finish(C, ld, col, shifted):
     c = _case(C, shifted)
-    rows = CNO3d.k_bn_rows()
+    rows = ops.rowbn_rows()
     a32, a64 = guarded.Arena(DEV), guarded.Arena(DEV, dtype=F64)
     o_y = _rows_in(a32, c["y"], ld, col, "y")
     o_gamma, o_beta = a32.inp(c["gamma"], "gamma"), a32.inp(c["beta"], "beta")
     outs = {k: a32.out(C, name=k) for k in ("a", "b", "mean", "rstd")}
     o_part = a64.out(rows, 2 * C, name="part")
     rm, rv = c["rm"].to(DEV), c["rv"].to(DEV)
-    CNO3d.k_bn_stats(o_y.at(col), ld, M_K, C, o_part.tensor())
+    ops.rowbn_stats(o_y.at(col), ld, M_K, C, o_part.tensor())
     a64.check()
     # (the finish reads the partials: a second fp64 arena holds them as an input)
     b64 = guarded.Arena(DEV, dtype=F64)
     i_part = b64.inp(o_part.get(), "part")
-    CNO3d.k_bn_finish(i_part.tensor(), rows, M_K, C, o_gamma.op, o_beta.op, rm, rv, EPS, MOM, *(outs[k].op for k in ("a", "b", "mean", "rstd")))
+    ops.rowbn_finish(i_part.tensor(), rows, M_K, C, o_gamma.op, o_beta.op, rm, rv, EPS, MOM, *(outs[k].op for k in ("a", "b", "mean", "rstd")))
     a32.check()
     b64.check()
     part = o_part.get()
@@ -132,8 +133,8 @@ def test_bn_stats_and_finish(C, ld, col, shifted):
     yb[:, col:col + C] = c["y"]
     yb, part2, ab2 = yb.to(DEV), torch.empty(rows, 2 * C, dtype=F64, device=DEV), torch.empty(4, C, device=DEV)
     rm2, rv2 = c["rm"].to(DEV), c["rv"].to(DEV)
-    CNO3d.k_bn_stats(ops.Sub(yb, col), ld, M_K, C, part2)
-    CNO3d.k_bn_finish(part2, rows, M_K, C, c["gamma"].to(DEV), c["beta"].to(DEV), rm2, rv2, EPS, MOM, *ab2)
+    ops.rowbn_stats(ops.Sub(yb, col), ld, M_K, C, part2)
+    ops.rowbn_finish(part2, rows, M_K, C, c["gamma"].to(DEV), c["beta"].to(DEV), rm2, rv2, EPS, MOM, *ab2)
     assert torch.equal(part2.cpu(), part) and torch.equal(rm2, rm) and torch.equal(rv2, rv)
     for i, k in enumerate(("a", "b", "mean", "rstd")):
         assert torch.equal(ab2[i].cpu(), outs[k].get()), k
@@ -156,7 +157,7 @@ def test_bn_act_fwd(C, ld, col, act, with_res, outs):
     o_op = a.out(3, M_K, ld // 2, name="planes", unwritten=unp if C < ld else None) if outs in ("both", "planes") else None
     kw = dict(res=None if o_res is None else o_res.at(col), ldr=ld, out=None if o_out is None else o_out.at(col), ldo=ld,
               out_planes=None if o_op is None else o_op.at(col // 2), ldp=ld)
-    CNO3d.k_bn_act_fwd(o_y.op, C, o_a.op, o_b.op, M_K, C, act, **kw)
+    ops.rowbn_act_fwd(o_y.op, C, o_a.op, o_b.op, M_K, C, act, **kw)
     a.check()
     y64, a64, b64 = c["y"].double(), c["a32"].double(), c["b32"].double()
     v = y64 * a64 + b64
@@ -179,7 +180,7 @@ def test_bn_act_fwd(C, ld, col, act, with_res, outs):
         out2, op2 = torch.zeros(M_K, ld, device=DEV), torch.zeros(3 * M_K * ld, dtype=I16, device=DEV)
         resb = torch.zeros(M_K, ld)
         resb[:, col:col + C] = c["res"]
-        CNO3d.k_bn_act_fwd(c["y"].to(DEV), C, c["a32"].to(DEV), c["b32"].to(DEV), M_K, C, act, res=ops.Sub(resb.to(DEV), col) if with_res else None,
+        ops.rowbn_act_fwd(c["y"].to(DEV), C, c["a32"].to(DEV), c["b32"].to(DEV), M_K, C, act, res=ops.Sub(resb.to(DEV), col) if with_res else None,
                            ldr=ld, out=ops.Sub(out2, col), ldo=ld, out_planes=op2.data_ptr() + 2 * col, ldp=ld)
         assert torch.equal(out2.cpu()[:, col:col + C], rows)
         assert torch.equal(op2.view(3, M_K, ld).cpu()[:, :, col:col + C], _planes(o_op.get(), M_K, ld)[:, :, col:col + C])
@@ -191,22 +192,22 @@ def test_bn_act_fwd(C, ld, col, act, with_res, outs):
 def test_bn_act_bwd(C, ld, col, act):
     """gv arrives at column ``col`` of an ld-wide gradient buffer (the concat); dy leaves max(C, 64) wide with zero pad columns."""
     c = _case(C)
-    rows, Cpad = CNO3d.k_bn_rows(), max(C, 64)
+    rows, Cpad = ops.rowbn_rows(), max(C, 64)
     a32, a64 = guarded.Arena(DEV), guarded.Arena(DEV, dtype=F64)
     o_gv, o_y = _rows_in(a32, c["gv"], ld, col, "gv"), a32.inp(c["y"], "y")
     vec = {k: a32.inp(c[k + "32"], k) for k in ("a", "b", "mean", "rstd")}
     o_dy, o_dp = a32.out(M_K, Cpad, name="dy"), a32.out(3, M_K, Cpad // 2, name="dy_planes")
     o_dg, o_db = a32.out(C, name="dgamma"), a32.out(C, name="dbeta")
     o_part = a64.out(rows, 2 * C, name="part")
-    CNO3d.k_bn_act_bwd_stats(o_gv.at(col), ld, o_y.op, C, vec["a"].op, vec["b"].op, vec["mean"].op, vec["rstd"].op, M_K, C, act, o_part.tensor())
+    ops.rowbn_act_bwd_stats(o_gv.at(col), ld, o_y.op, C, vec["a"].op, vec["b"].op, vec["mean"].op, vec["rstd"].op, M_K, C, act, o_part.tensor())
     a64.check()
     b64 = guarded.Arena(DEV, dtype=F64)
     i_part, o_sums = b64.inp(o_part.get(), "part"), b64.out(2 * C, name="sums")
-    CNO3d.k_sum64(i_part.tensor(), rows, C, o_sums.tensor())
+    ops.rowbn_sum64(i_part.tensor(), rows, C, o_sums.tensor())
     b64.check()
     c64 = guarded.Arena(DEV, dtype=F64)
     i_sums = c64.inp(o_sums.get(), "sums")
-    CNO3d.k_bn_act_bwd_apply(o_gv.at(col), ld, M_K, C, Cpad, act, y=o_y.op, ldy=C, a=vec["a"].op, b=vec["b"].op, mean=vec["mean"].op,
+    ops.rowbn_act_bwd_apply(o_gv.at(col), ld, M_K, C, Cpad, act, y=o_y.op, ldy=C, a=vec["a"].op, b=vec["b"].op, mean=vec["mean"].op,
                              rstd=vec["rstd"].op, sums=i_sums.tensor(), dy=o_dy.op, ldd=Cpad, dy_planes=o_dp.op, ldp=Cpad, dgamma=o_dg.op,
                              dbeta=o_db.op)
     a32.check()
@@ -239,9 +240,9 @@ def test_bn_act_bwd(C, ld, col, act):
     v32 = [c[k + "32"].to(DEV) for k in ("a", "b", "mean", "rstd")]
     part2, sums2 = torch.empty(rows, 2 * C, dtype=F64, device=DEV), torch.empty(2 * C, dtype=F64, device=DEV)
     dy2, dp2, dgb2 = torch.empty(M_K, Cpad, device=DEV), torch.empty(3 * M_K * Cpad, dtype=I16, device=DEV), torch.empty(2, C, device=DEV)
-    CNO3d.k_bn_act_bwd_stats(ops.Sub(gb, col), ld, yd, C, *v32, M_K, C, act, part2)
-    CNO3d.k_sum64(part2, rows, C, sums2)
-    CNO3d.k_bn_act_bwd_apply(ops.Sub(gb, col), ld, M_K, C, Cpad, act, y=yd, ldy=C, a=v32[0], b=v32[1], mean=v32[2], rstd=v32[3], sums=sums2,
+    ops.rowbn_act_bwd_stats(ops.Sub(gb, col), ld, yd, C, *v32, M_K, C, act, part2)
+    ops.rowbn_sum64(part2, rows, C, sums2)
+    ops.rowbn_act_bwd_apply(ops.Sub(gb, col), ld, M_K, C, Cpad, act, y=yd, ldy=C, a=v32[0], b=v32[1], mean=v32[2], rstd=v32[3], sums=sums2,
                              dy=dy2, ldd=Cpad, dy_planes=dp2, ldp=Cpad, dgamma=dgb2[0], dbeta=dgb2[1])
     assert torch.equal(part2.cpu(), o_part.get()) and torch.equal(sums2.cpu(), sums) and torch.equal(dy2.cpu(), dy)
     assert torch.equal(dp2.view(3, M_K, Cpad).cpu(), pl) and torch.equal(dgb2[0].cpu(), o_dg.get()) and torch.equal(dgb2[1].cpu(), o_db.get())
@@ -258,7 +259,7 @@ def test_gate_only_backward():
         o_gv, o_v = a.inp(c["gv"], "gv"), a.inp(v, "v")
         o_dy = a.out(M_K, 64, name="dy")
         o_dp = a.out(3, M_K, 32, name="dy_planes") if planes else None
-        CNO3d.k_bn_act_bwd_apply(o_gv.op, 64, M_K, 64, 64, 1, y=o_v.op, ldy=64, dy=o_dy.op, ldd=64, dy_planes=None if o_dp is None else o_dp.op,
+        ops.rowbn_act_bwd_apply(o_gv.op, 64, M_K, 64, 64, 1, y=o_v.op, ldy=64, dy=o_dy.op, ldd=64, dy_planes=None if o_dp is None else o_dp.op,
                                  ldp=64 if planes else 0)
         a.check()
         want = torch.where(v > 0, c["gv"].double(), 0.2 * c["gv"].double())     # (one rounded product with the fp32 constant 0.2f: 1.125 u)
@@ -269,20 +270,20 @@ def test_gate_only_backward():
 
 def test_row_kernels_refuse_what_they_do_not_cover():
     from realpdebench_amd import _lib
-    y, p = torch.zeros(8, 64, device=DEV), torch.zeros(CNO3d.k_bn_rows(), 128, dtype=F64, device=DEV)
+    y, p = torch.zeros(8, 64, device=DEV), torch.zeros(ops.rowbn_rows(), 128, dtype=F64, device=DEV)
     v = torch.zeros(4, 64, device=DEV)
-    with pytest.raises(_lib.RpbError, match="cno_bn_stats"):
-        CNO3d.k_bn_stats(y, 64, 8, 24, p)
-    with pytest.raises(_lib.RpbError, match="cno_bn_stats"):
-        CNO3d.k_bn_stats(y, 62, 8, 16, p)
-    with pytest.raises(_lib.RpbError, match="cno_bn_finish"):
-        CNO3d.k_bn_finish(p, 4, 1, 64, v[0], v[1], v[2], v[3], EPS, MOM, *torch.zeros(4, 64, device=DEV))       # M = 1: no batch statistics
-    with pytest.raises(_lib.RpbError, match="cno_bn_act_fwd"):
-        CNO3d.k_bn_act_fwd(y, 64, v[0], v[1], 8, 64, 1)                                                       # no output
-    with pytest.raises(_lib.RpbError, match="cno_bn_act_fwd"):
-        CNO3d.k_bn_act_fwd(y, 64, v[0], v[1], 8, 64, 1, out_planes=torch.zeros(3 * 8 * 64, dtype=I16, device=DEV), ldp=60)
-    with pytest.raises(_lib.RpbError, match="cno_bn_act_bwd_apply"):
-        CNO3d.k_bn_act_bwd_apply(y, 64, 8, 64, 32, 1, y=y, ldy=64, dy=torch.zeros(8, 64, device=DEV), ldd=64)   # Cpad < C
+    with pytest.raises(_lib.RpbError, match="rowbn_stats"):
+        ops.rowbn_stats(y, 64, 8, 24, p)
+    with pytest.raises(_lib.RpbError, match="rowbn_stats"):
+        ops.rowbn_stats(y, 62, 8, 16, p)
+    with pytest.raises(_lib.RpbError, match="rowbn_finish"):
+        ops.rowbn_finish(p, 4, 1, 64, v[0], v[1], v[2], v[3], EPS, MOM, *torch.zeros(4, 64, device=DEV))       # M = 1: no batch statistics
+    with pytest.raises(_lib.RpbError, match="rowbn_act_fwd"):
+        ops.rowbn_act_fwd(y, 64, v[0], v[1], 8, 64, 1)                                                       # no output
+    with pytest.raises(_lib.RpbError, match="rowbn_act_fwd"):
+        ops.rowbn_act_fwd(y, 64, v[0], v[1], 8, 64, 1, out_planes=torch.zeros(3 * 8 * 64, dtype=I16, device=DEV), ldp=60)
+    with pytest.raises(_lib.RpbError, match="rowbn_act_bwd_apply"):
+        ops.rowbn_act_bwd_apply(y, 64, 8, 64, 32, 1, y=y, ldy=64, dy=torch.zeros(8, 64, device=DEV), ldd=64)   # Cpad < C
     torch.cuda.synchronize()
 
 

@@ -1,4 +1,5 @@
-"""The row kernels of the DeepONet training step (csrc/rpb_deeponet_train.hip), every new entry point called alone.
+"""The row kernels of the DeepONet training step (csrc/rpb_deeponet_train.hip) and the row BatchNorm backward tail they feed
+(csrc/rpb_rowbn.hip: ``ops.rowbn_sum64``, ``ops.rowbn_act_bwd_apply``), every entry point called alone.
 
 Operands live in the guard-banded arenas of tests/guarded.py (fp64 partials and sums in fp64 arenas of their own).  References are the
 functions of tests/deeponet_train_restatement.py in fp64 on the CPU, computed once per shape; the verdict is tests/kernel_verdict.py: the
@@ -108,7 +109,7 @@ def _cols(M, ld, lo):
 @pytest.mark.parametrize("mode,C,ld,B,T,H,W", POOL_CASES)
 def test_pool_bwd_sum_and_apply(mode, C, ld, B, T, H, W):
     c = _pool_case(mode, C, B, T, H, W)
-    M, rows, tag = B * T * H * W, DeepONet.k_train_rows(), f"pool{mode} C{C} ld{ld} {B}x{T}x{H}x{W}"
+    M, rows, tag = B * T * H * W, ops.rowbn_rows(), f"pool{mode} C{C} ld{ld} {B}x{T}x{H}x{W}"
     Cpad = min(ld, C + 32) // 4 * 4
     ab = [c[k] for k in ("a", "b", "mean", "rstd")]
     a32, p64, s64 = guarded.Arena(DEV), guarded.Arena(DEV, dtype=F64), guarded.Arena(DEV, dtype=F64)
@@ -121,7 +122,7 @@ def test_pool_bwd_sum_and_apply(mode, C, ld, B, T, H, W):
     p64.check()
     gz, part = o_gz.get()[:, :C], o_part.get()
     i_part, o_sums = s64.inp(part, "part"), s64.out(2 * C, name="sums")
-    DeepONet.k_sum64(i_part.tensor(), rows, 2 * C, o_sums.tensor())
+    ops.rowbn_sum64(i_part.tensor(), rows, C, o_sums.tensor())
     s64.check()
     sums = o_sums.get()
     # the apply launch, out of place: gz and the sums as inputs of a second arena
@@ -131,7 +132,8 @@ def test_pool_bwd_sum_and_apply(mode, C, ld, B, T, H, W):
     i_sums = t64.inp(sums, "sums")
     o_dy = b32.out(M, ld, name="dy", unwritten=_cols(M, ld, Cpad))
     o_dg, o_db = b32.out(C, name="dgamma"), b32.out(C, name="dbeta")
-    DeepONet.k_bn_bwd_apply(i_gz.op, ld, i_y.op, ld, [o.op for o in i_ab], i_sums.tensor(), M, C, Cpad, o_dy.op, ld, dgamma=o_dg.op, dbeta=o_db.op)
+    v = dict(zip(("a", "b", "mean", "rstd"), (o.op for o in i_ab)))
+    ops.rowbn_act_bwd_apply(i_gz.op, ld, M, C, Cpad, 0, y=i_y.op, ldy=ld, **v, sums=i_sums.tensor(), dy=o_dy.op, ldd=ld, dgamma=o_dg.op, dbeta=o_db.op)
     b32.check()
     t64.check()
     dy = o_dy.get()
@@ -140,7 +142,7 @@ def test_pool_bwd_sum_and_apply(mode, C, ld, B, T, H, W):
     for name, got, k in (("gz", gz, 0), ("sums", sums, 1), ("dy", dy[:, :C], 2), ("dgamma", o_dg.get(), 3), ("dbeta", o_db.get(), 4)):
         for kind, e32, ek in zip(("rel-l2", "max-abs"), measures(r32[k], r64[k]), measures(got, r64[k])):
             figures.append((f"{name} {kind}", e32, ek))
-    verdict(tag, "don_pool_bwd + don_sum64 + don_bn_bwd_apply", figures)
+    verdict(tag, "don_pool_bwd + rowbn_sum64 + rowbn_act_bwd_apply", figures)
     assert not bool(dy[:, C:Cpad].any()), "pad columns are exactly zero"
     assert torch.equal((gz != 0), (r64[0] != 0)), "the gradient lands on exactly the cells the rule names"
     if not mode:
@@ -153,8 +155,9 @@ def test_pool_bwd_sum_and_apply(mode, C, ld, B, T, H, W):
     dy2, part2, sums2 = torch.full((M, ld), 7.0, device=DEV), torch.empty(rows, 2 * C, dtype=F64, device=DEV), torch.empty(2 * C, dtype=F64, device=DEV)
     dgb2 = torch.empty(2, C, device=DEV)
     DeepONet.k_pool_bwd(y2, ld, g2, ld, ab2, dy2, ld, B, T, H, W, C, mode, part2)
-    DeepONet.k_sum64(part2, rows, 2 * C, sums2)
-    DeepONet.k_bn_bwd_apply(dy2, ld, y2, ld, ab2, sums2, M, C, Cpad, dy2, ld, dgamma=dgb2[0], dbeta=dgb2[1])
+    ops.rowbn_sum64(part2, rows, C, sums2)
+    ops.rowbn_act_bwd_apply(dy2, ld, M, C, Cpad, 0, y=y2, ldy=ld, a=ab2[0], b=ab2[1], mean=ab2[2], rstd=ab2[3], sums=sums2, dy=dy2, ldd=ld,
+                            dgamma=dgb2[0], dbeta=dgb2[1])
     assert torch.equal(part2.cpu(), part) and torch.equal(sums2.cpu(), sums)
     assert torch.equal(dy2.cpu()[:, :Cpad], dy[:, :Cpad]) and torch.equal(dgb2[0].cpu(), o_dg.get()) and torch.equal(dgb2[1].cpu(), o_db.get())
     assert bool((dy2[:, Cpad:] == 7.0).all()), "columns beyond Cpad are not touched"
@@ -165,7 +168,7 @@ def test_max_pool_backward_takes_the_first_maximum_on_a_tie():
     goes to k = 3 alone.  Channel 1: eight equal positive values: k = 0.  Channel 2: every value <= 0 (the largest exactly 0): nothing.
     Channel 3: a unique maximum in the last cell.  The drawn cases above keep the two largest values 1e-3 apart; this one pins the strict
     comparison of the kernel's scan."""
-    C, rows = 32, DeepONet.k_train_rows()
+    C, rows = 32, ops.rowbn_rows()
     y = -torch.rand(8, C, generator=_g(3)) - 0.5
     y[:, 0] = torch.tensor([0.5, 1.0, 0.25, 2.0, 1.5, 2.0, 0.0, -1.0])
     y[:, 1] = 0.75
@@ -222,7 +225,7 @@ def test_point_mul_bwd(B, N, p, q0, R):
     """The chunk's rows, one launch per sample it touches (as the model walks them): gt accumulates over the samples, gb[s] over the
     launches of sample s through rpb_reduce_partials (accumulate)."""
     c = _point_case(B, N, p)
-    rows = DeepONet.k_train_rows()
+    rows = ops.rowbn_rows()
     gx = c["gx"][q0:q0 + R]
     t_d, b_d = c["t"].to(DEV), c["b"].to(DEV)
 
@@ -266,7 +269,7 @@ def test_point_mul_bwd(B, N, p, q0, R):
 def test_bad_arguments_are_refused():
     from realpdebench_amd._lib import RpbError
     z = torch.zeros(64, 64, device=DEV)
-    part = torch.zeros(DeepONet.k_train_rows(), 128, dtype=F64, device=DEV)
+    part = torch.zeros(ops.rowbn_rows(), 128, dtype=F64, device=DEV)
     with pytest.raises(RpbError, match="C in"):
         DeepONet.k_pool_bwd(z, 64, z, 64, z[:4], z, 64, 1, 4, 4, 4, 48, 0, part)
     with pytest.raises(RpbError, match="extents >= 2"):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """The opt-in CNO3d training step measured on the MI355X at the cylinder shape: one ``ArenaTrainer.step`` per batch size (median of 10
 after 3 warm-ups), the eval forward of the same run next to it, the per-launch HIP-event table by kernel family (the ``label``s of
-model/cno.py and ops.py), the share of the new row kernels (csrc/rpb_cno_train.hip) and ``torch.cuda.max_memory_allocated``.
+model/cno.py and ops.py), the share of the new row kernels (csrc/rpb_rowbn.hip) and ``torch.cuda.max_memory_allocated``.
 Launches under ~100 us are dominated by the event overhead in the table.
     python tools/cno_train_probe.py [--batches 1 2 4] [--runs 10] [--out profiles/cno_train_probe.txt]"""
 import argparse
@@ -17,7 +17,7 @@ from realpdebench_amd.model.cno import CNO3d              # noqa: E402
 from realpdebench_amd.trainer import make_trainer         # noqa: E402
 from tools.cno_probe import DEV, HBM_PEAK, SHAPE, median_ms          # noqa: E402
 
-ROW_KERNELS = ("cno_bn_stats", "cno_bn_finish", "cno_bn_act_fwd", "cno_bn_act_bwd_stats", "cno_sum64", "cno_bn_act_bwd_apply")
+ROW_KERNELS = ("rowbn_stats", "rowbn_finish", "rowbn_act_fwd", "rowbn_act_bwd_stats", "rowbn_sum64", "rowbn_act_bwd_apply")
 
 
 def family(label):

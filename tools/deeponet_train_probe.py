@@ -2,7 +2,7 @@
 """The opt-in DeepONet training step measured on the MI355X at the cylinder shape (p = 128, dropout 0.1): one ``ArenaTrainer.step`` per
 batch size (median of 10 after 3 warm-ups), the eval forward of the same run next to it, the per-launch HIP-event table by kernel
 family (the ``label``s of model/deeponet.py, model/_common.py and ops.py), the share of the new row kernels
-(csrc/rpb_deeponet_train.hip) and ``torch.cuda.max_memory_allocated``.  Launches under ~100 us are dominated by the event overhead in
+(csrc/rpb_deeponet_train.hip and the BatchNorm backward tail of csrc/rpb_rowbn.hip) and ``torch.cuda.max_memory_allocated``.  Launches under ~100 us are dominated by the event overhead in
 the table.  No speed threshold: the step / forward ratio is recorded, not asserted.
     python tools/deeponet_train_probe.py [--batches 1 4] [--runs 10] [--out profiles/deeponet_train_probe.txt]"""
 import argparse
@@ -19,7 +19,7 @@ from realpdebench_amd.trainer import make_trainer         # noqa: E402
 from tools.cno_probe import DEV, HBM_PEAK, median_ms      # noqa: E402
 from tools.deeponet_probe import P, SHAPE                 # noqa: E402
 
-ROW_KERNELS = ("don_pool_bwd", "don_sum64", "don_bn_bwd_apply", "don_point_mul", "don_point_mul_bwd")
+ROW_KERNELS = ("don_pool_bwd", "rowbn_sum64", "rowbn_act_bwd_apply", "don_point_mul", "don_point_mul_bwd")
 
 
 def family(label):
