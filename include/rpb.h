@@ -43,7 +43,8 @@ extern "C" {
  *      number moves so that a binding that expects them refuses a library without them)
  *   5  row BatchNorm, one family for CNO3d and DeepONet: rpb_cno_bn_rows / _stats / _finish / _act_fwd / _act_bwd_stats / _act_bwd_apply and
  *      rpb_cno_sum64 renamed rpb_rowbn_* (rpb_rowbn_sum64, rpb_rowbn_act_bwd_apply take C up to 256; the apply takes Cpad % 4 == 0 for rows);
- *      rpb_don_train_rows, rpb_don_sum64, rpb_don_bn_bwd_apply removed (rpb_rowbn_rows, rpb_rowbn_sum64, rpb_rowbn_act_bwd_apply) */
+ *      rpb_don_train_rows, rpb_don_sum64, rpb_don_bn_bwd_apply removed (rpb_rowbn_rows, rpb_rowbn_sum64, rpb_rowbn_act_bwd_apply);
+ *      later, additions only: rpb_rowbn_finish_sums, rpb_rowbn_act_bwd_apply_sync (SyncBN for CNO3d and DeepONet) */
 #define RPB_ABI_VERSION 5
 const char* rpb_last_error(void);
 int rpb_abi_version(void);
@@ -826,7 +827,15 @@ int rpb_cno_pack_f16x2(const float* x, void* planes, long M, int Cin, int* e, vo
  *     C..Cpad-1 written as zero; dbeta[c] = sums[c], dgamma[c] = sums[C + c] (may be null).  has_bn = 0: dy = dz with the gate taken from the
  *     sign of y itself (the saved LeakyReLU output); a, b, mean, rstd, sums unused.  C in {16, 32, 64, 128, 256}, Cpad % 4 == 0; plane
  *     output needs Cpad % 8 == 0.  `dy` may alias `gv` element for element (same address, ldd == ldg): a thread reads all its elements of
- *     a row and then writes them, nobody else touches those elements.  The DeepONet step applies in place on its pooling gradient. */
+ *     a row and then writes them, nobody else touches those elements.  The DeepONet step applies in place on its pooling gradient.
+ * SyncBN (enable_training(sync_bn=True): the statistics of W ranks with M rows each, M_total = W M; additions do not change RPB_ABI_VERSION).
+ * The caller all-reduces the fp64 sums between the two launches of a pass:
+ *     rpb_rowbn_finish_sums: rpb_rowbn_finish from sums[2 C] = (sum y, sum y^2) over M_total rows instead of partials.  With
+ *     sums = rpb_rowbn_sum64(part) and M_total = M every output is bit-equal to rpb_rowbn_finish(part, rows, M, ...).
+ *     rpb_rowbn_act_bwd_apply_sync: the has_bn = 1 form with dy = a (dz - sums_global[c] / M_total - xhat sums_global[C + c] / M_total) and
+ *     dbeta[c] = sums_local[c], dgamma[c] = sums_local[C + c] (this rank's part: the mean over the ranks of a per-rank mean loss is the global
+ *     gradient).  The checks of rpb_rowbn_act_bwd_apply, and M_total >= M.  With sums_global == sums_local and M_total == M it is bit-equal
+ *     to rpb_rowbn_act_bwd_apply. */
 int rpb_rowbn_rows(void);
 int rpb_rowbn_stats(const float* y, int ld, long M, int C, double* part, void* stream);
 int rpb_rowbn_finish(const double* part, int rows, long M, int C, const float* gamma, const float* beta, float* running_mean,
@@ -839,6 +848,11 @@ int rpb_rowbn_sum64(const double* part, int rows, int C, double* sums, void* str
 int rpb_rowbn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
                             const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy, int ldd,
                             void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
+int rpb_rowbn_finish_sums(const double* sums, long M_total, int C, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd, void* stream);
+int rpb_rowbn_act_bwd_apply_sync(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                                 const float* rstd, const double* sums_local, const double* sums_global, long M, long M_total, int C,
+                                 int Cpad, int act, float* dy, int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream);
 
 /*
  * DeepONet training step (opt-in: DeepONet.enable_training()) -- the row passes of the backward pass and of the chunked output net

@@ -230,6 +230,8 @@ SIGNATURES = {
     "rpb_rowbn_act_bwd_stats": (_I, "pi" + "pi" + "pppp" + "lii" + "p" + "p"),
     "rpb_rowbn_sum64": (_I, "p" + "ii" + "p" + "p"),
     "rpb_rowbn_act_bwd_apply": (_I, "pi" + "pi" + "pppp" + "p" + "liiii" + "pi" + "pi" + "pp" + "p"),
+    "rpb_rowbn_finish_sums": (_I, "p" + "li" + "pppp" + "dd" + "pppp" + "p"),
+    "rpb_rowbn_act_bwd_apply_sync": (_I, "pi" + "pi" + "pppp" + "pp" + "lliii" + "pi" + "pi" + "pp" + "p"),
     "rpb_don_pool_bwd": (_I, "pi" + "pi" + "pppp" + "pi" + "iiiiii" + "p" + "p"),
     "rpb_don_point_mul": (_I, "ppp" + "ll" + "il" + "i" + "p"),
     "rpb_don_point_mul_bwd": (_I, "ppppp" + "lll" + "i" + "p"),

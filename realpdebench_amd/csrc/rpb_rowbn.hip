@@ -9,6 +9,8 @@
 //   backward   dz = gv (z > 0 ? 1 : 0.2);  (sum dz, sum dz xhat), xhat = (y - mean) rstd   rpb_rowbn_act_bwd_stats -> fp64 partials
 //              fixed-order sum of the partials              rpb_rowbn_sum64
 //              dy = a (dz - dbeta / M - xhat dgamma / M);  dgamma, dbeta              rpb_rowbn_act_bwd_apply (fp32 rows and / or bf16 planes)
+//   SyncBN     the statistics from sums the caller all-reduced over its ranks      rpb_rowbn_finish_sums
+//              dy from the all-reduced sums and M_total, dgamma and dbeta from this rank's own      rpb_rowbn_act_bwd_apply_sync
 //
 // Every kernel is grid-stride with 16-byte accesses, uses no atomics and sums in a fixed order: two calls are bit-equal.  Every pointer
 // arrives at the first column the launch owns, with a leading dimension (producers own column ranges of shared buffers).  The gate of the
@@ -151,6 +153,20 @@ extern "C" int rpb_rowbn_finish(const double* part, int rows, long M, int C, con
     RPB_CHECK_LAUNCH("rowbn_finish");
 }
 
+// The finish from sums a caller reduced itself (SyncBN: the all-reduced sums of W ranks, M_total = W M): ct_sum_kernel<true> on the one
+// row `sums`.  Row group 0 holds the sum, the other seven add 0: with sums = rpb_rowbn_sum64(part) and M_total = M every output has the bits
+// of rpb_rowbn_finish(part, rows, M, ...).
+extern "C" int rpb_rowbn_finish_sums(const double* sums, long M_total, int C, const float* gamma, const float* beta, float* running_mean,
+                                     float* running_var, double eps, double momentum, float* a, float* b, float* mean, float* rstd,
+                                     void* stream) {
+    RPB_REQUIRE(sums && gamma && beta && running_mean && running_var && a && b && mean && rstd && M_total > 1 && rowbn_chan_ok(C, 16, 128) &&
+                    eps > 0. && momentum >= 0. && momentum <= 1.,
+                "rowbn_finish_sums: bad arguments (M_total=%ld C=%d; M_total > 1, C in {16, 32, 64, 128})", M_total, C);
+    CtFinArgs p{sums, nullptr, gamma, beta, running_mean, running_var, a, b, mean, rstd, M_total, 1, C, eps, momentum};
+    hipLaunchKernelGGL(ct_sum_kernel<true>, dim3(C / 16), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
+    RPB_CHECK_LAUNCH("rowbn_finish_sums");
+}
+
 extern "C" int rpb_rowbn_sum64(const double* part, int rows, int C, double* sums, void* stream) {
     RPB_REQUIRE(part && sums && rows > 0 && rowbn_chan_ok(C, 16, 256), "rowbn_sum64: bad arguments (rows=%d C=%d; C in {16, 32, 64, 128, 256})", rows, C);
     CtFinArgs p{part, sums, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, rows, C, 0., 0.};
@@ -208,18 +224,21 @@ extern "C" int rpb_rowbn_act_fwd(const float* y, int ldy, const float* a, const 
 }
 
 // ---------------------------------------------------------------------------------- backward apply
-// has_bn:  dy = a (dz - dbeta / M - xhat dgamma / M),  dz = gv or 0.2 gv by the sign of fmaf(y, a, b)
+// has_bn:  dy = a (dz - gsums[c] / Mtot - xhat gsums[C + c] / Mtot),  dz = gv or 0.2 gv by the sign of fmaf(y, a, b);  dbeta, dgamma = sums.
+//          One rank: gsums = sums, Mtot = M.  SyncBN (rpb_rowbn_act_bwd_apply_sync): gsums = the sums of all ranks, Mtot = the rows of all
+//          ranks, sums = this rank's own (the trainer's mean over the ranks makes them the global gradients).
 // else:    dy = dz, the gate from the sign of `y` itself (the saved LeakyReLU output, or conv + bias: same sign)
 // Columns C..Cpad-1 of the rows and planes are written as zero (the 64-wide operands of the narrow layers).  One thread = RUN channels
 // of one row: 8 (what a 16 B plane store takes) when Cpad % 8 == 0, else 4 (rows only); the expression per element is the same.  dy may
 // be gv itself (same address, ldd == ldg): a thread reads all its elements of a row before it writes them.
 struct CtBwdArgs {
     const float *gv, *y, *a, *b, *mean, *rstd;
-    const double* sums;    // [2 C]: (sum dz, sum dz xhat)
+    const double* sums;    // [2 C]: (sum dz, sum dz xhat) of these M rows -> dbeta, dgamma
+    const double* gsums;   // [2 C]: the same sums over all Mtot rows -> k1, k2
     float* dy;             // [M][ldd] or null
     uint16_t* dp;          // [3][M][ldp] or null
     float *dgamma, *dbeta; // [C] or null
-    long M;
+    long M, Mtot;
     int C, Cpad, ldg, ldy, ldd, ldp, act, has_bn;
 };
 
@@ -232,7 +251,7 @@ __global__ __launch_bounds__(ROWBN_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) 
             p.dbeta[c] = (float)p.sums[c];
             p.dgamma[c] = (float)p.sums[p.C + c];
         }
-    const double inv_m = 1.0 / (double)p.M;
+    const double inv_m = 1.0 / (double)p.Mtot;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const long m = idx / runs;
@@ -250,7 +269,7 @@ __global__ __launch_bounds__(ROWBN_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) 
                     const f32x4 mu = *reinterpret_cast<const f32x4*>(p.mean + c), rs = *reinterpret_cast<const f32x4*>(p.rstd + c);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float k1 = (float)(p.sums[c + i] * inv_m), k2 = (float)(p.sums[p.C + c + i] * inv_m);
+                        const float k1 = (float)(p.gsums[c + i] * inv_m), k2 = (float)(p.gsums[p.C + c + i] * inv_m);
                         const float z = __builtin_fmaf(y4[i], a4[i], b4[i]);
                         const float dz = (p.act && !(z > 0.f)) ? 0.2f * g4[i] : g4[i];
                         const float xh = (y4[i] - mu[i]) * rs[i];
@@ -270,24 +289,44 @@ __global__ __launch_bounds__(ROWBN_THREADS) void ct_act_bwd_kernel(CtBwdArgs p) 
     }
 }
 
-extern "C" int rpb_rowbn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
-                                       const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy,
-                                       int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream) {
+// The argument checks and the launch of both backward applies; `who` names the entry point in the messages.  A refused call writes nothing.
+static int rowbn_bwd_apply(const char* who, const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                           const float* rstd, const double* sums, const double* gsums, long M, long Mtot, int C, int Cpad, int act,
+                           int has_bn, float* dy, int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream) {
     RPB_REQUIRE(gv && (dy || dy_planes) && M > 0 && M < (1L << 31) && rowbn_chan_ok(C, 16, 256) && Cpad >= C && Cpad % 4 == 0 && (act == 0 || act == 1) &&
                     (has_bn == 0 || has_bn == 1),
-                "rowbn_act_bwd_apply: bad arguments (M=%ld C=%d Cpad=%d act=%d has_bn=%d; C in {16, 32, 64, 128, 256}, Cpad >= C, Cpad %% 4 == 0)",
-                M, C, Cpad, act, has_bn);
-    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && rowbn_al16(gv), "rowbn_act_bwd_apply: ldg=%d (>= C, %% 4 == 0, gv 16-byte aligned)", ldg);
-    RPB_REQUIRE(!(has_bn || act) || (y && ldy >= C && ldy % 4 == 0 && rowbn_al16(y)), "rowbn_act_bwd_apply: y / ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", ldy);
-    RPB_REQUIRE(!has_bn || (a && b && mean && rstd && sums && rowbn_al16(a) && rowbn_al16(b) && rowbn_al16(mean) && rowbn_al16(rstd) && (!dgamma == !dbeta)),
-                "rowbn_act_bwd_apply: has_bn needs a, b, mean, rstd (16-byte aligned) and sums; dgamma and dbeta come together");
-    RPB_REQUIRE(!dy || (ldd >= Cpad && ldd % 4 == 0 && rowbn_al16(dy)), "rowbn_act_bwd_apply: ldd=%d (>= Cpad, %% 4 == 0, dy 16-byte aligned)", ldd);
+                "%s: bad arguments (M=%ld C=%d Cpad=%d act=%d has_bn=%d; C in {16, 32, 64, 128, 256}, Cpad >= C, Cpad %% 4 == 0)", who, M, C, Cpad,
+                act, has_bn);
+    RPB_REQUIRE(Mtot >= M, "%s: M_total=%ld must be >= M=%ld (the rows of all ranks, this rank's included)", who, Mtot, M);
+    RPB_REQUIRE(ldg >= C && ldg % 4 == 0 && rowbn_al16(gv), "%s: ldg=%d (>= C, %% 4 == 0, gv 16-byte aligned)", who, ldg);
+    RPB_REQUIRE(!(has_bn || act) || (y && ldy >= C && ldy % 4 == 0 && rowbn_al16(y)), "%s: y / ldy=%d (>= C, %% 4 == 0, 16-byte aligned)", who, ldy);
+    RPB_REQUIRE(!has_bn || (a && b && mean && rstd && sums && gsums && rowbn_al16(a) && rowbn_al16(b) && rowbn_al16(mean) && rowbn_al16(rstd) &&
+                            (!dgamma == !dbeta)),
+                "%s: has_bn needs a, b, mean, rstd (16-byte aligned) and sums; dgamma and dbeta come together", who);
+    RPB_REQUIRE(!dy || (ldd >= Cpad && ldd % 4 == 0 && rowbn_al16(dy)), "%s: ldd=%d (>= Cpad, %% 4 == 0, dy 16-byte aligned)", who, ldd);
     RPB_REQUIRE(!dy_planes || (Cpad % 8 == 0 && ldp >= Cpad && ldp % 8 == 0 && rowbn_al16(dy_planes)),
-                "rowbn_act_bwd_apply: plane output needs a 16-byte aligned first column, Cpad %% 8 == 0 and ldp %% 8 == 0 (Cpad=%d ldp=%d)", Cpad, ldp);
-    CtBwdArgs p{gv, y, a, b, mean, rstd, sums, dy, (uint16_t*)dy_planes, dgamma, dbeta, M, C, Cpad, ldg, ldy, ldd, ldp, act, has_bn};
+                "%s: plane output needs a 16-byte aligned first column, Cpad %% 8 == 0 and ldp %% 8 == 0 (Cpad=%d ldp=%d)", who, Cpad, ldp);
+    CtBwdArgs p{gv, y, a, b, mean, rstd, sums, gsums, dy, (uint16_t*)dy_planes, dgamma, dbeta, M, Mtot, C, Cpad, ldg, ldy, ldd, ldp, act, has_bn};
     if (Cpad % 8 == 0)
         hipLaunchKernelGGL(ct_act_bwd_kernel<8>, dim3(rowbn_grid(M * (Cpad / 8))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(ct_act_bwd_kernel<4>, dim3(rowbn_grid(M * (Cpad / 4))), dim3(ROWBN_THREADS), 0, (hipStream_t)stream, p);
-    RPB_CHECK_LAUNCH("rowbn_act_bwd_apply");
+    RPB_CHECK_LAUNCH(who);
+}
+
+extern "C" int rpb_rowbn_act_bwd_apply(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b, const float* mean,
+                                       const float* rstd, const double* sums, long M, int C, int Cpad, int act, int has_bn, float* dy,
+                                       int ldd, void* dy_planes, int ldp, float* dgamma, float* dbeta, void* stream) {
+    return rowbn_bwd_apply("rowbn_act_bwd_apply", gv, ldg, y, ldy, a, b, mean, rstd, sums, sums, M, M, C, Cpad, act, has_bn, dy, ldd, dy_planes,
+                           ldp, dgamma, dbeta, stream);
+}
+
+// The BatchNorm form (has_bn = 1) over the rows of several ranks.  With sums_global == sums_local and M_total == M it has the bits of
+// rpb_rowbn_act_bwd_apply: the same kernel, the same expression per element.
+extern "C" int rpb_rowbn_act_bwd_apply_sync(const float* gv, int ldg, const float* y, int ldy, const float* a, const float* b,
+                                            const float* mean, const float* rstd, const double* sums_local, const double* sums_global, long M,
+                                            long M_total, int C, int Cpad, int act, float* dy, int ldd, void* dy_planes, int ldp,
+                                            float* dgamma, float* dbeta, void* stream) {
+    return rowbn_bwd_apply("rowbn_act_bwd_apply_sync", gv, ldg, y, ldy, a, b, mean, rstd, sums_local, sums_global, M, M_total, C, Cpad, act, 1,
+                           dy, ldd, dy_planes, ldp, dgamma, dbeta, stream);
 }

@@ -204,13 +204,17 @@ def layer_buckets(seg, n_layers, total):
 class StatsSync:
     """SyncBN-only hook for models whose parameter gradients are reduced by the trainer after backward (the Galerkin
     Transformer: its spectral regressor is an FNO block with a training-mode BatchNorm3d, galerkin_transformer_libs/
-    model.py:572,622): global-batch statistics forward and backward, no gradient buckets."""
+    model.py:572,622): global-batch statistics forward and backward, no gradient buckets.  ``trainer.ArenaTrainer`` also attaches one, as
+    ``bn_sync``, to a CNO3d or DeepONet instance enabled with ``sync_bn=True`` (``model._common.batch_norm_rows``).
+    ``sync_stats_always`` (RPB_DP_SYNCBN_ALWAYS=1, as for ``DataParallel``): a one-rank group runs the reductions anyway, so that its step
+    contains every launch of the N-rank step."""
 
     def __init__(self, process_group=None, comm=None):
         self.group = process_group
         self.world_size = dist.get_world_size(process_group)
         self.rank = dist.get_rank(process_group)
         self.comm = comm
+        self.sync_stats_always = os.environ.get("RPB_DP_SYNCBN_ALWAYS") == "1"
 
     def all_reduce_sum(self, t):
         if self.comm is not None and t.is_cuda:

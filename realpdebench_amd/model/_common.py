@@ -112,37 +112,68 @@ def weight_grad_view(dW, Co, Ci, N, K):
     return dW.view(N, 3, 3, 3, K)[:Co, :, :, :, :Ci].permute(0, 4, 1, 2, 3).contiguous()
 
 
-def batch_norm_rows(y, ld, M, C, bn, parts=None):
+def reduces_stats(sync):
+    """Does ``sync`` (None, or ``dp.StatsSync``) sum the BatchNorm statistics over its ranks?  A one-rank group has nothing to sum and runs
+    the plain launches, unless ``sync_stats_always`` asks for every launch of the N-rank step (RPB_DP_SYNCBN_ALWAYS=1)."""
+    return sync is not None and (sync.world_size > 1 or sync.sync_stats_always)
+
+
+def batch_norm_rows(y, ld, M, C, bn, parts=None, sync=None):
     """Batch statistics of y [M][ld] (csrc/rpb_rowbn.hip) -> ab [4][C] = (a, b, mean, rstd), a = gamma rstd, b = beta - mean a; the running
     statistics of ``bn`` are updated on the device (``num_batches_tracked`` is the caller's).  C = 256 runs as two column halves.
     ``parts``: fp64 partials already accumulated (a forward in chunks of samples), [2 if C == 256 else 1][rows][2 Ch].
-    M < 2 raises torch's ValueError before anything is launched (CNO3d cannot get there: its input has T > in_dim >= 1, so M >= 2); the
-    version counters of the running statistics are bumped here, once per call."""
-    if M < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size [{M} cells, {C} channels]")
+    ``sync`` (``dp.StatsSync``; None: one rank, today's launches): SyncBN over its W ranks, each with M rows (equal per-rank batches, as
+    in FNO3d's SyncBN).  The local partials are summed in their fixed order (``rowbn_sum64``), the sums of all halves travel in ONE
+    all-reduce, and ``rowbn_finish_sums`` forms the statistics of the M_total = W M rows (biased variance; the running variance with
+    M_total / (M_total - 1)): every rank then holds the same ab and the same running statistics.  The call is collective.
+    M_total < 2 raises torch's ValueError before anything is launched (CNO3d cannot get there: its input has T > in_dim >= 1, so M >= 2);
+    the version counters of the running statistics are bumped here, once per call."""
+    reduces = reduces_stats(sync)
+    Mt = M * sync.world_size if reduces else M
+    if Mt < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size [{Mt} cells, {C} channels]")
     Ch, nh = min(C, 128), max(1, C // 128)
     if parts is None:
         parts = torch.empty(nh, ops.rowbn_rows(), 2 * Ch, device=y.device, dtype=torch.float64)
         for h in range(nh):
             ops.rowbn_stats(ops.Sub(y, h * Ch), ld, M, Ch, parts[h])
     ab = torch.empty(4, C, device=y.device, dtype=torch.float32)
+    if reduces:
+        sums = torch.empty(nh, 2 * Ch, device=y.device, dtype=torch.float64)
+        for h in range(nh):
+            ops.rowbn_sum64(parts[h], parts.shape[1], Ch, sums[h])
+        sync.all_reduce_sum(sums.view(-1))
     for h in range(nh):
         o = h * Ch
-        ops.rowbn_finish(parts[h], parts.shape[1], M, Ch, ops.Sub(bn.weight.data, o), ops.Sub(bn.bias.data, o), ops.Sub(bn.running_mean, o),
-                         ops.Sub(bn.running_var, o), bn.eps, bn.momentum, *(ops.Sub(ab, k * C + o) for k in range(4)))
+        out = (ops.Sub(bn.weight.data, o), ops.Sub(bn.bias.data, o), ops.Sub(bn.running_mean, o), ops.Sub(bn.running_var, o), bn.eps,
+               bn.momentum, *(ops.Sub(ab, k * C + o) for k in range(4)))
+        if reduces:
+            ops.rowbn_finish_sums(sums[h], Mt, Ch, *out)
+        else:
+            ops.rowbn_finish(parts[h], parts.shape[1], M, Ch, *out)
     torch.autograd.graph.increment_version(bn.running_mean)           # written through raw pointers: the layout cache is keyed on these
     torch.autograd.graph.increment_version(bn.running_var)
     return ab
 
 
-def batch_norm_rows_bwd(part, gv, ldg, y, ldy, ab, M, C, Cpad, act, dy, ldd, dy_planes=None, ldp=0):
+def batch_norm_rows_bwd(part, gv, ldg, y, ldy, ab, M, C, Cpad, act, dy, ldd, dy_planes=None, ldp=0, sync=None):
     """The tail of a BatchNorm backward, from the fp64 partials ``part`` [rows][2 C] of (sum dz, sum dz xhat): their fixed-order sum, then
-    dy = a (dz - sum dz / M - xhat sum dz xhat / M) as fp32 rows (``dy`` may be ``gv``) and bf16 planes.  Returns (dgamma, dbeta)."""
+    dy = a (dz - sum dz / M - xhat sum dz xhat / M) as fp32 rows (``dy`` may be ``gv``) and bf16 planes.  Returns (dgamma, dbeta).
+    ``sync`` (as in ``batch_norm_rows``; the call is collective): the sums inside dy are those of all W ranks (one all-reduce of a copy)
+    over M_total = W M rows, while dgamma and dbeta stay this rank's own sums -- each rank differentiates the mean over ITS samples, and
+    the trainer's mean over the ranks turns them into the gradients of the global batch (the global sums there would be W times too
+    large)."""
     sums = torch.empty(2 * C, device=part.device, dtype=torch.float64)
     dgb = torch.empty(2, C, device=part.device, dtype=torch.float32)
     ops.rowbn_sum64(part, part.shape[0], C, sums)
-    ops.rowbn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=y, ldy=ldy, a=ab[0], b=ab[1], mean=ab[2], rstd=ab[3], sums=sums, dy=dy, ldd=ldd,
-                            dy_planes=dy_planes, ldp=ldp, dgamma=dgb[0], dbeta=dgb[1])
+    if reduces_stats(sync):
+        gsums = sums.clone()
+        sync.all_reduce_sum(gsums)
+        ops.rowbn_act_bwd_apply_sync(gv, ldg, M, M * sync.world_size, C, Cpad, act, y, ldy, ab[0], ab[1], ab[2], ab[3], sums, gsums, dy=dy,
+                                     ldd=ldd, dy_planes=dy_planes, ldp=ldp, dgamma=dgb[0], dbeta=dgb[1])
+    else:
+        ops.rowbn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=y, ldy=ldy, a=ab[0], b=ab[1], mean=ab[2], rstd=ab[3], sums=sums, dy=dy, ldd=ldd,
+                                dy_planes=dy_planes, ldp=ldp, dgamma=dgb[0], dbeta=dgb[1])
     return dgb[0], dgb[1]
 
 
@@ -189,17 +220,30 @@ class EvalByDefault:
     hip_training = False               # enable_training() sets it on the instance
     dp_unavailable = None              # enabled instances: why trainer.make_trainer refuses more than one rank (the class's DP_MSG)
     DP_MSG = None                      # the class's reason
+    sync_bn = False                    # enable_training(sync_bn=True) sets it on the instance: BatchNorm over the global batch
+    bn_sync = None                     # the ``dp.StatsSync`` a trainer attaches to a ``sync_bn`` instance under a process group
     # The class's training step computes BatchNorm statistics over the batch: they couple the samples of a step, so an enabled instance
     # stops declaring ``batch_independent`` (no micro-batching).
     BATCH_STATISTICS = False
 
-    def enable_training(self):
-        """Opt this instance into the HIP training step (``hip_training: true`` in a config)."""
+    def enable_training(self, sync_bn=False):
+        """Opt this instance into the HIP training step (``hip_training: true`` in a config).
+
+        ``sync_bn`` (``sync_bn: true`` next to it; the ``BATCH_STATISTICS`` models, CNO3d and DeepONet): the instance trains
+        data-parallel.  ``trainer.make_trainer`` then accepts more than one rank (``dp_unavailable`` is None) and attaches a
+        ``dp.StatsSync`` as ``bn_sync``; BatchNorm statistics and their backward sums are taken over the global batch
+        (``batch_norm_rows``), so N ranks with B / N samples each take the step one rank takes on all B samples.  Per-rank batches must
+        be equal.  Every ``train()``-mode forward of such an instance under a process group is COLLECTIVE, a ``torch.no_grad()`` one
+        included: all ranks must call it together.  ``eval()`` mode uses the running statistics and is untouched.  On one rank the flag
+        changes no launch."""
+        if sync_bn and not self.BATCH_STATISTICS:
+            raise ValueError(f"{type(self).__name__} has no BatchNorm statistics to synchronise: sync_bn is for CNO3d and DeepONet")
         self.hip_training = True
         self.training_unavailable = None
         if self.BATCH_STATISTICS:
             self.batch_independent = False
-        self.dp_unavailable = self.DP_MSG
+        self.sync_bn = bool(sync_bn)
+        self.dp_unavailable = None if self.sync_bn else self.DP_MSG
         return self
 
     def _require_eval(self, x):

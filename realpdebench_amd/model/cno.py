@@ -8,8 +8,9 @@ at full resolution, each followed by an eval BatchNorm3d, LeakyReLU(0.2), a resi
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
 every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``), ``trainer.make_trainer`` refuses the model at
 construction and BatchNorm3d uses its running statistics in every mode.  ``enable_training()`` (``hip_training: true`` through
-``load_model``) opts an instance in: in ``train()`` mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction`` with
-batch-statistics BatchNorm (csrc/rpb_rowbn.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
+``load_model``; ``sync_bn=True`` / ``sync_bn: true`` for data-parallel training with SyncBN) opts an instance in:
+in ``train()`` mode ``forward`` / ``train_loss`` then run through ``_common.HipFunction`` with batch-statistics BatchNorm
+(csrc/rpb_rowbn.hip), the data gradient is rpb_cno_conv3x on flipped, transposed taps (the exact-fp32
 implicit GEMM for the seven ``EXACT_DGRAD`` layers) and the weight gradient is ``_common.wgrad``; ``eval()`` mode stays the code below,
 untouched.
 
@@ -238,9 +239,12 @@ class CNO3d(EvalByDefault, Model):
     batch_independent = True                       # BatchNorm runs on its running statistics only
     training_unavailable = EvalByDefault.TRAIN_MSG.format("CNO", "CNO3d")
     # An enabled instance computes batch statistics: they couple the samples of a step, so it stops declaring ``batch_independent`` (no
-    # micro-batching) and refuses more than one rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for CNO is not built).
+    # micro-batching) and refuses more than one rank (per-rank statistics would break "N ranks == 1 rank") unless it was enabled with
+    # ``sync_bn=True``: then the statistics of every BatchNorm layer, forward and backward, are summed over the ranks (the ``dp.StatsSync``
+    # the trainer attaches as ``bn_sync``; ``_common.batch_norm_rows``), and every ``train()``-mode forward is collective.
     BATCH_STATISTICS = True
-    DP_MSG = "CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
+    DP_MSG = ("CNO3d training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank "
+              "-- or opt in with enable_training(sync_bn=True) (sync_bn: true next to hip_training: true in a config)")
 
     def __init__(self, in_dim, in_size, N_layers, N_res=1, N_res_neck=6, channel_multiplier=32, conv_kernel=3, cutoff_den=2.0001,
                  filter_size=6, lrelu_upsampling=2, half_width_mult=0.8, radial=False, batch_norm=True, out_dim=1, out_dim_mult=1,
@@ -402,7 +406,7 @@ class CNO3d(EvalByDefault, Model):
                 continue
             y = torch.empty(M, N, device=dev, dtype=torch.float32)
             self.k_conv(src.planes.ptr(), s["wz"], s["sc"], s["sh"], M, N, K, mesh, N, 0, out=y, ldo=N)
-            ab = batch_norm_rows(y, N, M, Co, bn)                     # a, b, mean, rstd
+            ab = batch_norm_rows(y, N, M, Co, bn, sync=self.bn_sync)  # a, b, mean, rstd
             ops.rowbn_act_fwd(y, N, ab[0], ab[1], M, Co, act, res=None if res is None else res.rows, ldr=0 if res is None else res.ld,
                               out=dst.at(col), ldo=dst.ld, out_planes=dst.planes.ptr(col), ldp=dst.ld)
             rec["y"], rec["ab"] = y, ab
@@ -452,7 +456,8 @@ class CNO3d(EvalByDefault, Model):
                 part = torch.empty(rows, 2 * Co, device=dev, dtype=torch.float64)
                 dy = torch.empty(M, N, device=dev, dtype=torch.float32)
                 ops.rowbn_act_bwd_stats(gv, ldg, y, N, *ab, M, Co, act, part)
-                grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part, gv, ldg, y, N, ab, M, Co, N, act, dy, N, dy_planes=dyp, ldp=N)
+                grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part, gv, ldg, y, N, ab, M, Co, N, act, dy, N, dy_planes=dyp, ldp=N,
+                                                                           sync=self.bn_sync)
             elif act:                                                 # lift.0 / project.0: the gate from the sign of the saved v
                 dy = torch.empty(M, N, device=dev, dtype=torch.float32)
                 ops.rowbn_act_bwd_apply(gv, ldg, M, Co, N, 1, y=dst.rows, ldy=dst.ld, dy=dy, ldd=N, dy_planes=dyp, ldp=N)

@@ -4,7 +4,8 @@
 Evaluation forward, ``train_loss`` as a value, the autoregressive rollout and checkpoint I/O.  By default the training step is refused:
 every attempt to backpropagate raises ``NotImplementedError`` (``_common.EvalByDefault``) instead of returning tensors without a graph,
 ``trainer.make_trainer`` refuses the model at construction, dropout is the identity and BatchNorm3d uses its running statistics in
-every mode.  ``enable_training()`` (``hip_training: true`` through ``load_model``) opts an instance in: in ``train()`` mode ``forward`` /
+every mode.  ``enable_training()`` (``hip_training: true`` through ``load_model``; ``sync_bn=True`` / ``sync_bn: true`` for data-parallel
+training with SyncBN) opts an instance in: in ``train()`` mode ``forward`` /
 ``train_loss`` then run through ``_common.HipFunction`` with batch-statistics BatchNorm and active dropout (``_forward_hip`` /
 ``_backward_hip`` below, csrc/rpb_rowbn.hip and csrc/rpb_deeponet_train.hip); ``eval()`` mode stays the pipeline
 below, untouched.
@@ -35,7 +36,8 @@ import torch.nn as nn
 from .. import _lib, ops
 from ..ops import Sub, _p, _stream, amax_exp, conv3_f16x2_weights, conv3x, conv3x_f16x2, conv3x_wprep, reduce_partials, split2h, split3
 from ..ops import add as ops_add
-from ._common import EvalByDefault, batch_norm_rows, batch_norm_rows_bwd, flipped_weight, padded_weight, weight_grad_view, wgrad
+from ._common import (EvalByDefault, batch_norm_rows, batch_norm_rows_bwd, flipped_weight, padded_weight, reduces_stats, weight_grad_view,
+                      wgrad)
 from .model import Model
 
 I16 = torch.int16
@@ -156,6 +158,17 @@ class _Trunk(nn.Module):
         self.fc = nn.Sequential(nn.Linear(3, 64), nn.ReLU(), nn.Linear(64, 128), nn.ReLU(), nn.Linear(128, p))
 
 
+RANK_SEED_SHIFT = 56           # the rank enters the dropout seed base above every step a run reaches (``rank_seed_base``)
+
+
+def rank_seed_base(base, rank):
+    """The base of rank ``rank``'s dropout seeds: ``(base + rank * 2^56) mod 2^62``.  ``train.py`` seeds every rank alike, so without
+    the rank all ranks would draw one mask.  Rank 0 keeps ``base`` (the single-rank seeds); the seeds of ``drop_seed`` over distinct
+    (rank, step, layer, chunk) are distinct for rank < 64 and step < 2^32."""
+    assert 0 <= rank < 1 << (62 - RANK_SEED_SHIFT)
+    return (int(base) + (int(rank) << RANK_SEED_SHIFT)) % (1 << 62)
+
+
 def drop_seed(base, step, layer, chunk):
     """The Philox seed of one dropout launch of the training step: ``(base + step * 2^24 + layer * 2^22 + chunk) mod 2^62``.  ``base``:
     the instance's ``dropout_seed``; ``step``: the number of training forwards the instance has run (one per optimiser step: batch
@@ -175,7 +188,8 @@ class DeepONet(EvalByDefault, Model):
     batch_independent = True                        # BatchNorm runs on its running statistics only
     training_unavailable = EvalByDefault.TRAIN_MSG.format("DeepONet", "DeepONet")
     BATCH_STATISTICS = True                         # an enabled instance: see enable_training
-    DP_MSG = "DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank"
+    DP_MSG = ("DeepONet training computes BatchNorm statistics per rank: data-parallel training (SyncBN) is not built, run it on one rank "
+              "-- or opt in with enable_training(sync_bn=True) (sync_bn: true next to hip_training: true in a config)")
     _point_rows = _POINT_ROWS                       # (tests force several chunks by lowering it on an instance)
     # what set_arith("f16x2") moves: the output net ("point") and branch stages 2-4 ("convs"; tools/deeponet_probe.py measures both)
     ALL_F16X2_SITES = F16X2_SITES = ("point", "convs")
@@ -205,11 +219,16 @@ class DeepONet(EvalByDefault, Model):
         self.dropout_seed, self._drop_step, self._mask_override = 0, 0, None      # the opt-in training step, see enable_training / drop_seed
 
     # ------------------------------------------------------------------ the opt-in training step
-    def enable_training(self, seed=None):
+    def enable_training(self, seed=None, sync_bn=False):
         """Opt this instance into the HIP training step (batch-statistics BatchNorm, active dropout; ``hip_training: true`` in a config).
         Batch statistics couple the samples of a step, so the instance stops declaring ``batch_independent`` (no micro-batching) and
-        refuses more than one rank (per-rank statistics would break "N ranks == 1 rank"; SyncBN for DeepONet is not built).  ``seed``:
-        the base of the dropout seeds (``drop_seed``); default: torch's initial seed, as the trainer's run was seeded.
+        refuses more than one rank (per-rank statistics would break "N ranks == 1 rank") unless ``sync_bn`` is set (``sync_bn: true``):
+        then the four BatchNorm layers take their statistics and backward sums over the global batch through the ``dp.StatsSync`` the
+        trainer attaches as ``bn_sync`` (``_common.EvalByDefault.enable_training``; equal per-rank batches), every ``train()``-mode
+        forward -- a ``torch.no_grad()`` one included -- is collective, ``eval()`` is untouched, and the rank enters the base of the
+        dropout seeds (``rank_seed_base``: rank 0 draws the single-rank masks, the others their own).  An explicit ``_mask_override``
+        holds the rank's own rows.  ``seed``: the base of the dropout seeds (``drop_seed``); default: torch's initial seed, as the
+        trainer's run was seeded.
 
         The step number of the seeds, ``_drop_step``, counts the training forwards this INSTANCE has completed since this call: a
         ``no_grad`` forward in ``train()`` mode uses one up like a step with a graph, a forward that raises uses none.  It is not part of
@@ -217,7 +236,7 @@ class DeepONet(EvalByDefault, Model):
         step 0 and redraws the masks of the first steps; a caller that minds sets ``model._drop_step`` to the resumed iteration."""
         self.dropout_seed = int(torch.initial_seed() if seed is None else seed) % (1 << 62)
         self._drop_step = 0
-        return super().enable_training()
+        return super().enable_training(sync_bn=sync_bn)
 
     # ------------------------------------------------------------------ kernel-side layouts
     def _prep(self, device):
@@ -511,10 +530,9 @@ class DeepONet(EvalByDefault, Model):
         _lib.call("rpb_don_point_mul_bwd", _p(gx), _p(t), _p(b), _p(gt), _p(part), n0, R, N, p, _stream(), label="don_point_mul_bwd",
                   nbytes=16 * R * p)
 
-    @staticmethod
-    def _bn_batch(y, ld, M, C, bn, parts=None):
+    def _bn_batch(self, y, ld, M, C, bn, parts=None):
         """``batch_norm_rows`` and the stage's batch counter"""
-        ab = batch_norm_rows(y, ld, M, C, bn, parts)
+        ab = batch_norm_rows(y, ld, M, C, bn, parts, sync=self.bn_sync)
         bn.num_batches_tracked += 1
         return ab
 
@@ -525,7 +543,8 @@ class DeepONet(EvalByDefault, Model):
         if self._mask_override is not None:
             m = self._mask_override[layer]
             return Sub(m, row0 * m.shape[1])
-        return (drop_seed(self.dropout_seed, step, layer, chunk), 1.0 - self.dropout_rate)
+        rank = self.bn_sync.rank if self.bn_sync is not None else 0
+        return (drop_seed(rank_seed_base(self.dropout_seed, rank), step, layer, chunk), 1.0 - self.dropout_rate)
 
     def _point_chunk(self, prep, t, b, q0, R, B, N, step, ci):
         """x, h1, h2 of the points q0 .. q0 + R - 1 (forward, and the backward's recomputation with the same seeds / masks)."""
@@ -547,8 +566,9 @@ class DeepONet(EvalByDefault, Model):
         B, T, H, W, Cin = x.shape
         T_out, p, Cout = self.shape_out[0], self.p, self.output_channels
         prep, ext, rows = self._prep_train(dev), pooled_extents(T, H, W), ops.rowbn_rows()
+        world = self.bn_sync.world_size if reduces_stats(self.bn_sync) else 1       # SyncBN: the statistics see the rows of every rank
         for Ti, Hi, Wi in ext:                                        # before anything is launched: no statistic moves, no step is used up
-            if B * Ti * Hi * Wi < 2:
+            if world * B * Ti * Hi * Wi < 2:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size [{B}, C, {Ti}, {Hi}, {Wi}]")
         step = self._drop_step
         stages = []
@@ -669,7 +689,8 @@ class DeepONet(EvalByDefault, Model):
             dy = torch.empty(M, Nw, **f)
             part64 = torch.empty(rows, 2 * C, device=dev, dtype=torch.float64)
             self.k_pool_bwd(y, Nw, g, ldg, ab, dy, Nw, B, Ti, Hi, Wi, C, 1 if i == 4 else 0, part64)
-            grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part64, dy, Nw, y, Nw, ab, M, C, Nw, 0, dy, Nw)       # in place on dy
+            grads[bn.weight], grads[bn.bias] = batch_norm_rows_bwd(part64, dy, Nw, y, Nw, ab, M, C, Nw, 0, dy, Nw,
+                                                                       sync=self.bn_sync)       # in place on dy
             if i == 1:                                                  # the im2col GEMM form, chunked like the forward
                 cells = Ti * Hi * Wi
                 nb = max(1, _COL_FLOATS // (cells * s["K"]))

@@ -12,6 +12,10 @@ def load_model(train_dataset, device="cpu", **kwargs):
     logging.info(f"Loading model {model_name} with input shape {input_shape} and output shape {output_shape}")
     # opt-in of mwt, deeponet and cno to their HIP training step (``EvalByDefault.enable_training``); it never reaches a constructor
     hip_training = model_name in ("mwt", "deeponet", "cno") and kwargs.pop("hip_training", False)
+    # ``sync_bn: true`` next to it (cno, deeponet): BatchNorm statistics over the global batch, so that the instance trains data-parallel
+    sync_bn = model_name in ("deeponet", "cno") and kwargs.pop("sync_bn", False)
+    if sync_bn and not hip_training:
+        raise ValueError("sync_bn: true needs hip_training: true (it is a switch of the opt-in HIP training step)")
     if model_name == "fno":
         from .fno import FNO3d
         model = FNO3d(
@@ -73,5 +77,5 @@ def load_model(train_dataset, device="cpu", **kwargs):
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
                          "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno)")
     if hip_training:
-        model.enable_training()
+        model.enable_training(**({"sync_bn": True} if sync_bn else {}))
     return model

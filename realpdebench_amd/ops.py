@@ -1226,3 +1226,19 @@ def rowbn_act_bwd_apply(gv, ldg, M, C, Cpad, act, y=None, ldy=0, a=None, b=None,
               M, C, Cpad, int(act), int(sums is not None), _ptr(dy), ldd, _ptr(dy_planes, torch.int16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(),
               label="rowbn_act_bwd_apply",
               nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))
+
+
+def rowbn_finish_sums(sums, M_total, C, gamma, beta, rmean, rvar, eps, momentum, a, b, mean, rstd):
+    """``rowbn_finish`` from sums [2 C] = (sum y, sum y^2) over ``M_total`` rows (SyncBN: the all-reduced ``rowbn_sum64`` of every rank)"""
+    _lib.call("rpb_rowbn_finish_sums", _ptr(sums, torch.float64), M_total, C, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), float(eps),
+              float(momentum), _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd), _stream(), label="rowbn_finish_sums", nbytes=16 * C)
+
+
+def rowbn_act_bwd_apply_sync(gv, ldg, M, M_total, C, Cpad, act, y, ldy, a, b, mean, rstd, sums_local, sums_global, dy=None, ldd=0,
+                             dy_planes=None, ldp=0, dgamma=None, dbeta=None):
+    """The BatchNorm form of ``rowbn_act_bwd_apply`` over the rows of several ranks: dy from ``sums_global`` / ``M_total``, dgamma and
+    dbeta from ``sums_local`` (this rank's part of them)."""
+    _lib.call("rpb_rowbn_act_bwd_apply_sync", _ptr(gv), ldg, _ptr(y), ldy, _ptr(a), _ptr(b), _ptr(mean), _ptr(rstd),
+              _ptr(sums_local, torch.float64), _ptr(sums_global, torch.float64), M, M_total, C, Cpad, int(act), _ptr(dy), ldd,
+              _ptr(dy_planes, torch.int16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(), label="rowbn_act_bwd_apply_sync",
+              nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))

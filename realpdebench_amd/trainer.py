@@ -205,6 +205,16 @@ class ArenaTrainer:
             core = getattr(model, "regressor", None)
             if core is not None and hasattr(core, "dp"):
                 core.dp = StatsSync(dp_group, comm=self.comm)       # BatchNorm3d over the global batch (SyncBN)
+            if getattr(model, "sync_bn", False):                    # CNO3d / DeepONet enabled with sync_bn=True: the same, in every layer
+                model.bn_sync = StatsSync(dp_group, comm=self.comm)
+        elif (getattr(model, "sync_bn", False) and os.environ.get("RPB_DP_SYNCBN_ALWAYS") == "1" and torch.distributed.is_available()
+              and torch.distributed.is_initialized()):
+            # the one-GPU proxy: a one-rank group runs every reduction and both SyncBN kernels of the N-rank step (sums over one rank:
+            # the same values); without the switch a flagged one-rank run issues the plain launches
+            from .dp import RcclComm, StatsSync, use_rccl_abi
+            if use_rccl_abi(self.flat, dp_group):
+                self.comm = RcclComm(dp_group)
+            model.bn_sync = StatsSync(dp_group, comm=self.comm)
         # p2p (opt-in, RPB_DP_P2P=1): gradients and parameters travel over peer pointers inside the update kernel (dp.PeerExchange,
         # rpb_dp_p2p_*) instead of all-reduce buckets + a full-arena Adam on every rank; nothing is enqueued during backward
         self.peer = None

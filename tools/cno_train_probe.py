@@ -3,10 +3,13 @@
 after 3 warm-ups), the eval forward of the same run next to it, the per-launch HIP-event table by kernel family (the ``label``s of
 model/cno.py and ops.py), the share of the new row kernels (csrc/rpb_rowbn.hip) and ``torch.cuda.max_memory_allocated``.
 Launches under ~100 us are dominated by the event overhead in the table.
-    python tools/cno_train_probe.py [--batches 1 2 4] [--runs 10] [--out profiles/cno_train_probe.txt]"""
+    python tools/cno_train_probe.py [--batches 1 2 4] [--runs 10] [--out profiles/cno_train_probe.txt]
+``--sync-bn``: what SyncBN costs a rank (``sync_vs_plain`` below), instead of the table.
+    python tools/cno_train_probe.py --sync-bn [--batches 1 2 4] [--runs 5] [--repeats 3] [--out profiles/cno_syncbn_probe.txt]"""
 import argparse
 import os
 import re
+import statistics
 import sys
 
 import torch
@@ -25,14 +28,70 @@ def family(label):
     return re.sub(r"\[.*\]$", "", label)
 
 
+def sync_vs_plain(title, new_model, shape, batches, runs, repeats, backend):
+    """The syncing step against the plain step of the same process, on a one-rank process group with RPB_DP_SYNCBN_ALWAYS=1: the syncing
+    instance (``enable_training(sync_bn=True)``) then runs every launch of the N-rank step -- per BatchNorm layer one more rowbn_sum64, the
+    finish from sums, a copy of the backward sums and two all-reduces over one rank -- but no byte crosses a link.  Per batch size the
+    two steps are timed alternately, ``repeats`` times each (median of ``runs`` after 3 warm-ups); reported: the median of those medians
+    and their spread (min .. max).  ``new_model(**enable_training arguments)`` builds an enabled instance on the device."""
+    import torch.distributed as dist
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29531")
+    os.environ["RPB_DP_SYNCBN_ALWAYS"] = "1"
+    dist.init_process_group(backend, rank=0, world_size=1)
+    lines = [f"{title}, shape {shape}: SyncBN step against the plain step, one process, one-rank {backend} group, RPB_DP_SYNCBN_ALWAYS=1",
+             "(the one-rank proxy: every launch of the N-rank step, no link traffic; no run with more than one rank on RCCL has taken place)"]
+    trs = {}
+    try:
+        torch.manual_seed(0)
+        plain, sync = new_model(), new_model(sync_bn=True)
+        trs["plain"], trs["sync"] = make_trainer(plain, lr=1e-4, num_update=10000), make_trainer(sync, lr=1e-4, num_update=10000)
+        assert plain.bn_sync is None and sync.bn_sync is not None and sync.bn_sync.sync_stats_always
+        lines.append(f"reductions: {'RCCL through the C ABI (rpb_dp_allreduce_inline)' if sync.bn_sync.comm is not None else 'torch.distributed'}")
+        for B in batches:
+            x, y = torch.randn(B, *shape, device=DEV), torch.randn(B, *shape, device=DEV)
+            meds = {"plain": [], "sync": []}
+            for _ in range(repeats):
+                for k in ("sync", "plain"):
+                    meds[k].append(median_ms(lambda: trs[k].step(x, y), runs)[0])
+            mp, ms = statistics.median(meds["plain"]), statistics.median(meds["sync"])
+            lines.append(f"B={B}: plain step {mp:.2f} ms (medians {min(meds['plain']):.2f} .. {max(meds['plain']):.2f}); syncing step {ms:.2f} ms "
+                         f"(medians {min(meds['sync']):.2f} .. {max(meds['sync']):.2f}); sync - plain = {ms - mp:+.2f} ms = {(ms - mp) / mp:+.4f} "
+                         f"of the plain step; {repeats} alternating repeats of the median of {runs} runs after 3 warm-ups")
+            del x, y
+            torch.cuda.empty_cache()
+    finally:
+        for tr in trs.values():
+            tr.close()
+        dist.destroy_process_group()
+    return lines
+
+
+def emit(lines, out):
+    txt = "\n".join(lines)
+    print(txt)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(txt + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4])
-    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--runs", type=int, default=None, help="default 10; 5 with --sync-bn")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sync-bn", action="store_true", help="time the SyncBN step against the plain step (sync_vs_plain)")
+    ap.add_argument("--repeats", type=int, default=3, help="--sync-bn: alternating repeats of each median")
+    ap.add_argument("--backend", default="nccl", help="--sync-bn: backend of the one-rank process group")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/cno_train_probe.py measures on an MI355X: no GPU, no number")
+    if a.sync_bn:
+        new = lambda **kw: CNO3d(in_dim=SHAPE[-1], in_size=SHAPE[1], N_layers=3, out_dim=SHAPE[-1]).to(DEV).enable_training(**kw)
+        return emit(sync_vs_plain("CNO3d N_layers = 3, opt-in training step (ArenaTrainer.step)", new, SHAPE, a.batches, a.runs or 5, a.repeats,
+                                  a.backend), a.out)
+    a.runs = a.runs or 10
     torch.manual_seed(0)
     m = CNO3d(in_dim=SHAPE[-1], in_size=SHAPE[1], N_layers=3, out_dim=SHAPE[-1]).to(DEV).enable_training()
     tr = make_trainer(m, lr=1e-4, num_update=10000)
@@ -68,12 +127,7 @@ def main():
                          f"{v['tf'] / t:>9.2f}")
         del x, y
         torch.cuda.empty_cache()
-    txt = "\n".join(lines)
-    print(txt)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(txt + "\n")
+    emit(lines, a.out)
 
 
 if __name__ == "__main__":

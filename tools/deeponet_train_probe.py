@@ -4,7 +4,9 @@ batch size (median of 10 after 3 warm-ups), the eval forward of the same run nex
 family (the ``label``s of model/deeponet.py, model/_common.py and ops.py), the share of the new row kernels
 (csrc/rpb_deeponet_train.hip and the BatchNorm backward tail of csrc/rpb_rowbn.hip) and ``torch.cuda.max_memory_allocated``.  Launches under ~100 us are dominated by the event overhead in
 the table.  No speed threshold: the step / forward ratio is recorded, not asserted.
-    python tools/deeponet_train_probe.py [--batches 1 4] [--runs 10] [--out profiles/deeponet_train_probe.txt]"""
+    python tools/deeponet_train_probe.py [--batches 1 4] [--runs 10] [--out profiles/deeponet_train_probe.txt]
+``--sync-bn``: what SyncBN costs a rank (``tools.cno_train_probe.sync_vs_plain``), instead of the table.
+    python tools/deeponet_train_probe.py --sync-bn [--batches 1 4] [--runs 5] [--repeats 3] [--out profiles/deeponet_syncbn_probe.txt]"""
 import argparse
 import os
 import re
@@ -17,6 +19,7 @@ from realpdebench_amd import _lib                         # noqa: E402
 from realpdebench_amd.model.deeponet import DeepONet      # noqa: E402
 from realpdebench_amd.trainer import make_trainer         # noqa: E402
 from tools.cno_probe import DEV, HBM_PEAK, median_ms      # noqa: E402
+from tools.cno_train_probe import emit, sync_vs_plain     # noqa: E402
 from tools.deeponet_probe import P, SHAPE                 # noqa: E402
 
 ROW_KERNELS = ("don_pool_bwd", "rowbn_sum64", "rowbn_act_bwd_apply", "don_point_mul", "don_point_mul_bwd")
@@ -30,11 +33,19 @@ def family(label):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4])
-    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--runs", type=int, default=None, help="default 10; 5 with --sync-bn")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sync-bn", action="store_true", help="time the SyncBN step against the plain step (sync_vs_plain)")
+    ap.add_argument("--repeats", type=int, default=3, help="--sync-bn: alternating repeats of each median")
+    ap.add_argument("--backend", default="nccl", help="--sync-bn: backend of the one-rank process group")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/deeponet_train_probe.py measures on an MI355X: no GPU, no number")
+    if a.sync_bn:
+        new = lambda **kw: DeepONet(SHAPE, SHAPE, SHAPE[-1], SHAPE[-1], P, dropout_rate=0.1).to(DEV).enable_training(**kw)
+        return emit(sync_vs_plain(f"DeepONet p = {P}, dropout 0.1, opt-in training step (ArenaTrainer.step)", new, SHAPE, a.batches, a.runs or 5,
+                                  a.repeats, a.backend), a.out)
+    a.runs = a.runs or 10
     torch.manual_seed(0)
     m = DeepONet(SHAPE, SHAPE, SHAPE[-1], SHAPE[-1], P, dropout_rate=0.1).to(DEV).enable_training()
     tr = make_trainer(m, lr=1e-4, num_update=10000)
@@ -70,12 +81,7 @@ def main():
                          f"{v['tf'] / t:>9.2f}")
         del x, y
         torch.cuda.empty_cache()
-    txt = "\n".join(lines)
-    print(txt)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(txt + "\n")
+    emit(lines, a.out)
 
 
 if __name__ == "__main__":
