@@ -934,6 +934,22 @@ int rpb_afno_wprep_f16x2(const float* w, void* Wz, float* sc, int nb, int bs, vo
 int rpb_afno_mlp_f16x2(const float* X, const void* Waz, const float* sca, const float* ba, const void* Wbz, const float* scb,
                        const float* bb, float* out, long ntok, int nb, int bs, void* stream);
 
+/*
+ * DMD baseline (realpdebench/model/dmd.py; csrc/rpb_dmd.hip; additions do not change RPB_ABI_VERSION).
+ * x: fp32 [B][T][P][C] contiguous, P = H W; f <= C: the leading channels the model reads.  2 <= T <= 32, f <= 64, C <= 4096,
+ * B <= 65535; anything else is RPB_ERR_ARG.
+ *     rpb_dmd_gram: G fp64 [B][T][T], G[b][i][j] = sum over p and c < f of x[b][i][p][c] x[b][j][p][c], accumulated in fp64
+ *     (v_mfma_f64_16x16x4_f64).  part: device scratch of B * rpb_dmd_gram_groups(B, P, f) * T * T doubles (the per-workgroup partial
+ *     matrices; a second launch of the same call sums them in a fixed order).  No atomics: two calls are bit-equal, and G is
+ *     symmetric bit for bit.
+ *     rpb_dmd_predict: out fp32 [B][S][P][f], out[b][s][p][c] = sum over k < T-1 of M[b][k][s] x[b][k+1][p][c] for c < f, M fp64
+ *     [B][T-1][S], 1 <= S <= 32, accumulated in fp64 and rounded once.  Nothing is written outside out.
+ * Neither call synchronises with the host.
+ */
+int rpb_dmd_gram_groups(int B, long P, int f);
+int rpb_dmd_gram(const float* x, double* G, double* part, int B, int T, long P, int C, int f, void* stream);
+int rpb_dmd_predict(const float* x, const double* M, float* out, int B, int T, long P, int C, int f, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

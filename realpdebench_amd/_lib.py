@@ -244,6 +244,9 @@ SIGNATURES = {
     "rpb_afno_mlp_f16x2_supported": (_I, "ii"),
     "rpb_afno_wprep_f16x2": (_I, "ppp" + "ii" + "p"),
     "rpb_afno_mlp_f16x2": (_I, "pppppppp" + "lii" + "p"),
+    "rpb_dmd_gram_groups": (_I, "ili"),
+    "rpb_dmd_gram": (_I, "ppp" + "iilii" + "p"),
+    "rpb_dmd_predict": (_I, "ppp" + "iiliii" + "p"),
 }
 
 _lib = None

@@ -40,7 +40,8 @@ def main(argv=None):
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
     set_seed(args.seed)
-    exp_path = os.path.dirname(args.checkpoint_path) if args.checkpoint_path else args.results_path
+    # a checkpoint_path without a directory part (DMD's literal 'no model needed') puts the results under results_path
+    exp_path = (os.path.dirname(args.checkpoint_path) if args.checkpoint_path else "") or args.results_path
     os.makedirs(exp_path, exist_ok=True)
     setup_logging(exp_path, is_train=False)
 
@@ -73,7 +74,8 @@ METRIC_NAMES = ("rmse", "mae", "rel l2 error", "r2", "ke error", "f error", "low
 def evaluate(model, loader, normalizer, n_ar, test_batch_size):
     """The test loop of realpdebench/eval.py:286-365 on the device: returns ``(results, pred, target)`` with the
     de-normalised rollout and targets of the whole split (``None`` when the targets cover a single step only)."""
-    device = next(model.parameters()).device
+    device = next((p.device for p in model.parameters()), None) or model.device       # a parameter-free model (DMD) says where it is
+    leading = getattr(model, "PREDICTS_LEADING_CHANNELS", False)
     normalized_test_loss, n_batches, nb = 0.0, 0, 0
     pred_list, target_list = [], []
     unmeasured_c = None
@@ -89,8 +91,16 @@ def evaluate(model, loader, normalizer, n_ar, test_batch_size):
         c_out = tgt.shape[-1]
         para = inp[..., c_out:].contiguous() if inp.shape[-1] != c_out else None          # eval.py:304-308
         x, t = normalizer.preprocess(inp, tgt)
-        pred = autoregressive_rollout(model, x, n_ar, normalizer=normalizer, para_input=para)[..., :c_out].contiguous()
-        if pred.shape == t.shape:        # real test splits carry n_ar * T_out target frames; synthetic sets only T_out
+        pred = autoregressive_rollout(model, x, n_ar, normalizer=normalizer, para_input=para)
+        if leading:                      # DMD predicts f <= C_out channels: metrics and loss run over the first c of them, as in the reference
+            f = pred.shape[-1] - (para.shape[-1] if para is not None else 0)
+            if c > f:                    # the reference dies here with a broadcast error (eval.py:323)
+                raise ValueError(f"{type(model).__name__} predicts {f} channels but the targets have {c} measured (non-zero) channels: "
+                                 "the metrics cannot cover a channel the model does not predict")
+            pred = pred[..., :f].contiguous()
+        else:
+            pred = pred[..., :c_out].contiguous()
+        if pred.shape[:-1] == t.shape[:-1]:        # real test splits carry n_ar * T_out target frames; synthetic sets only T_out
             normalized_test_loss += float(((pred[..., :c] - t[..., :c]) ** 2).reshape(b, -1).mean())       # eval.py:323
             _, p = normalizer.postprocess(x, pred)
             _, tt = normalizer.postprocess(x, t)

@@ -73,9 +73,17 @@ def load_model(train_dataset, device="cpu", **kwargs):
             raise ValueError(f"Output shape {output_shape[1]} is not a multiple of input shape {input_shape[1]}")
         model = CNO3d(in_dim=input_shape[-1], out_dim=output_shape[-1], out_dim_mult=out_dim_mult, in_size=input_shape[2],
                       N_layers=kwargs["N_layers"]).to(device)
+    elif model_name == "dmd":
+        from .dmd import DMD
+        keys = ("n_modes", "n_predict", "input_feature", "N_autoregressive")                                 # load_model.py:154-156
+        missing = [k for k in keys if k not in kwargs]
+        if missing:
+            raise ValueError(f"model_name 'dmd' needs the config keys {', '.join(keys)}: missing {', '.join(missing)}")
+        model = DMD(n_modes=kwargs["n_modes"], n_predict=kwargs["n_predict"], input_feature=kwargs["input_feature"],
+                    n_autoregressive=kwargs["N_autoregressive"], shape_in=input_shape, shape_out=output_shape).to(device)
     else:
         raise ValueError(f"Model {model_name} not supported by the MI355X backend "
-                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno)")
+                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno, dmd)")
     if hip_training:
         model.enable_training(**({"sync_bn": True} if sync_bn else {}))
     return model

@@ -1242,3 +1242,26 @@ def rowbn_act_bwd_apply_sync(gv, ldg, M, M_total, C, Cpad, act, y, ldy, a, b, me
               _ptr(sums_local, torch.float64), _ptr(sums_global, torch.float64), M, M_total, C, Cpad, int(act), _ptr(dy), ldd,
               _ptr(dy_planes, torch.int16), ldp, _ptr(dgamma), _ptr(dbeta), _stream(), label="rowbn_act_bwd_apply_sync",
               nbytes=8 * M * C + M * Cpad * ((4 if dy is not None else 0) + (6 if dy_planes is not None else 0)))
+
+
+def dmd_gram(x, f):
+    """x [B,T,P,C] -> G [B,T,T] fp64, G[b,i,j] = sum over p and c < f of x[b,i,p,c] x[b,j,p,c] (fp64 accumulation, fixed order)"""
+    B, T, P, C = x.shape
+    ng = _lib.query("rpb_dmd_gram_groups", B, P, f)
+    G = torch.empty(B, T, T, device=x.device, dtype=torch.float64)
+    part = torch.empty(B * ng * T * T, device=x.device, dtype=torch.float64)
+    _lib.call("rpb_dmd_gram", _p(x), _ptr(G, torch.float64), _ptr(part, torch.float64), B, T, P, C, f, _stream(), label="dmd_gram",
+              nbytes=4 * B * T * P * C + 8 * B * T * T, flops=2 * B * T * T * P * f)
+    return G
+
+
+def dmd_predict(x, M, f):
+    """x [B,T,P,C], M [B,T-1,S] fp64 -> out [B,S,P,f] fp32, out[b,s,p,c] = sum_k M[b,k,s] x[b,k+1,p,c] (fp64 accumulation)"""
+    B, T, P, C = x.shape
+    S = M.shape[2]
+    if tuple(M.shape) != (B, T - 1, S):
+        raise _lib.RpbError(f"dmd_predict: M {tuple(M.shape)} does not fit x {tuple(x.shape)}")
+    out = torch.empty(B, S, P, f, device=x.device, dtype=F32)
+    _lib.call("rpb_dmd_predict", _p(x), _ptr(M, torch.float64), _p(out), B, T, P, C, f, S, _stream(), label="dmd_predict",
+              nbytes=4 * B * (T - 1) * P * C + 4 * B * S * P * f + 8 * B * (T - 1) * S, flops=2 * B * (T - 1) * S * P * f)
+    return out
