@@ -950,6 +950,49 @@ int rpb_dmd_gram_groups(int B, long P, int f);
 int rpb_dmd_gram(const float* x, double* G, double* part, int B, int T, long P, int C, int f, void* stream);
 int rpb_dmd_predict(const float* x, const double* M, float* out, int B, int T, long P, int C, int f, int S, void* stream);
 
+/*
+ * WDNO, the wavelet-domain diffusion operator (realpdebench/model/wdno.py; csrc/rpb_conv7x.hip, csrc/rpb_wdno.hip; additions do not change
+ * RPB_ABI_VERSION).  Everything is channels-last fp32, has a fixed summation order and no atomics (two calls are
+ * bit-equal), and no call synchronises with the host.
+ *     rpb_conv7x: out[M][ldo] (columns 0..N) = nn.Conv3d(Ci, N, KS, padding = KS / 2)(x [B][T][H][W][Ci]) + bias[N] (bias may be null),
+ *     M = B T H W, as an implicit GEMM on the bf16 MFMA from three-plane operands (six products per fp32 product, fp32 accumulation: the
+ *     default grade, as rpb_conv3x).  The A operand is gathered from x with the zero halo formed on load: no column matrix reaches
+ *     memory.  KS odd, 1..7; Ci % 8 == 0, 8 <= Ci <= 256; N = 64, 128 or 256; M < 2^31; ldo >= N -- rpb_conv7x_supported says so without
+ *     launching, anything else is RPB_ERR_ARG.  Wz: rpb_conv7x_wprep of the weight W [N][Ci][KS][KS][KS] (nn.Conv3d's own layout),
+ *     rpb_conv7x_wz_elems(N, Ci, KS) bf16 values in MFMA B-operand order, prepared once per weight.  x, Wz, out 16-byte aligned.
+ *     Nothing is read outside x[0, M Ci) and nothing is written outside out[m][0..N), m < M.
+ *     filt (rpb_wdno_dec / _rec): [4][L] = the wavelet's dec_lo, dec_hi, rec_lo, rec_hi as published; L = 2 (bior1.1) or 6 (bior1.3).
+ *     The coefficient mesh is Nc = (N + L - 1) / 2 per axis; the state is [B][Tp][Hp][Wp][ld], padded mesh >= coefficient mesh.
+ *     rpb_wdno_dec, mode 0: one level of ptwt.wavedec3(mode = "zero") of x [B][r T][H][W][C], frame sub T + t of channel c being virtual
+ *     channel c r + sub; per axis (2L - 3) / 2 zeros on each side (one more on the right of an odd length), cross-correlation with the
+ *     reversed decomposition filter at stride 2.  state column col0 + 8 (c r + sub) + s = sub-band s (aaa, aad, ada, add, daa, dad, dda,
+ *     ddd: T, H, W letters) divided by rescaler[that column] (rescaler: [ld]), zero wherever t >= Tc, h >= Hc or w >= Wc; other columns
+ *     are untouched.  ld % 4 == 0, col0 % 4 == 0.  mode 1 writes no state: part [rpb_wdno_dec_rows()][8 C r] receives per-column partial
+ *     maxima of |coefficient| (undivided; C r <= 256); the maximum over the rows is the column's maximum.
+ *     rpb_wdno_rec: the inverse for the columns from col0 on: state x rescaler through the transposed convolution at stride 2 with the
+ *     reconstruction filters, (2L - 3) / 2 trimmed per side, cropped to [T][H][W]; out [B][r T][H][W][C], out[b][sub T + t][h][w][c] from
+ *     virtual channel c r + sub.
+ *     rpb_wdno_step: the point-wise part of one sampling step over img / eps / noise / out [B][Tp][Hp][Wp][Cs]; out may be img.
+ *     sc: five scalars of device memory.  mode 0 (DDIM): x0 = clamp(sc0 img - sc1 eps, +-1), eps' = (sc0 img - x0) / sc1,
+ *     out = sc2 x0 + sc3 eps' + sc4 noise; mode 1 (last DDIM step): out = x0; mode 2 (ancestral): out = sc2 x0 + sc3 img + sc4 noise
+ *     (noise null: no noise term); mode 3 (q_sample): sc is [B][2], out = sc[b][0] img + sc[b][1] noise and out2 = noise; mode 4
+ *     (start): out = noise.  Then the input condition -- columns < Ccond are cond [cells][Ccond] (mode 3: out keeps img, out2 gets 0) --
+ *     and the pad condition (zero outside the coefficient mesh).  Products and sums are rounded one by one in the reference's order.
+ *     Cs % 4 == 0, Ccond % 4 == 0.
+ */
+int rpb_conv7x_supported(long M, int N, int Ci, int KS);
+long rpb_conv7x_wz_elems(int N, int Ci, int KS);
+int rpb_conv7x_wprep(const float* W, void* Wz, int N, int Ci, int KS, void* stream);
+int rpb_conv7x(const float* x, const void* Wz, const float* bias, float* out, int B, int T, int H, int W, int Ci, int N, int KS, int ldo,
+               void* stream);
+int rpb_wdno_dec_rows(void);
+int rpb_wdno_dec(const float* x, const float* filt, const float* rescaler, float* state, float* part, int B, int T, int H, int W, int C,
+                 int r, int L, int Tp, int Hp, int Wp, int ld, int col0, int mode, void* stream);
+int rpb_wdno_rec(const float* state, const float* filt, const float* rescaler, float* out, int B, int T, int H, int W, int C, int r, int L,
+                 int Tp, int Hp, int Wp, int ld, int col0, void* stream);
+int rpb_wdno_step(const float* img, const float* eps, const float* cond, const float* noise, const float* sc, float* out, float* out2,
+                  int B, int Tp, int Hp, int Wp, int Tc, int Hc, int Wc, int Cs, int Ccond, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

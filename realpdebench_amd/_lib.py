@@ -247,6 +247,14 @@ SIGNATURES = {
     "rpb_dmd_gram_groups": (_I, "ili"),
     "rpb_dmd_gram": (_I, "ppp" + "iilii" + "p"),
     "rpb_dmd_predict": (_I, "ppp" + "iiliii" + "p"),
+    "rpb_conv7x_supported": (_I, "liii"),
+    "rpb_conv7x_wz_elems": (_L, "iii"),
+    "rpb_conv7x_wprep": (_I, "pp" + "iii" + "p"),
+    "rpb_conv7x": (_I, "pppp" + "iiiiiiii" + "p"),
+    "rpb_wdno_dec_rows": (_I, ""),
+    "rpb_wdno_dec": (_I, "ppppp" + "iiiiiii" + "iiiii" + "i" + "p"),
+    "rpb_wdno_rec": (_I, "pppp" + "iiiiiii" + "iiiii" + "p"),
+    "rpb_wdno_step": (_I, "ppppppp" + "iiiiiiiiii" + "p"),
 }
 
 _lib = None

@@ -3,6 +3,8 @@
 switches on ``kwargs['model_name']``.  Only the MI355X-native hot-path models are registered."""
 import logging
 
+SUPPORTED = ("fno", "transolver", "galerkin_transformer", "unet", "dpot", "mwt", "deeponet", "cno", "dmd", "wdno")
+
 
 def load_model(train_dataset, device="cpu", **kwargs):
     model_name = kwargs["model_name"]
@@ -81,9 +83,27 @@ def load_model(train_dataset, device="cpu", **kwargs):
             raise ValueError(f"model_name 'dmd' needs the config keys {', '.join(keys)}: missing {', '.join(missing)}")
         model = DMD(n_modes=kwargs["n_modes"], n_predict=kwargs["n_predict"], input_feature=kwargs["input_feature"],
                     n_autoregressive=kwargs["N_autoregressive"], shape_in=input_shape, shape_out=output_shape).to(device)
+    elif model_name == "wdno":
+        from .unet import Unet3d
+        from .wdno import WDNO, WAVELETS, coef_len
+        keys = ("dim", "dim_mults", "wave_type", "pad_mode", "beta_schedule", "sampling_timesteps", "ddim_sampling_eta", "dataset_root",
+                "dataset_name")                                                                                 # load_model.py:24-45
+        missing = [k for k in keys if k not in kwargs]
+        if missing:                     # a bare model_name builds nothing here: say what a wdno.yaml carries, and what else the registry has
+            raise ValueError(f"model_name 'wdno' needs the config keys {', '.join(keys)}: missing {', '.join(missing)} "
+                             f"(the registry's models: {', '.join(SUPPORTED)})")
+        channels = 8 * (input_shape[-1] + output_shape[-1] * output_shape[0] // input_shape[0])                 # load_model.py:24-45
+        if kwargs["wave_type"] not in WAVELETS:
+            raise NotImplementedError(f"WDNO on MI355X: wave_type {kwargs['wave_type']!r} is not built (the configs use {', '.join(WAVELETS)})")
+        # the denoiser sees the padded coefficient mesh: no frame replication, relative-position bias over Tp (wdno_libs/unet.py:510)
+        stride = 2 ** len(kwargs["dim_mults"])
+        Tp = -(-coef_len(input_shape[0], len(WAVELETS[kwargs["wave_type"]][0])) // stride) * stride
+        base_model = Unet3d(dim=kwargs["dim"], dim_mults=kwargs["dim_mults"], channels=channels, in_time=Tp, out_time=Tp).to(device)
+        model = WDNO(base_model, train_dataset, kwargs["dataset_root"], kwargs["dataset_name"], kwargs["wave_type"], kwargs["pad_mode"],
+                     timesteps=1000, beta_schedule=kwargs["beta_schedule"], sampling_timesteps=kwargs["sampling_timesteps"],
+                     ddim_sampling_eta=kwargs["ddim_sampling_eta"]).to(device)
     else:
-        raise ValueError(f"Model {model_name} not supported by the MI355X backend "
-                         "(supported: fno, transolver, galerkin_transformer, unet, dpot, mwt, deeponet, cno, dmd)")
+        raise ValueError(f"Model {model_name} not supported by the MI355X backend (supported: {', '.join(SUPPORTED)})")
     if hip_training:
         model.enable_training(**({"sync_bn": True} if sync_bn else {}))
     return model

@@ -8,7 +8,8 @@ Activations are channels-last token tensors ``[B*T*H*W][C]`` at three resolution
 
 * 3x3x3 convolutions, the (1,4,4)/stride-2 down-sampling convolution, the transposed up-sampling convolution (four
   output-parity classes), every 1x1 convolution / ``nn.Linear``: implicit-GEMM modes of ``rpb_gemm_nt`` on fp32 MFMA;
-  their weight gradients ``rpb_gemm_tn``; the 7x7x7 ``init_conv`` (C_in = 3) as ``rpb_im2col`` + plain GEMM;
+  their weight gradients ``rpb_gemm_tn``; the 7x7x7 ``init_conv`` (C_in = 3) as ``rpb_im2col`` + plain GEMM (with ``init_conv_implicit``,
+  which WDNO sets for its 8 (C_in + C_out r) input channels: the implicit GEMM ``rpb_conv7x`` in the forward that records no backward);
 * GroupNorm(8) + time scale/shift + SiLU: ``rpb_chan_stats`` / ``rpb_affine_silu_*`` (per-(sample, channel) passes) around
   ``rpb_gn_affine_{fwd,bwd}`` (group statistics -> per-(sample, channel) affine and back, ``B x C`` numbers); the time-embedding MLPs
   are small ``rpb_gemm_nt`` / ``rpb_gemm_tn`` calls + ``rpb_silu_*``, the relative-position bias ``rpb_relpos_bias_*`` -- no torch
@@ -212,6 +213,9 @@ class Unet3d(_ModelBase):
         conv("final_conv.1", self.out_dim, dim, 1, 1, 1)
         self._wcache = {}
         self.arith = "f32"              # arithmetic of the eval / rollout forward's 3x3x3 convolutions, see set_arith
+        # WDNO sets this: its state has 8 (C_in + C_out r) channels, and the im2col matrix of the init convolution would be gigabytes per
+        # sample.  On, the forward that records no backward runs init_conv as the implicit GEMM rpb_conv7x where it takes the shape.
+        self.init_conv_implicit = False
 
     # ------------------------------------------------------------------ parameter tree with the reference's names
     def _register(self, name, value, buffer=False):
@@ -281,6 +285,8 @@ class Unet3d(_ModelBase):
             v = d.reshape(d.shape[0], -1).t()
         elif kind == "flat":
             v = d.reshape(d.shape[0], -1)
+        elif kind == "conv7x":         # rpb_conv7x's B-operand planes of the Conv3d weight as it is (WDNO's init_conv)
+            v = ops.conv7x_wprep(d.contiguous())
         elif kind == "init":           # [dim,Cin,k,k,k] -> [dim][ldc] with column = tap*Cin + ci, zero-padded
             k = d.shape[2]
             cols = k * k * k * d.shape[1]
@@ -609,6 +615,29 @@ class Unet3d(_ModelBase):
         tp.add(bwd)
         return y
 
+    def _init_conv_im2col(self, tp, x, B, mesh, Cin):
+        """The 7^3 init convolution as rpb_im2col + a plain GEMM (written for C_in = 3), with its taped backward."""
+        T, H, W = mesh
+        M, dim = B * T * H * W, self.dim
+        Wi = self._w("init", "init_conv.weight")
+        ldc = Wi.shape[1]
+        col = _new(M, ldc, like=x)
+        ops.im2col(x.reshape(M, Cin).contiguous(), col, B, T, H, W, Cin, self.ks, ldc)
+        h = _new(M, dim, like=x)
+        ops.gemm_nt(col, Wi, h, M, dim, ldc, bias=self.p("init_conv.bias").detach())
+        if tp.record:
+            h0 = h
+
+            def bwd_init():
+                gy = tp.grad(h0)
+                dW, db = _wgrad(gy, col, M, dim, ldc)
+                k, cols = self.ks, self.ks ** 3 * Cin
+                tp.pacc("init_conv.weight", dW[:, :cols].reshape(dim, k, k, k, Cin).permute(0, 4, 1, 2, 3).contiguous())
+                tp.pacc("init_conv.bias", db)
+
+            tp.add(bwd_init)
+        return h
+
     # ------------------------------------------------------------------ forward / backward drivers
     @torch.no_grad()
     def _forward_hip(self, x, tp):
@@ -655,26 +684,12 @@ class Unet3d(_ModelBase):
         tp.add(bwd_glue)
         mesh = (T, H, W)
         M = B * T * H * W
-        # ---- init conv (7^3, C_in channels) as im2col + GEMM
-        Wi = self._w("init", "init_conv.weight")
-        ldc = Wi.shape[1]
-        col = _new(M, ldc, like=x)
-        ops.im2col(x.reshape(M, Cin).contiguous(), col, B, T, H, W, Cin, self.ks, ldc)
-        h = _new(M, dim, like=x)
-        ops.gemm_nt(col, Wi, h, M, dim, ldc, bias=self.p("init_conv.bias").detach())
-        if tp.record:
-            h0 = h
-
-            def bwd_init():
-                gy = tp.grad(h0)
-                dW, db = _wgrad(gy, col, M, dim, ldc)
-                k, cols = self.ks, self.ks ** 3 * Cin
-                tp.pacc("init_conv.weight", dW[:, :cols].reshape(dim, k, k, k, Cin).permute(0, 4, 1, 2, 3).contiguous())
-                tp.pacc("init_conv.bias", db)
-
-            tp.add(bwd_init)
+        # ---- init conv (7^3, C_in channels) as im2col + GEMM; WDNO's eval forward: the implicit GEMM (no column matrix)
+        if self.init_conv_implicit and not tp.record and ops.conv7x_supported(M, dim, Cin, self.ks):
+            h = _new(M, dim, like=x)
+            ops.conv7x(x, self._w("conv7x", "init_conv.weight"), h, B, mesh, Cin, dim, self.ks, bias=self.p("init_conv.bias").detach())
         else:
-            del col
+            h = self._init_conv_im2col(tp, x, B, mesh, Cin)
         h = self._temporal_attn(tp, h, "init_temporal_attn.fn.", B, mesh, dim, bias)
         r = h
         skips = []

@@ -1265,3 +1265,56 @@ def dmd_predict(x, M, f):
     _lib.call("rpb_dmd_predict", _p(x), _ptr(M, torch.float64), _p(out), B, T, P, C, f, S, _stream(), label="dmd_predict",
               nbytes=4 * B * (T - 1) * P * C + 4 * B * S * P * f + 8 * B * (T - 1) * S, flops=2 * B * (T - 1) * S * P * f)
     return out
+
+
+# ---- WDNO: the 7x7x7 implicit-GEMM init convolution and the wavelet / sampler kernels (csrc/rpb_conv7x.hip, csrc/rpb_wdno.hip)
+def conv7x_supported(M, N, Ci, KS):
+    return bool(_lib.load().rpb_conv7x_supported(M, N, Ci, KS))
+
+
+def conv7x_wprep(W):
+    """W [N,Ci,KS,KS,KS] (nn.Conv3d's layout) -> its three bf16 planes in MFMA B-operand order (an int16 tensor), prepared once per weight."""
+    N, Ci, KS = W.shape[0], W.shape[1], W.shape[2]
+    wz = torch.empty(_lib.query("rpb_conv7x_wz_elems", N, Ci, KS), dtype=torch.int16, device=W.device)
+    _lib.call("rpb_conv7x_wprep", _p(W), _p(wz, torch.int16), N, Ci, KS, _stream(), label="conv7x_wprep", nbytes=10 * W.numel())
+    return wz
+
+
+def conv7x(x, wz, out, B, mesh, Ci, N, KS, bias=None, ldo=None):
+    """out[M][ldo] = Conv3d(Ci, N, KS, padding=KS // 2)(x [B,T,H,W,Ci]) + bias: the A operand is gathered from x, no column matrix."""
+    T, H, W = mesh
+    M = B * T * H * W
+    _lib.call("rpb_conv7x", _p(x), _ptr(wz, torch.int16), _p(bias), _p(out), B, T, H, W, Ci, N, KS, N if ldo is None else ldo, _stream(),
+              label=f"conv7x[N{N},Ci{Ci},K{KS}]", nbytes=4 * M * Ci * KS * KS + 4 * M * N + 6 * N * Ci * KS ** 3,
+              flops=2 * M * N * Ci * KS ** 3)
+
+
+def wdno_dec_rows():
+    return _lib.query("rpb_wdno_dec_rows")
+
+
+def wdno_dec(x, filt, rescaler, state, B, T, H, W, C, r, L, padded, ld, col0):
+    """state[..., col0 + 8 cv + s] = sub-band s of virtual channel cv of x [B, r T, H, W, C], divided by rescaler[column]"""
+    _lib.call("rpb_wdno_dec", _p(x), _p(filt), _p(rescaler), _p(state), None, B, T, H, W, C, r, L, *padded, ld, col0, 0, _stream(),
+              label="wdno_dec", nbytes=4 * B * r * T * H * W * C * 2)
+
+
+def wdno_dec_max(x, filt, part, B, T, H, W, C, r, L):
+    """part [wdno_dec_rows()][8 C r] = per-column partial maxima of |coefficient| of x [B, r T, H, W, C]"""
+    _lib.call("rpb_wdno_dec", _p(x), _p(filt), None, None, _p(part), B, T, H, W, C, r, L, 0, 0, 0, 0, 0, 1, _stream(),
+              label="wdno_dec_max", nbytes=4 * B * r * T * H * W * C)
+
+
+def wdno_rec(state, filt, rescaler, out, B, T, H, W, C, r, L, padded, ld, col0):
+    """out [B, r T, H, W, C] = the inverse transform of the state columns from col0 on (times their rescaler), cropped"""
+    _lib.call("rpb_wdno_rec", _p(state), _p(filt), _p(rescaler), _p(out), B, T, H, W, C, r, L, *padded, ld, col0, _stream(),
+              label="wdno_rec", nbytes=4 * B * r * T * H * W * C * 2)
+
+
+WDNO_DDIM, WDNO_DDIM_LAST, WDNO_ANCESTRAL, WDNO_QSAMPLE, WDNO_START = range(5)
+
+
+def wdno_step(mode, out, B, padded, coef, Cs, Ccond, img=None, eps=None, cond=None, noise=None, sc=None, out2=None):
+    """The point-wise part of one sampling step (modes: include/rpb.h); ``sc``: the step's scalars in device memory."""
+    _lib.call("rpb_wdno_step", _p(img), _p(eps), _p(cond), _p(noise), _p(sc), _p(out), _p(out2), B, *padded, *coef, Cs, Ccond, int(mode),
+              _stream(), label="wdno_step", nbytes=4 * B * padded[0] * padded[1] * padded[2] * Cs * 4)
